@@ -9,15 +9,21 @@ Contract (driver):  python bench.py --gpus N --steps K --warmup W
   beyond the 256 MiB Infinity Cache) per GPU.  Independent block instances shard one
   per GPU with no data-path collective -> "scaling": "weak".
 Rank 0 prints ONE JSON line.  `value` = samples all ranks processed / max-over-ranks
-time over EXACTLY K steps.  `sustained` repeats the same launch back to back for >= 2 s
-(median / min of the per-launch time over batches: clocks under a long load, not a 4 ms
-burst).  `roofline` prices the FFT kernel against HBM (16 algorithmic bytes per complex
-sample); `cpu_baseline` times the oracle's restatement of the reference's
+time over EXACTLY K steps; `ms_per_step` = wall time of one of the K steps.  Before the
+W warm-up steps the same launch runs back to back for --sustain-s seconds (unless
+--no-sustained), so that the K steps see the clocks of a loaded device.  `roofline` prices the FFT kernel
+against HBM (16 algorithmic bytes per complex sample) from the events of the
+same K steps.  --dump-outputs DIR writes what the last timed step computed (rank 0).
+
+--full adds everything else:  `sustained` times that back-to-back leg (median / min of
+the per-launch time over batches: clocks under a long load, not a 4 ms burst); after the
+headline, `cpu_baseline` times the oracle's restatement of the reference's
 CPU path (clFFT_impl::testCPU) on ONE host core and on ALL of them (threads over frames)
 over a bounded sample, with the host's CPU model and core counts.  `blocks` carries the
 other hot-path blocks (device resident), the host-pointer work() calls (`*_hostpath`,
 PCIe inclusive, never `value`), BASELINE config 1 as SURVEY 8d states it, and the
-sharded X-engine (all-to-all corner turn overlapped with the correlation).
+sharded X-engine (all-to-all corner turn overlapped with the correlation);
+`baseline_configs` sums up the five BASELINE configs.
 """
 import argparse
 import json
@@ -335,6 +341,42 @@ def sustained(fn, samples_per_launch, min_s=2.0, batch=64):
                 "us_per_launch_max": round(per[-1], 2),
                 "hbm_frac_median": round(samples_per_launch * BYTES_PER_SAMPLE / (per[len(per) // 2] * 1e-6) / 1e9 / HBM_PEAK_GBS, 4)}
     return finish
+
+
+def load_clocks(fn, min_s, batch=64):
+    """The launch pattern of `sustained` without its events: >= min_s of back-to-back launches, untimed, queue depth bounded the same way."""
+    import torch
+    torch.cuda.synchronize()
+    marks = []
+    t0 = time.perf_counter()
+    while True:
+        for _ in range(batch):
+            fn()
+        e = torch.cuda.Event()
+        e.record()
+        marks.append(e)
+        if len(marks) % 8 == 0:
+            marks[-8].synchronize()
+            if time.perf_counter() - t0 >= min_s:
+                break
+    torch.cuda.synchronize()
+
+
+DUMP_FRAMES = 1024  # 1024 of the 16384 output frames: 32 MiB of float32
+DUMP_SEED = 20261016
+
+
+def dump_outputs(out_dir, y):
+    """What the timed path hands its caller, the complex64 output frames of the last step, as float32 (frame, bin, re/im): a fixed,
+    seeded sample of DUMP_FRAMES whole frames (the whole output is 512 MiB).  DIR/clFFT_4096_out.npy; its frame numbers in
+    DIR/clFFT_4096_out_frames.npy (float64)."""
+    import torch
+    frames = np.sort(np.random.default_rng(DUMP_SEED).choice(FRAMES_PER_STEP, DUMP_FRAMES, replace=False))
+    idx = torch.as_tensor(frames, dtype=torch.long, device=y.device)
+    sample = y.view(FRAMES_PER_STEP, FFT_N, 2).index_select(0, idx).cpu().numpy().astype(np.float32, copy=False)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "clFFT_4096_out.npy"), sample)
+    np.save(os.path.join(out_dir, "clFFT_4096_out_frames.npy"), frames.astype(np.float64))
 
 
 def hostpath_blocks(pkg, o_taps, dev):
@@ -966,12 +1008,17 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary per-block lines")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--no-sustained", action="store_true", help="skip the >= 2 s back-to-back leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the sustained leg, the other blocks, the sharded X-engine and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (rank 0)")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the secondary per-block lines")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline leg")
+    ap.add_argument("--no-sustained", action="store_true", help="skip the back-to-back leg before the timed steps (with --full: and `sustained`)")
     ap.add_argument("--sustain-s", type=float, default=5.0)
     ap.add_argument("--secondary-timeout", type=int, default=300, help="seconds the secondary legs may take before the line is printed without the rest")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch
     rank, world, local = dist_setup(a.gpus)
@@ -991,12 +1038,18 @@ def main():
     samples_per_step = FRAMES_PER_STEP * FFT_N
     # The long leg runs FIRST: the K timed steps that follow then see the clocks of a loaded device instead of the first
     # milliseconds after idle (the same K-step burst measured cold is ~5 % slower than the 2 s median on this device).
+    # Without --full it is only that warm-up; with it, its own events are read out as `sustained`.
     sus = None
     if not a.no_sustained:
-        sus = sustained(step, samples_per_step, a.sustain_s)
+        if a.full:
+            sus = sustained(step, samples_per_step, a.sustain_s)
+        else:
+            load_clocks(step, a.sustain_s)
     wall, ev = time_steps(step, a.steps, a.warmup, world)
     if sus is not None:
         sus = sus()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, y)
     wall = max_over_ranks(wall, world)
     ev = max_over_ranks(ev, world)
     value = world * samples_per_step * a.steps / wall / 1e6
@@ -1028,15 +1081,19 @@ def main():
                                "%d frames/step/GPU device-resident (1 GiB in+out)" % FRAMES_PER_STEP,
                    "fft_size": FFT_N, "frames_per_step": FRAMES_PER_STEP, "parallelism": "replica-per-gpu x%d" % world},
         "per_gpu_MSamples_per_s": round(value / world, 1),
-        "sustained": sus,
         "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
                      "traffic_source": (pmc or {}).get("source"),
                      "kernel": "k_fft<4096,-1,false,1>", "kernel_us": round(kernel_s * 1e6, 2),
                      "algorithmic_bytes_per_launch": samples_per_step * BYTES_PER_SAMPLE},
-        "cpu_baseline": None,
-        "blocks": extras,
+        "full": a.full,
     }
+    if not a.full:
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        close_dist()
+        return
+    line.update({"sustained": sus, "cpu_baseline": None, "blocks": extras})
     # The headline is measured; everything below is secondary.  A watchdog guarantees the ONE JSON line even if a secondary
     # leg hangs (e.g. a rank lost inside a collective of the sharded X-engine): rank 0 prints what exists, every rank exits.
     import threading
@@ -1124,6 +1181,10 @@ def main():
                                          "clFFT_4096_blackman_shift_MSamples_per_s": harness["clFFT_4096_blackman_shift"]}
     dog.cancel()
     emit()
+    close_dist()
+
+
+def close_dist():
     import torch.distributed as dist
     if dist.is_available() and dist.is_initialized():
         dist.destroy_process_group()

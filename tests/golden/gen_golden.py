@@ -394,5 +394,31 @@ def main():
     print("golden fixtures written, %.1f KiB" % (tot / 1024))
 
 
+def grc_reference(grc_dir, names):
+    """What a saved flowgraph depends on, taken from the reference's own block descriptions (grc/clenabled_<X>.block.yml):
+    block id, parameter ids in file order, and (domain, dtype) of every declared input and output port."""
+    import yaml
+
+    def ports(d, side):
+        return [[x.get("domain"), str(x.get("dtype", "")).replace(" ", "")] for x in d.get(side) or []]
+
+    out = {"_source": "the reference's grc/clenabled_<X>.block.yml: id, parameter ids, port domains and dtypes"}
+    for name in sorted(names):
+        with open(os.path.join(grc_dir, "clenabled_%s.block.yml" % name)) as f:
+            d = yaml.safe_load(f)
+        out[name] = {"id": d["id"], "parameters": [p["id"] for p in d.get("parameters", [])],
+                     "inputs": ports(d, "inputs"), "outputs": ports(d, "outputs")}
+    with open(os.path.join(HERE, "grc_reference.json"), "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+
+
 if __name__ == "__main__":
-    main()
+    import sys
+    if len(sys.argv) == 3 and sys.argv[1] == "--grc-reference":
+        # python tests/golden/gen_golden.py --grc-reference <reference checkout>/grc  (only grc_reference.json, for this repo's 25 blocks)
+        grc_reference(sys.argv[2], [os.path.basename(p)[len("clenabled_"):-len(".block.yml")]
+                                    for p in sorted(os.listdir(os.path.join(HERE, "..", "..", "gr-clenabled_amd", "grc")))
+                                    if p.startswith("clenabled_") and p.endswith(".block.yml")])
+    else:
+        main()

@@ -5,6 +5,7 @@ below), that every ${...} of a template names a declared parameter, and that eac
 positional argument count the declared `make(...)` of host/include/clenabled/<Block>.h (and blocks.py) accepts."""
 import glob
 import inspect
+import json
 import os
 import re
 
@@ -57,7 +58,8 @@ BLOCK_ID = {
     "clMagPhaseToComplex": "clenabled_magphasetocomplex", "clQuadratureDemod": "clenabled_clQuadratureDemod",
     "clxcorrelate_fft_vcf": "clenabled_clxcorrelate_fft_vcf",
 }
-REFERENCE_GRC = "/root/reference/grc"  # present in the build container only; never read by the GPU tests
+# the reference's own block descriptions, reduced to what the tables above freeze (tests/golden/gen_golden.py --grc-reference)
+REFERENCE_GRC = os.path.join(ROOT, "tests", "golden", "grc_reference.json")
 
 
 def split_args(s):
@@ -111,20 +113,20 @@ def test_every_hot_path_block_has_a_description():
     assert names == set(REFERENCE_IDS) == set(BLOCK_ID) and len(BLOCK_ID) == 25
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE_GRC), reason="reference tree not present (GPU box)")
 @pytest.mark.parametrize("name", sorted(BLOCK_ID))
 def test_frozen_tables_equal_the_reference_files(name):
     """The frozen id / parameter tables above are what the reference's own block descriptions say (same file names)."""
-    ref = yaml.safe_load(open(os.path.join(REFERENCE_GRC, "clenabled_%s.block.yml" % name)))
+    with open(REFERENCE_GRC) as f:
+        ref = json.load(f)[name]
     assert ref["id"] == BLOCK_ID[name]
-    ref_params = [p["id"] for p in ref.get("parameters", [])]
+    ref_params = ref["parameters"]
     assert sorted(ref_params) == sorted(REFERENCE_IDS[name]), (ref_params, REFERENCE_IDS[name])
     ours = yaml.safe_load(open(os.path.join(GRC, "clenabled_%s.block.yml" % name)))
     assert ours["id"] == ref["id"]
     # port layout a saved connection depends on: number of declared ports per domain, their dtypes and multiplicities
     for side in ("inputs", "outputs"):
-        r, o = ref.get(side) or [], ours.get(side) or []
-        assert [(x.get("domain"), str(x.get("dtype", "")).replace(" ", "")) for x in r] == \
+        r, o = ref[side], ours.get(side) or []
+        assert [(d, t) for d, t in r] == \
                [(x.get("domain"), str(x.get("dtype", "")).replace(" ", "")) for x in o], side
 
 

@@ -88,7 +88,8 @@ def test_bench_two_rank_dry_run(gpu, tmp_path):
     error.  The numbers of such a run mean nothing (two ranks share a device); under the driver the same code runs over RCCL."""
     import json
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--no-sustained"]
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--no-sustained",
+           "--full"]
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="1", MI355_BENCH_BACKEND="gloo", MI355_BENCH_ONE_DEVICE="1")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=str(tmp_path))
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
