@@ -142,6 +142,15 @@ def lib():
         "mi355_xcorr_fft_destroy": (i, [vp]),
         "mi355_xcorr_fft_work": (i, [vp, i, vp, vp]),
         "mi355_xcorr_fft_work_dev": (i, [vp, i, vp, vp, vp]),
+        "mi355_xcorr_td_plan": (i, [i, i, C.POINTER(C.c_int)]),
+        "mi355_xcorr_td_create": (i, [vp, i, i, i, i, i, pp]),
+        "mi355_xcorr_td_destroy": (i, [vp]),
+        "mi355_xcorr_td_max_shift": (i, [vp]),
+        "mi355_xcorr_td_work": (i, [vp, pp, vp, vp]),
+        "mi355_xcorr_td_submit": (i, [vp, pp]),
+        "mi355_xcorr_td_poll": (i, [vp, vp, vp]),
+        "mi355_xcorr_td_wait": (i, [vp]),
+        "mi355_xcorr_td_work_dev": (i, [vp, i, pp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)  # AttributeError here = header/library mismatch: fail loudly

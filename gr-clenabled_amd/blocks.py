@@ -679,3 +679,110 @@ class clxcorrelate_fft_vcf(_Block):
         op = (C.c_void_p * len(output_items))(*[_dp(y) for y in output_items])
         check(self._L.mi355_xcorr_fft_work_dev(self._h, noutput_items, ip, op, _torch_stream(self.device)), "mi355_xcorr_fft_work_dev")
         return noutput_items
+
+
+class clXCorrelate(_Block):
+    """clXCorrelate::make(openCLPlatformType, devSelector, platformId, devId, setDebug, num_inputs, signal_length, data_type,
+    data_size, max_search_index, decim_frames, async=false) -- include/clenabled/clXCorrelate.h:55-56 (``async`` is a Python
+    keyword: the keyword form here is ``async_``).  Time-domain lag search of inputs 1..num_inputs-1 against input 0; every
+    processed frame publishes a PDU ``{"corrvect": float32[num_inputs-1], "corrective_lags": int32[num_inputs-1]}`` on port
+    "corr" (lib/clXCorrelate_impl.cc:1594-1600), read here with pop_pdu().  decim_frames and async follow work() (:1529-1645):
+    with async the frame is submitted and work() returns at once; the result of the previous submission is published when the
+    next frame is accepted, and frames arriving while a submission runs pass through uncounted."""
+    _destroy = "mi355_xcorr_td_destroy"
+
+    def __init__(self, openCLPlatformType, devSelector, platformId, devId, setDebug, num_inputs, signal_length, data_type,
+                 data_size, max_search_index, decim_frames, async_=False):
+        super().__init__(openCLPlatformType, devSelector, platformId, devId, setDebug)
+        self.num_inputs, self.signal_length = int(num_inputs), int(signal_length)
+        self.data_type, self.decim_frames, self.async_ = int(data_type), int(decim_frames), bool(async_)
+        check(self._L.mi355_xcorr_td_create(self._ctx, self.num_inputs, self.signal_length, self.data_type, int(data_size),
+                                            int(max_search_index), C.byref(self._h)), "mi355_xcorr_td_create")
+        self.max_shift = self._L.mi355_xcorr_td_max_shift(self._h)
+        self._np = np.complex64 if self.data_type == DTYPE_COMPLEX else np.float32
+        self._counter = 1           # cur_frame_counter (:708)
+        self._pending = False       # a submission not yet collected
+        self._ready = None          # its result, once collected, waiting for the next accepted frame
+        self._pdus = []
+
+    def message_ports_out(self):
+        return ["corr"]
+
+    def pop_pdu(self):
+        """The oldest published PDU as a dict, or None."""
+        return self._pdus.pop(0) if self._pdus else None
+
+    def _inputs(self, input_items):
+        if len(input_items) != self.num_inputs:
+            raise ValueError("work(): %d inputs expected" % self.num_inputs)
+        ins = [_host(np.asarray(x).reshape(-1)[:self.signal_length], self._np) for x in input_items]
+        for k, x in enumerate(ins):
+            _need("input %d" % k, x, self.signal_length)
+        return ins, (C.c_void_p * len(ins))(*[_hp(x) for x in ins])
+
+    def _result(self):
+        n = self.num_inputs - 1
+        return np.empty(n, np.float32), np.empty(n, np.int32)
+
+    def _publish(self, corr, lags):
+        self._pdus.append({"corrvect": corr, "corrective_lags": lags})
+
+    def _decimate(self):
+        """True if this frame is processed (:1539-1546 / :1607-1615)."""
+        if self.decim_frames > 1:
+            c = self._counter
+            self._counter += 1
+            if c % self.decim_frames != 0:
+                return False
+            self._counter = 1
+        return True
+
+    def work(self, noutput_items, input_items, output_items=None):
+        """One frame of signal_length items per input; returns signal_length (0 if fewer items are available)."""
+        n = self.signal_length
+        if noutput_items < n:
+            return 0
+        if not self.async_:
+            if not self._decimate():
+                return n
+            ins, ip = self._inputs(input_items)
+            corr, lags = self._result()
+            check(self._L.mi355_xcorr_td_work(self._h, ip, _hp(corr), _hp(lags)), "mi355_xcorr_td_work")
+            self._publish(corr, lags)
+            return n
+        if self._pending:
+            corr, lags = self._result()
+            r = self._L.mi355_xcorr_td_poll(self._h, _hp(corr), _hp(lags))
+            if r < 0:
+                check(r, "mi355_xcorr_td_poll")
+            if r == 0:
+                return n  # still running: the frame passes through, uncounted
+            self._pending, self._ready = False, (corr, lags)
+        if not self._decimate():
+            return n
+        ins, ip = self._inputs(input_items)
+        if self._ready is not None:
+            self._publish(*self._ready)
+            self._ready = None
+        check(self._L.mi355_xcorr_td_submit(self._h, ip), "mi355_xcorr_td_submit")
+        self._pending = True
+        return n
+
+    def wait(self):
+        """Block until the running submission (if any) has finished (test / shutdown aid; its result is published with the next
+        accepted frame)."""
+        check(self._L.mi355_xcorr_td_wait(self._h), "mi355_xcorr_td_wait")
+
+    def work_device(self, nframes, input_items, corr, lags, curves=None):
+        """Device path: input_items = num_inputs CUDA tensors of [nframes][signal_length] items; corr (float32) and lags (int32)
+        of [nframes][num_inputs-1]; curves (float32, [nframes][num_inputs-1][2*max_shift]) or None.  Enqueued on torch's
+        current stream."""
+        nf, nsig = int(nframes), self.num_inputs - 1
+        isz = 8 if self.data_type == DTYPE_COMPLEX else 4
+        if len(input_items) != self.num_inputs:
+            raise ValueError("work_device(): %d inputs expected" % self.num_inputs)
+        ip = (C.c_void_p * self.num_inputs)(*[_dp(x, nf * self.signal_length * isz, "input") for x in input_items])
+        cv = _dp(curves, nf * nsig * 2 * self.max_shift * 4, "curves") if curves is not None else C.c_void_p()
+        check(self._L.mi355_xcorr_td_work_dev(self._h, nf, ip, _dp(corr, nf * nsig * 4, "corr"), _dp(lags, nf * nsig * 4, "lags"), cv,
+                                              _torch_stream(self.device)), "mi355_xcorr_td_work_dev")
+        return nf

@@ -14,6 +14,7 @@
 #include <cstring>
 #include <iostream>
 #include <string>
+#include <vector>
 
 using namespace gr::clenabled;
 
@@ -458,17 +459,55 @@ static int scheduler_contract_test()
 #endif
 }
 
+// --xcorrelate-only (the reference's lib/test-clxcorrelate.cc:349 options: --num_inputs=, --maxsearch=, --input_complex, size):
+// time per work() call of clXCorrelate, and a known answer -- input s is input 0 delayed by 3 s + 1 samples, so its lag is -(3 s + 1)
+static int xcorrelate_test(size_t n, int num_inputs, int maxsearch, bool cplx)
+{
+#ifdef MI355_WITH_GNURADIO
+    (void)n; (void)num_inputs; (void)maxsearch; (void)cplx;
+    printf("--xcorrelate-only reads the published PDUs of the stand-alone build\n");
+    return 2;
+#else
+    const int dt = cplx ? DTYPE_COMPLEX : DTYPE_FLOAT, ds = cplx ? 8 : 4;
+    auto b = clXCorrelate::make(OCLTYPE_GPU, OCLDEVICESELECTOR_SPECIFIC, 0, g_dev, false, num_inputs, (int)n, dt, ds, maxsearch, 1, false);
+    const int delay_max = 3 * (num_inputs - 1) + 1;
+    std::vector<float> base((n + delay_max) * (cplx ? 2 : 1));
+    uint32_t seed = 12345u;
+    for (auto &v : base) { seed = seed * 1664525u + 1013904223u; v = (float)((seed >> 8) & 0xffff) / 65536.0f - 0.5f; }
+    gr_vector_const_void_star in(num_inputs);
+    gr_vector_void_star out;
+    const size_t w = cplx ? 2 : 1;
+    in[0] = base.data() + delay_max * w;
+    for (int s = 1; s < num_inputs; s++) in[s] = base.data() + (delay_max - (3 * s + 1)) * w;  // y[j] = x[j - d]
+    const double sec = time_calls([&] { b->work((int)n, in, out); });
+    gr::shim_message msg, last;
+    int count = 0;
+    while (b->pop_message(msg)) { last = msg; count++; }
+    bool ok = count == g_iter + 1 && last.port == "corr" && (int)last.f32.size() == num_inputs - 1 && (int)last.s32.size() == num_inputs - 1;
+    for (int s = 1; ok && s < num_inputs; s++) ok = last.s32[s - 1] == -(3 * s + 1) && std::fabs(last.f32[s - 1] - 1.0f) < 1e-4f;
+    char name[128];
+    snprintf(name, sizeof name, "clXCorrelate N=%zu, %d %s inputs, max shift %d", n, num_inputs, cplx ? "complex" : "float", b->max_shift());
+    printf("%-60s %10.1f us/call  %s\n", name, sec * 1e6, ok ? "ok" : "MISMATCH");
+    return ok ? 0 : 1;
+#endif
+}
+
 int main(int argc, char **argv)
 {
     size_t n = 8192;  // the reference's default block size
     int fft_size = 4096, ntaps = 65;
-    bool only_fft = false;
+    bool only_fft = false, only_xcorrelate = false, xc_complex = false;
+    int xc_inputs = 2, xc_maxsearch = 512;
     for (int i = 1; i < argc; i++) {
         if (!strncmp(argv[i], "--device=", 9)) g_dev = atoi(argv[i] + 9);
         else if (!strncmp(argv[i], "--iterations=", 13)) g_iter = atoi(argv[i] + 13);
         else if (!strncmp(argv[i], "--fft-size=", 11)) fft_size = atoi(argv[i] + 11);
         else if (!strncmp(argv[i], "--ntaps=", 8)) ntaps = atoi(argv[i] + 8);
         else if (!strcmp(argv[i], "--fft-only")) only_fft = true;
+        else if (!strcmp(argv[i], "--xcorrelate-only")) only_xcorrelate = true;
+        else if (!strncmp(argv[i], "--num_inputs=", 13)) xc_inputs = atoi(argv[i] + 13);
+        else if (!strncmp(argv[i], "--maxsearch=", 12)) xc_maxsearch = atoi(argv[i] + 12);
+        else if (!strcmp(argv[i], "--input_complex")) xc_complex = true;
         else if (!strncmp(argv[i], "--xengine-stream=", 17)) {
             try { return xengine_stream_test(argv[i] + 17); }
             catch (const std::exception &e) { std::cerr << "error: " << e.what() << std::endl; return 2; }
@@ -482,9 +521,15 @@ int main(int argc, char **argv)
             catch (const std::exception &e) { std::cerr << "error: " << e.what() << std::endl; return 2; }
         }
         else if (!strcmp(argv[i], "--help")) {
-            printf("usage: %s [--device=N] [--iterations=N] [--fft-size=N] [--ntaps=N] [--fft-only] [block size]\n", argv[0]);
+            printf("usage: %s [--device=N] [--iterations=N] [--fft-size=N] [--ntaps=N] [--fft-only] [block size]\n"
+                   "       %s --xcorrelate-only [--num_inputs=N] [--maxsearch=N] [--input_complex] [--iterations=N] [signal length]\n",
+                   argv[0], argv[0]);
             return 0;
         } else n = strtoull(argv[i], nullptr, 10);
+    }
+    if (only_xcorrelate) {
+        try { return xcorrelate_test(n, xc_inputs, xc_maxsearch, xc_complex); }
+        catch (const std::exception &e) { std::cerr << "error: " << e.what() << std::endl; return 2; }
     }
     try {
         printf("test-clenabled-mi355: block size %zu, %d iterations, device %d (times include H2D + D2H)\n", n, g_iter, g_dev);

@@ -22,3 +22,25 @@
 #include "clMagPhaseToComplex.h"
 #include "clQuadratureDemod.h"
 #include "clxcorrelate_fft_vcf.h"
+
+namespace gr {
+namespace clenabled {
+
+// gr::clenabled::clXCorrelate -- make() as the reference's include/clenabled/clXCorrelate.h:55-56.  Time-domain lag search of
+// inputs 1..num_inputs-1 against input 0 over frames of signal_length items (data_size bytes each: complex 8 / float 4); no
+// outputs, one message port "corr" carrying {"corrvect": f32vector, "corrective_lags": s32vector} per processed frame
+// (lib/clXCorrelate_impl.cc:1594-1600).  (The reference's per-block header of this name is not installed by this build yet.)
+class CLENABLED_API clXCorrelate : virtual public gr::sync_block {
+public:
+    typedef std::shared_ptr<clXCorrelate> sptr;
+    static sptr make(int openCLPlatformType, int devSelector, int platformId, int devId, bool setDebug, int num_inputs,
+                     int signal_length, int data_type, int data_size, int max_search_index, int decim_frames, bool async = false);
+    // the effective max shift (max_search_index rounded up to a power of two, :716-747)
+    virtual int max_shift() const = 0;
+    virtual int signal_length() const = 0;  // items per frame (the output multiple)
+    // async: block until the running submission (if any) has finished; its result is published with the next accepted frame
+    virtual void wait() = 0;
+};
+
+}  // namespace clenabled
+}  // namespace gr

@@ -47,11 +47,14 @@ public:
     int sizeof_stream_item(int i) const { return d_sizes.empty() ? 0 : d_sizes[(size_t)i < d_sizes.size() ? i : d_sizes.size() - 1]; }
 };
 
-// one published message of the stand-alone build: port, key of the pair, and either a complex vector or an integer
+// one published message of the stand-alone build: port, key of the pair, and either a complex vector or an integer;
+// clXCorrelate's PDU (a dict of "corrvect" f32vector and "corrective_lags" s32vector) is one message with key "corrvect" and both
 struct shim_message {
     std::string port, key;
     std::vector<gr_complex> c32;
     uint64_t u64 = 0;
+    std::vector<float> f32;
+    std::vector<int32_t> s32;
 };
 
 class basic_block_shim {

@@ -193,4 +193,33 @@ PYBIND11_MODULE(clenabled_python, m)
     MI355_BIND_ELEM(clxcorrelate_fft_vcf, py::arg("fftSize"), py::arg("num_inputs"), MI355_DEV_ARGS, py::arg("input_type") = 1);
 #undef MI355_DEV_ARGS
 #undef MI355_BIND_ELEM
+
+    // time-domain lag search (lib/clXCorrelate_impl.cc): no outputs; work() takes the input buffers only
+    py::class_<clXCorrelate SYNC_BASES, std::shared_ptr<clXCorrelate>>(m, "clXCorrelate")
+        .def(py::init(&clXCorrelate::make), py::arg("openCLPlatformType"), py::arg("devSelector"), py::arg("platformId"), py::arg("devId"),
+             py::arg("setDebug"), py::arg("num_inputs"), py::arg("signal_length"), py::arg("data_type"), py::arg("data_size"),
+             py::arg("max_search_index"), py::arg("decim_frames"), py::arg("async_") = false)
+        .def("work",
+             [](clXCorrelate &b, int noutput_items, const std::vector<py::array> &in) {
+                 need(noutput_items >= 0, "noutput_items is negative");
+                 auto i = in_ptrs(in);
+                 const size_t items = (size_t)std::min(noutput_items, b.signal_length());
+                 for (size_t k = 0; k < in.size(); k++)
+                     need((size_t)in[k].nbytes() >= items * item_size(b, true, k), "input " + std::to_string(k) + " holds fewer than a frame");
+                 gr_vector_void_star o;
+                 return b.work(noutput_items, i, o);
+             },
+             py::arg("noutput_items"), py::arg("input_items"))
+        .def("max_shift", &clXCorrelate::max_shift)
+        .def("wait", &clXCorrelate::wait)
+#ifndef MI355_WITH_GNURADIO
+        // the published PDUs of the stand-alone build, oldest first: [(corrvect, corrective_lags), ...]
+        .def("pop_pdus", [](clXCorrelate &b) {
+            py::list out;
+            gr::shim_message msg;
+            while (b.pop_message(msg)) out.append(py::make_tuple(msg.f32, msg.s32));
+            return out;
+        })
+#endif
+        ;
 }

@@ -80,6 +80,7 @@ typedef struct mi355_pfb     mi355_pfb;
 typedef struct mi355_xengine mi355_xengine;
 typedef struct mi355_elem    mi355_elem;
 typedef struct mi355_xcorr_fft mi355_xcorr_fft;
+typedef struct mi355_xcorr_td mi355_xcorr_td;
 
 /* ---------------------------------------------------------------------------
  * Runtime: replaces GRCLBase::InitOpenCL / cleanup (lib/GRCLBase.cpp:17-369,
@@ -384,6 +385,41 @@ int mi355_xcorr_fft_create(mi355_ctx *ctx, int fft_size, int num_inputs, int inp
 int mi355_xcorr_fft_destroy(mi355_xcorr_fft *h);
 int mi355_xcorr_fft_work(mi355_xcorr_fft *h, int nframes, const void *const *inputs, void *const *outputs);
 int mi355_xcorr_fft_work_dev(mi355_xcorr_fft *h, int nframes, const void *const *d_inputs, void *const *d_outputs, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Time-domain lag-search correlator, replaces clXCorrelate (all lines: lib/clXCorrelate_impl.cc):
+ *   make(openCLPlatformType, devSelector, platformId, devId, setDebug, num_inputs, signal_length, data_type, data_size,
+ *        max_search_index, decim_frames, async=false)            include/clenabled/clXCorrelate.h:55-56, ctor :700-747
+ * data_type 1 (complex, data_size 8: magnitudes sqrtf(fmaf(re, re, im*im)), :915) or 2 (float, data_size 4: raw values).
+ * Effective max shift M (:716-747): signal_length and max_search_index even; max_search_index <= 0 takes (int)(0.7*N) rounded
+ * up to even; then rounded up to a power of two (M may reach or exceed N).  Limits here: num_inputs 2..32, signal_length
+ * 2..2^24, M <= 2^24; anything else is an error (the reference exit(1)s).
+ * Per frame of N items and per input s >= 1 (x = input 0, y = input s), g = 0 .. 2M-1, shift = g - M (kernel :851-899):
+ *     curve[g] = sum_j x[j+shift] y[j] / sqrt(sum x^2 * sum y^2)    sums over the overlap 0 <= j, j+shift < N
+ *     curve[g] = -2                                               if that energy product is 0 (no overlap included)
+ *     corr = max curve, lag = argmax - M                            (find_max :1014-1045; ties go to the lowest g, non-finite
+ *                                                                    entries never win; none finite: NaN and lag -M)
+ * A copy of x delayed by d samples gives lag -d.  The PDU of the block (:1594-1600) carries corr / lag of every s >= 1.
+ *   _plan       validation and rounding only (no device): *max_shift = M
+ *   _work       one frame, host pointers inputs[num_inputs] of N items, blocking; corr / lags: num_inputs-1 values
+ *   _submit / _poll / _wait   the async form (:1601-1645): submit enqueues one frame on the handle's stream and returns; poll
+ *               returns 1 (result copied out) or 0 (still running); wait blocks until the submission has finished (poll
+ *               then returns 1).  One submission at a time: submit or work with a result not yet polled is MI355_ERR_STATE.
+ *   _work_dev   d_inputs[k] -> [nframes][N] items; d_corr, d_lags -> [nframes][num_inputs-1]; d_curves (or NULL) ->
+ *               [nframes][num_inputs-1][2M] floats.  Two kernel launches per call (a call needing more than 256 MiB of
+ *               workspace is cut into several pairs); the result of a frame does not depend on how frames are batched.
+ * ------------------------------------------------------------------------------------------------ */
+int mi355_xcorr_td_plan(int signal_length, int max_search_index, int *max_shift);
+int mi355_xcorr_td_create(mi355_ctx *ctx, int num_inputs, int signal_length, int data_type, int data_size, int max_search_index,
+                          mi355_xcorr_td **out);
+int mi355_xcorr_td_destroy(mi355_xcorr_td *h);
+int mi355_xcorr_td_max_shift(const mi355_xcorr_td *h);
+int mi355_xcorr_td_work(mi355_xcorr_td *h, const void *const *inputs, float *corr, int *lags);
+int mi355_xcorr_td_submit(mi355_xcorr_td *h, const void *const *inputs);
+int mi355_xcorr_td_poll(mi355_xcorr_td *h, float *corr, int *lags);
+int mi355_xcorr_td_wait(mi355_xcorr_td *h);
+int mi355_xcorr_td_work_dev(mi355_xcorr_td *h, int nframes, const void *const *d_inputs, float *d_corr, int *d_lags,
+                            float *d_curves, void *stream);
 
 #ifdef __cplusplus
 }

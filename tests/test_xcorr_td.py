@@ -1,0 +1,82 @@
+"""CPU: clXCorrelate (time-domain lag search) -- the float64 oracle against its literal form, the planning of the effective max
+shift, and the C++ block's declarations (stand-alone header and the GNU Radio branch of its unit)."""
+import ctypes as C
+import os
+import subprocess
+import sysconfig
+
+import numpy as np
+import pytest
+
+from conftest import ROOT
+import xcorr_td_ref as ref
+
+INCLUDE = os.path.join(ROOT, "gr-clenabled_amd", "host", "include")
+UNIT = os.path.join(ROOT, "gr-clenabled_amd", "host", "lib", "clXCorrelate_impl.cc")
+
+
+@pytest.mark.parametrize("n,ms,cplx,seed", [(2, 2, True, 0), (6, 6, False, 1), (16, 4, True, 2), (40, 64, False, 3), (64, 16, True, 4),
+                                            (30, 0, False, 5)])
+def test_vectorised_oracle_equals_the_literal_kernel(n, ms, cplx, seed):
+    rng = np.random.default_rng(seed)
+    m = ref.plan(n, ms)
+    if cplx:
+        x = (rng.standard_normal(n) + 1j * rng.standard_normal(n)).astype(np.complex64)
+        y = (rng.standard_normal(n) + 1j * rng.standard_normal(n)).astype(np.complex64)
+    else:
+        x, y = rng.standard_normal(n).astype(np.float32), rng.standard_normal(n).astype(np.float32)
+    y[: n // 3] = 0  # a zero run: exact -2 where the overlap holds only zeros of y
+    a, b = ref.curve_literal(x, y, m), ref.curve(x, y, m)
+    assert np.array_equal(a == -2.0, b == -2.0)
+    assert np.abs(a - b).max() < 1e-12
+
+
+def _plan(pkg, n, ms):
+    L = pkg.lib()
+    out = C.c_int(-7)
+    rc = L.mi355_xcorr_td_plan(n, ms, C.byref(out))
+    return rc, out.value
+
+
+def test_plan_rounds_like_the_reference(pkg):
+    assert _plan(pkg, 8192, 0) == (0, 8192)      # (int)(0.7 * 8192) = 5734 -> 8192
+    assert _plan(pkg, 100, 0) == (0, 128)        # 70 -> 128
+    assert _plan(pkg, 2, 0) == (0, 2)            # 1 -> 2 (even) -> 2
+    assert _plan(pkg, 8192, 300) == (0, 512)
+    assert _plan(pkg, 8192, 512) == (0, 512)
+    assert _plan(pkg, 8192, 6000) == (0, 8192)   # may reach the frame length
+    assert _plan(pkg, 1000, 4000) == (0, 4096)   # or exceed it
+    assert _plan(pkg, 1 << 24, 1 << 24) == (0, 1 << 24)
+    assert _plan(pkg, 8192, -4) == (0, 8192)     # <= 0: the 0.7 rule
+    for n, ms in [(8192, 0), (100, 0), (2, 0), (8192, 300), (1000, 4000), (30, 0)]:
+        assert _plan(pkg, n, ms)[1] == ref.plan(n, ms)
+
+
+def test_plan_refuses_odd_and_out_of_range_values(pkg):
+    for n, ms in [(8191, 0), (8192, 301), (8192, 1), (0, 0), (1, 2), (-2, 2), ((1 << 24) + 2, 0), (8192, (1 << 24) + 2)]:
+        rc, m = _plan(pkg, n, ms)
+        assert rc != 0 and m == 0, (n, ms, rc, m)
+    assert _plan(pkg, 8191, 0)[0] == -1 and _plan(pkg, 8192, 301)[0] == -1   # MI355_ERR_INVALID_ARG (the reference: exit(1))
+    assert _plan(pkg, (1 << 24) + 2, 0)[0] == -3                             # MI355_ERR_UNSUPPORTED
+
+
+def test_make_signature_compiles_against_clenabled_h(tmp_path):
+    src = tmp_path / "tu.cc"
+    src.write_text("#include <clenabled/clenabled.h>\n"
+                   "gr::clenabled::clXCorrelate::sptr (*f)(int, int, int, int, bool, int, int, int, int, int, int, bool) = "
+                   "&gr::clenabled::clXCorrelate::make;\n"
+                   "gr::clenabled::clXCorrelate::sptr six(int n) { return gr::clenabled::clXCorrelate::make(1, 2, 0, 0, false, 2, n, 1, 8, 512, 1); }\n"
+                   "int main() { return 0; }\n")
+    r = subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-Wno-unused-variable", "-fsyntax-only", "-I", INCLUDE,
+                        "-I", os.path.join(ROOT, "include"), str(src)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+
+
+def test_gnuradio_branch_of_the_unit_compiles_against_the_api_model():
+    """-DMI355_WITH_GNURADIO: the PDU is built with pmt::make_dict / dict_add / init_f32vector / init_s32vector (GNU Radio 3.10's pmt
+    API); tests/gr_api_mock/ does not declare those four, so their declarations are force-included from a file of this test."""
+    decls = os.path.join(ROOT, "tests", "gr_pmt_dict_decls.h")
+    r = subprocess.run(["g++", "-std=c++17", "-Wall", "-fsyntax-only", "-DMI355_WITH_GNURADIO", "-include", decls,
+                        "-I", os.path.join(ROOT, "tests", "gr_api_mock"), "-I", INCLUDE, "-I", os.path.join(ROOT, "include"), UNIT],
+                       capture_output=True, text=True)
+    assert r.returncode == 0 and "warning" not in r.stderr, r.stderr
