@@ -76,11 +76,34 @@ __device__ __forceinline__ void load_group(c32 (&v)[16], const void *__restrict_
     }
 }
 
-template <int N, int SIGN, bool REAL, int PF, class G>
+// Dynamic frame-group claims of the persistent schedule (PF = 1, DYN).  The groups are split into kClaimWords contiguous
+// ranges, each handed out by one claim word in a 256-byte segment of its own.  Workgroup w belongs to class (w >> 3) % kClaimWords,
+// so under the round-robin dispatch every class holds workgroups of all eight XCDs.  A workgroup's first kClaimStatic groups
+// are static (its rank in the class, plus multiples of the class size), the rest come one per returning atomic add.
+constexpr int kClaimWords = 8;
+constexpr int kClaimStride = 64;                              // unsigned words from one claim word to the next (256 B)
+constexpr int kClaimStatic = 3;                               // static groups per workgroup = depth of the claim pipeline
+constexpr int kClaimSetWords = kClaimWords * kClaimStride;   // one word set
+constexpr int kClaimSets = 8;                                 // word sets per handle: one per stream that calls it
+// Tuning aid (MI355_FFT_TS, kernels with TS = true only): kTsSlots 64-bit stamps per workgroup of the persistent schedule,
+// 100 MHz wall clock.
+// [0] start, [1] end, [2] groups done, [3] XCC_ID << 16 | SE_ID << 8 | CU_ID, [8 + i] end of the workgroup's group 8 i + 7.
+constexpr int kTsSlots = 64;
+
+__device__ __forceinline__ unsigned hw_cu_id()
+{
+    const unsigned hw = __builtin_amdgcn_s_getreg((3 << 11) | (8 << 6) | 4);    // HW_ID.CU_ID, bits 11:8
+    const unsigned se = __builtin_amdgcn_s_getreg((1 << 11) | (13 << 6) | 4);   // HW_ID.SE_ID, bits 14:13
+    const unsigned xcc = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20);  // XCC_ID, bits 3:0
+    return (xcc << 16) | (se << 8) | hw;
+}
+
+template <int N, int SIGN, bool REAL, int PF, class G, bool DYN = false, bool TS = false>
 __global__ __launch_bounds__(G::TH, (N <= 4096 ? (PF == 2 ? 2 : MI355_FFT_WPE) : 1)) void k_fft(const void *__restrict__ in, c32 *__restrict__ out,
                                                                  const float *__restrict__ window,
                                                                  const c32 *__restrict__ twtab, int nframes, int ngroups,
-                                                                 int shift)
+                                                                 int shift, unsigned *__restrict__ claims,
+                                                                 unsigned long long *__restrict__ ts)
 {
     using P = Plan<N>;
     constexpr int TH = G::TH, PTS = G::PTS, F = G::F, NP = P::NP;
@@ -184,6 +207,13 @@ __global__ __launch_bounds__(G::TH, (N <= 4096 ? (PF == 2 ? 2 : MI355_FFT_WPE) :
         if constexpr (NP > 1 || SMALL) __syncthreads();  // last pass' LDS reads finish before the next group's writes
     };
     const int stride = gridDim.x;
+    static_assert(!TS || PF == 1, "stamps: the persistent schedule only");
+    if constexpr (TS) {
+        if (tid0 == 0) {
+            ts[(size_t)blockIdx.x * kTsSlots + 0] = (unsigned long long)wall_clock64();
+            ts[(size_t)blockIdx.x * kTsSlots + 3] = hw_cu_id();
+        }
+    }
     if constexpr (PF == 2) {
         // Two groups of lead (64 KiB in flight per workgroup, two persistent workgroups per CU): the loop is unrolled three times so
         // that the three register buffers rotate by name, not by moves.
@@ -207,9 +237,67 @@ __global__ __launch_bounds__(G::TH, (N <= 4096 ? (PF == 2 ? 2 : MI355_FFT_WPE) :
             MI355_FFT_STEP(b2, b1)
         }
 #undef MI355_FFT_STEP
+    } else if constexpr (PF == 1 && DYN) {
+        // Dynamic claims (see kClaimWords).  Iteration k transforms g_k and loads g_(k+1); thread 0 issues claim k (-> g_(k+3))
+        // BEFORE those loads and hands claim k-1 (-> g_(k+2)) to the workgroup through claimed[k & 1] before the transform.  Claim
+        // k-1 was issued before the loads of g_k, which the window multiply waits for anyway, so reading its result waits for
+        // nothing the static schedule does not.  The next iteration reads the slot after the barriers of the transform.
+        // Every workgroup makes exactly two failing claims (the one that fails first and the one already issued behind it), so
+        // word c returns each of 0 .. T-1 once, T = size - (kClaimStatic - 2) * m, and the claim that returns T-1 is the
+        // launch's last on that word: its workgroup resets the word to 0 for the next launch.
+        static_assert(NP > 1 || SMALL, "the transform ends with a workgroup barrier");
+        __shared__ int claimed[2];
+        const int nb = (int)gridDim.x >> 3, b = (int)blockIdx.x >> 3, cls = b % kClaimWords;
+        const int m = (nb / kClaimWords + (cls < nb % kClaimWords ? 1 : 0)) * 8 + (nb % kClaimWords == cls ? ((int)gridDim.x & 7) : 0);
+        const int rank = (b / kClaimWords) * 8 + ((int)blockIdx.x & 7);
+        const int lo = (int)((long long)cls * ngroups / kClaimWords), hi = (int)((long long)(cls + 1) * ngroups / kClaimWords);
+        const unsigned nclaim = (unsigned)(hi - lo - kClaimStatic * m);        // claims that succeed (the host checks >= 0)
+        const unsigned last = (unsigned)(hi - lo - (kClaimStatic - 2) * m - 1);  // T - 1
+        unsigned *word = claims + cls * kClaimStride;
+        unsigned t_prev = ~0u;  // (thread 0) result of the previous iteration's claim; ~0u: none
+        bool claiming = true;   // (thread 0) no failing claim seen yet
+        int g = lo + rank, g_next = g + m;
+        [[maybe_unused]] int done = 0;  // (TS)
+        c32 cur[16];
+        load_group<N, REAL, G>(cur, in, g, tid0, nframes, in_xor);
+        for (int k = 0; k < ngroups; k++) {  // (bounded even if a word were corrupted)
+            int tid = tid0;
+            asm volatile("" : "+v"(tid));
+            unsigned t_new = ~0u;
+            if (tid0 == 0 && claiming) t_new = atomicAdd(word, 1u);
+            __builtin_amdgcn_sched_barrier(0);  // the claim goes out before the prefetch
+            c32 nxt[16];
+            if (g_next >= 0) load_group<N, REAL, G>(nxt, in, g_next, tid, nframes, in_xor);
+            __builtin_amdgcn_sched_barrier(0);  // keep the prefetch ahead of the transform
+            if (tid0 == 0 && k > 0) {
+                const bool ok = t_prev < nclaim;
+                claimed[k & 1] = ok ? lo + kClaimStatic * m + (int)t_prev : -1;
+                if (!ok) claiming = false;
+                if (t_prev == last) atomicExch(word, 0u);
+            }
+            t_prev = t_new;
+            body(cur, g, tid);
+            if constexpr (TS) {
+                done++;
+                if (tid0 == 0 && (done & 7) == 0 && (done >> 3) <= kTsSlots - 8)
+                    ts[(size_t)blockIdx.x * kTsSlots + 7 + (done >> 3)] = (unsigned long long)wall_clock64();
+            }
+            if (g_next < 0) break;
+            g = g_next;
+            g_next = k == 0 ? lo + rank + 2 * m : claimed[k & 1];
+#pragma unroll
+            for (int s = 0; s < 16; s++) cur[s] = nxt[s];
+        }
+        if constexpr (TS) {
+            if (tid0 == 0) {
+                ts[(size_t)blockIdx.x * kTsSlots + 1] = (unsigned long long)wall_clock64();
+                ts[(size_t)blockIdx.x * kTsSlots + 2] = (unsigned long long)done;
+            }
+        }
     } else {
         // PF == 1: the loads of the NEXT frame group are issued before the current group is transformed
         c32 cur[16];
+        [[maybe_unused]] int done = 0;  // (TS)
         if ((int)blockIdx.x < ngroups) load_group<N, REAL, G>(cur, in, blockIdx.x, tid0, nframes, in_xor);
         for (int grp = blockIdx.x; grp < ngroups; grp += stride) {
             int tid = tid0;
@@ -223,9 +311,20 @@ __global__ __launch_bounds__(G::TH, (N <= 4096 ? (PF == 2 ? 2 : MI355_FFT_WPE) :
                 load_group<N, REAL, G>(cur, in, grp, tid, nframes, in_xor);
             }
             body(cur, grp, tid);
+            if constexpr (TS) {
+                done++;
+                if (tid0 == 0 && (done & 7) == 0 && (done >> 3) <= kTsSlots - 8)
+                    ts[(size_t)blockIdx.x * kTsSlots + 7 + (done >> 3)] = (unsigned long long)wall_clock64();
+            }
             if constexpr (PF == 1) {
 #pragma unroll
                 for (int s = 0; s < 16; s++) cur[s] = nxt[s];
+            }
+        }
+        if constexpr (TS) {
+            if (tid0 == 0) {
+                ts[(size_t)blockIdx.x * kTsSlots + 1] = (unsigned long long)wall_clock64();
+                ts[(size_t)blockIdx.x * kTsSlots + 2] = (unsigned long long)done;
             }
         }
     }
@@ -933,9 +1032,55 @@ __global__ __launch_bounds__(NR / 2) void k_fft_tile_h(const void *__restrict__ 
     }
 }
 
+// tuning aid (MI355_FFT_TS): device buffer of the per-workgroup stamps of the persistent schedule, and their dump after a
+// synchronous launch.  MI355_FFT_TS_FILE names a file that each such launch appends to: a header line, then one line per
+// workgroup "block hw start end groups t8 t16 ..." in raw 100 MHz ticks (tools/fft_stamps.py reads it).
+unsigned long long *stamps_buffer(int grid)
+{
+    static std::mutex mu;
+    static unsigned long long *d = nullptr;
+    static int cap = 0;
+    std::lock_guard<std::mutex> g(mu);
+    if (cap < grid) {
+        if (d) (void)hipFree(d);
+        d = nullptr;
+        cap = 0;
+        if (hipMalloc(&d, (size_t)grid * kTsSlots * 8) != hipSuccess) return nullptr;
+        cap = grid;
+    }
+    return d;
+}
+
+int dump_stamps(const unsigned long long *d_ts, int n, int sign, int sched, int grid, int ngroups, hipStream_t st)
+{
+    MI355_HIP(hipStreamSynchronize(st));
+    std::vector<unsigned long long> h((size_t)grid * kTsSlots);
+    MI355_HIP(hipMemcpy(h.data(), d_ts, h.size() * 8, hipMemcpyDeviceToHost));
+    unsigned long long t0 = ~0ull, t1 = 0;
+    for (int b = 0; b < grid; b++) {
+        t0 = std::min(t0, h[(size_t)b * kTsSlots]);
+        t1 = std::max(t1, h[(size_t)b * kTsSlots + 1]);
+    }
+    fprintf(stderr, "[fft stamps] N %d sign %d sched %d: %d workgroups, %d groups, first start to last end %.2f us\n", n, sign, sched, grid,
+            ngroups, (double)(t1 - t0) * 0.01);
+    if (const char *path = getenv("MI355_FFT_TS_FILE")) {
+        if (FILE *f = fopen(path, "a")) {
+            fprintf(f, "# n %d sign %d sched %d grid %d ngroups %d\n", n, sign, sched, grid, ngroups);
+            for (int b = 0; b < grid; b++) {
+                const unsigned long long *r = &h[(size_t)b * kTsSlots];
+                fprintf(f, "%d %llu %llu %llu %llu", b, r[3], r[0], r[1], r[2]);
+                for (int i = 8; i < kTsSlots && r[i]; i++) fprintf(f, " %llu", r[i]);
+                fprintf(f, "\n");
+            }
+            fclose(f);
+        }
+    }
+    return MI355_OK;
+}
+
 template <int N, class G>
 int launch_g(mi355_ctx *ctx, int sign, const void *in, void *out, const float *window, const void *tw, int nframes, int shift,
-             int real_in, hipStream_t st)
+             int real_in, hipStream_t st, unsigned *claims)
 {
     constexpr int F = G::F, TH = G::TH, WAVES = TH / 64;
     int ngroups = (nframes + F - 1) / F;
@@ -956,33 +1101,50 @@ int launch_g(mi355_ctx *ctx, int sign, const void *in, void *out, const float *w
     if (const char *e = getenv("MI355_FFT_WG_PER_CU")) {
         if (atoi(e) > 0) grid = ngroups < cus * atoi(e) ? ngroups : cus * atoi(e);
     }
-#define LAUNCH_FFT(SG, RL)                                                                                              \
-    do {                                                                                                                     \
-        if (pf == 2)                                                                                                         \
-            hipLaunchKernelGGL((k_fft<N, SG, RL, 2, G>), dim3(grid), dim3(TH), 0, st, in, (c32 *)out, window, (const c32 *)tw, \
-                               nframes, ngroups, shift);                                                                     \
-        else if (pf == 1)                                                                                                    \
-            hipLaunchKernelGGL((k_fft<N, SG, RL, 1, G>), dim3(grid), dim3(TH), 0, st, in, (c32 *)out, window, (const c32 *)tw, \
-                               nframes, ngroups, shift);                                                                     \
-        else                                                                                                                 \
-            hipLaunchKernelGGL((k_fft<N, SG, RL, 0, G>), dim3(grid), dim3(TH), 0, st, in, (c32 *)out, window,                \
-                               (const c32 *)tw, nframes, ngroups, shift);                                                    \
+    // Persistent schedule: frame groups by dynamic claims (kClaimWords, 1) or by the static grid stride (0); MI355_FFT_SCHED (per
+    // call) picks one, both give bit-identical results.  Claims by default only at N = 4096, where the static split's workgroups
+    // ended up to 25 us apart (tools/fft_stamps.py): 181.4 -> 169.1 us per GiB in one process.  At 256 ... 2048 points they
+    // measured 1-4 % slower (DESIGN_EXPERIMENTS.md R7.1).  Claims need a word set (the caller's, NULL: none) and every
+    // workgroup's static groups.
+    int sched = getenv("MI355_FFT_SCHED") ? atoi(getenv("MI355_FFT_SCHED")) : (N == 4096 ? 1 : 0);
+    // (every class needs a workgroup, grid >= 8 * kClaimWords, or its groups would be left undone)
+    if (!(pf == 1 && persistent2 && claims && grid >= 8 * kClaimWords &&
+          ngroups / kClaimWords >= kClaimStatic * ((grid + 8 * kClaimWords - 1) / (8 * kClaimWords)) * 8))
+        sched = 0;
+    if (sched != 1) claims = nullptr;
+    unsigned long long *ts = nullptr;
+    if (pf == 1 && getenv("MI355_FFT_TS")) {
+        ts = stamps_buffer(grid);
+        if (ts) MI355_HIP(hipMemsetAsync(ts, 0, (size_t)grid * kTsSlots * 8, st));
+    }
+#define LAUNCH_FFT_K(...) hipLaunchKernelGGL((k_fft<__VA_ARGS__>), dim3(grid), dim3(TH), 0, st, in, (c32 *)out, window, (const c32 *)tw, \
+                                                nframes, ngroups, shift, claims, ts)
+#define LAUNCH_FFT(SG, RL)                                                                      \
+    do {                                                                                             \
+        if (pf == 2) LAUNCH_FFT_K(N, SG, RL, 2, G);                                                  \
+        else if (pf == 1 && sched == 1 && ts) LAUNCH_FFT_K(N, SG, RL, 1, G, true, true);             \
+        else if (pf == 1 && sched == 1) LAUNCH_FFT_K(N, SG, RL, 1, G, true);                         \
+        else if (pf == 1 && ts) LAUNCH_FFT_K(N, SG, RL, 1, G, false, true);                          \
+        else if (pf == 1) LAUNCH_FFT_K(N, SG, RL, 1, G);                                             \
+        else LAUNCH_FFT_K(N, SG, RL, 0, G);                                                          \
     } while (0)
     if (sign < 0) { if (real_in) LAUNCH_FFT(-1, true); else LAUNCH_FFT(-1, false); }
     else          { if (real_in) LAUNCH_FFT(1, true);  else LAUNCH_FFT(1, false); }
 #undef LAUNCH_FFT
+#undef LAUNCH_FFT_K
     MI355_HIP(hipGetLastError());
+    if (ts) return dump_stamps(ts, N, sign, sched, grid, ngroups, st);
     return MI355_OK;
 }
 
 template <int N>
 int launch_n(mi355_ctx *ctx, int sign, const void *in, void *out, const float *window, const void *tw, int nframes, int shift,
-             int real_in, hipStream_t st)
+             int real_in, hipStream_t st, unsigned *claims)
 {
     if constexpr (N >= 16 && N <= 1024) {
         // MI355_FFT_WAVE_GEO=1: one-wave workgroups (no workgroup barriers); measured slower for N >= 256, off by default
         static const bool wave = getenv("MI355_FFT_WAVE_GEO") ? atoi(getenv("MI355_FFT_WAVE_GEO")) != 0 : false;
-        if (wave) return launch_g<N, GeoW<N>>(ctx, sign, in, out, window, tw, nframes, shift, real_in, st);
+        if (wave) return launch_g<N, GeoW<N>>(ctx, sign, in, out, window, tw, nframes, shift, real_in, st, claims);
     }
     if constexpr (N == 32768) return launch_s<N>(ctx, sign, in, out, window, tw, nframes, shift, real_in, st);
     else if constexpr (N == 8192 || N == 16384) {
@@ -990,14 +1152,15 @@ int launch_n(mi355_ctx *ctx, int sign, const void *in, void *out, const float *w
         static const bool whole = getenv("MI355_FFT_WHOLE_FRAME") ? atoi(getenv("MI355_FFT_WHOLE_FRAME")) != 0 : false;
         if (!whole) return launch_s<N>(ctx, sign, in, out, window, tw, nframes, shift, real_in, st);
     }
-    if constexpr (N != 32768) return launch_g<N, Geo<N>>(ctx, sign, in, out, window, tw, nframes, shift, real_in, st);
+    if constexpr (N != 32768) return launch_g<N, Geo<N>>(ctx, sign, in, out, window, tw, nframes, shift, real_in, st, claims);
 }
 
+// claims: a word set of the calling handle for the dynamic schedule of the persistent path (NULL: the static schedule)
 int launch_fft(mi355_ctx *ctx, int n, int sign, const void *in, void *out, const float *window, const void *tw, int nframes,
-               int shift, int real_in, hipStream_t st)
+               int shift, int real_in, hipStream_t st, unsigned *claims = nullptr)
 {
     switch (n) {
-#define CASE_N(NN) case NN: return launch_n<NN>(ctx, sign, in, out, window, tw, nframes, shift, real_in, st)
+#define CASE_N(NN) case NN: return launch_n<NN>(ctx, sign, in, out, window, tw, nframes, shift, real_in, st, claims)
         CASE_N(2); CASE_N(4); CASE_N(8); CASE_N(16); CASE_N(32); CASE_N(64); CASE_N(128); CASE_N(256); CASE_N(512);
         CASE_N(1024); CASE_N(2048); CASE_N(4096); CASE_N(8192); CASE_N(16384); CASE_N(32768);
 #undef CASE_N
@@ -1033,6 +1196,13 @@ struct mi355_fft {
     std::mutex ws_lock;
     hipEvent_t ws_done = nullptr;
     bool ws_used = false;
+    // Claim words of the dynamic persistent schedule (one pass, n <= 4096): kClaimSets word sets, zeroed at create; every launch
+    // leaves its words at zero again.  A stream keeps the set it was given first, so two calls in flight at once never share
+    // one.  Calls from further streams, and calls captured into a graph, take the static schedule (same results); see claim_words.
+    unsigned *d_claims = nullptr;
+    hipStream_t claim_st[kClaimSets] = {};
+    int nclaim_st = 0;
+    std::mutex claim_lock;
 };
 
 namespace {
@@ -1467,13 +1637,37 @@ int launch_mr_tile(mi355_fft *h, const void *in, void *out, int nframes, hipStre
     return ws_release(h, st);
 }
 
+// The claim word set of calls on stream st (NULL: the static schedule, same results).  The table is keyed by the stream's
+// handle value and never released, so its limits are:
+//  - the first kClaimSets streams that call a handle get a set each; calls from any further stream take the static schedule;
+//  - hipStreamPerThread names a different stream in every thread, so it takes the static schedule;
+//  - a stream destroyed while this handle's kernel still runs on it, and a new stream that gets the same handle value, would
+//    share a set while both are in flight.  Nothing in this project destroys a stream with work of its own in flight.
+unsigned *claim_words(mi355_fft *h, hipStream_t st)
+{
+    if (!h->d_claims || st == hipStreamPerThread) return nullptr;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) != hipSuccess) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    if (cs != hipStreamCaptureStatusNone) return nullptr;
+    std::lock_guard<std::mutex> g(h->claim_lock);
+    for (int i = 0; i < h->nclaim_st; i++)
+        if (h->claim_st[i] == st) return h->d_claims + (size_t)i * kClaimSetWords;
+    if (h->nclaim_st == kClaimSets) return nullptr;
+    h->claim_st[h->nclaim_st] = st;
+    return h->d_claims + (size_t)h->nclaim_st++ * kClaimSetWords;
+}
+
 int launch_handle(mi355_fft *h, const void *in, void *out, int nvec, hipStream_t st)
 {
     if (h->mrt.n) return launch_mr_tile(h, in, out, nvec, st);
     if (h->mr.n) return mi355_fft_mr_launch(h->mr, h->ctx, h->sign, in, out, h->d_window, nvec, h->shift, h->dtype == MI355_DTYPE_FLOAT, st);
     if (h->m) return launch_bluestein(h, in, out, nvec, st);
     if (h->n > 32768 || (h->n == 32768 && h->two_kernel)) return launch_big(h, in, out, nvec, st);
-    return launch_fft(h->ctx, h->n, h->sign, in, out, h->d_window, h->d_tw, nvec, h->shift, h->dtype == MI355_DTYPE_FLOAT, st);
+    return launch_fft(h->ctx, h->n, h->sign, in, out, h->d_window, h->d_tw, nvec, h->shift, h->dtype == MI355_DTYPE_FLOAT, st,
+                      claim_words(h, st));
 }
 
 // iterative radix-2 FFT in double (host side, used once per handle for the chirp spectrum)
@@ -1660,6 +1854,11 @@ extern "C" int mi355_fft_create(mi355_ctx *ctx, int fft_size, int direction, con
         if (mi355_upload(ctx, h->d_window, w.data(), sizeof(float) * (size_t)fft_size) != hipSuccess)
             return fail(MI355_ERR_HIP);
     }
+    if (pow2 && fft_size <= 4096) {
+        const std::vector<unsigned> zero((size_t)kClaimSets * kClaimSetWords, 0u);
+        if (hipMalloc(&h->d_claims, zero.size() * sizeof(unsigned)) != hipSuccess) return fail(MI355_ERR_NOMEM);
+        if (mi355_upload(ctx, h->d_claims, zero.data(), zero.size() * sizeof(unsigned)) != hipSuccess) return fail(MI355_ERR_HIP);
+    }
     int rc = h->pipe.init(ctx);
     if (rc) return fail(rc);
     if (!pow2) {
@@ -1789,7 +1988,7 @@ extern "C" int mi355_fft_destroy(mi355_fft *h)
     if (h->mr.d_tw) (void)hipFree(h->mr.d_tw);
     if (h->mrt.a.d_tw) (void)hipFree(h->mrt.a.d_tw);
     if (h->mrt.b.d_tw) (void)hipFree(h->mrt.b.d_tw);
-    for (void *p : {h->d_pre, h->d_post, h->d_bspec, h->d_twm_f, h->d_twm_i, (void *)h->d_ones, h->d_wa, h->d_wb})
+    for (void *p : {h->d_pre, h->d_post, h->d_bspec, h->d_twm_f, h->d_twm_i, (void *)h->d_ones, h->d_wa, h->d_wb, (void *)h->d_claims})
         if (p) (void)hipFree(p);
     if (h->ws_done) (void)hipEventDestroy(h->ws_done);
     if (h->sub_f) (void)mi355_fft_destroy(h->sub_f);
