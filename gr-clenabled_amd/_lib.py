@@ -54,6 +54,7 @@ def lib():
     L = C.CDLL(LIB_PATH)
     vp, i, sz, f = C.c_void_p, C.c_int, C.c_size_t, C.c_float
     pp = C.POINTER(C.c_void_p)
+    d, dp = C.c_double, C.POINTER(C.c_double)
     sigs = {
         "mi355_strerror": (C.c_char_p, [i]),
         "mi355_last_error": (C.c_char_p, []),
@@ -151,6 +152,21 @@ def lib():
         "mi355_xcorr_td_poll": (i, [vp, vp, vp]),
         "mi355_xcorr_td_wait": (i, [vp]),
         "mi355_xcorr_td_work_dev": (i, [vp, i, pp, vp, vp, vp, vp]),
+        "mi355_sigsource_create": (i, [vp, i, d, i, d, f, pp]),
+        "mi355_sigsource_destroy": (i, [vp]),
+        "mi355_sigsource_set_frequency": (i, [vp, d]),
+        "mi355_sigsource_get_state": (i, [vp, dp, dp]),
+        "mi355_sigsource_set_phase": (i, [vp, d]),
+        "mi355_sigsource_work": (i, [vp, sz, vp]),
+        "mi355_sigsource_work_dev": (i, [vp, sz, vp, vp]),
+        "mi355_costas_plan": (i, [f, i, C.POINTER(f), C.POINTER(f)]),
+        "mi355_costas_create": (i, [vp, f, i, i, pp]),
+        "mi355_costas_destroy": (i, [vp]),
+        "mi355_costas_set_loop_bandwidth": (i, [vp, f]),
+        "mi355_costas_get_state": (i, [vp, vp, vp, vp]),
+        "mi355_costas_set_state": (i, [vp, vp, vp]),
+        "mi355_costas_work": (i, [vp, sz, vp, vp, vp]),
+        "mi355_costas_work_dev": (i, [vp, sz, vp, vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)  # AttributeError here = header/library mismatch: fail loudly

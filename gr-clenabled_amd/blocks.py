@@ -786,3 +786,130 @@ class clXCorrelate(_Block):
         check(self._L.mi355_xcorr_td_work_dev(self._h, nf, ip, _dp(corr, nf * nsig * 4, "corr"), _dp(lags, nf * nsig * 4, "lags"), cv,
                                               _torch_stream(self.device)), "mi355_xcorr_td_work_dev")
         return nf
+
+
+class clSignalSource(_Block):
+    """clSignalSource::make(idataType, openCLPlatformType, devSelector, platformId, devId, samp_rate, waveform, freq, amplitude,
+    setDebug=0) -- include/clenabled/clSignalSource.h:49-50.  NCO / tone generator: waveform 1 cos, 2 sin (complex output carries
+    both); the phase advances from call to call and is kept by set_frequency()."""
+    _destroy = "mi355_sigsource_destroy"
+
+    def __init__(self, idataType, openCLPlatformType, devSelector, platformId, devId, samp_rate, waveform, freq, amplitude, setDebug=0):
+        super().__init__(openCLPlatformType, devSelector, platformId, devId, setDebug)
+        self.dtype = int(idataType)
+        check(self._L.mi355_sigsource_create(self._ctx, self.dtype, float(samp_rate), int(waveform), float(freq), float(amplitude),
+                                             C.byref(self._h)), "mi355_sigsource_create")
+
+    def set_frequency(self, freq):
+        check(self._L.mi355_sigsource_set_frequency(self._h, float(freq)), "mi355_sigsource_set_frequency")
+
+    def set_phase(self, angle_pos):
+        check(self._L.mi355_sigsource_set_phase(self._h, float(angle_pos)), "mi355_sigsource_set_phase")
+
+    def get_state(self):
+        """(angle_pos, angle_rate_inc): the phase of the next call's first item and the phase step per item, in radians"""
+        pos, inc = C.c_double(), C.c_double()
+        check(self._L.mi355_sigsource_get_state(self._h, C.byref(pos), C.byref(inc)), "mi355_sigsource_get_state")
+        return pos.value, inc.value
+
+    def work(self, noutput_items, input_items, output_items):
+        c = _host(output_items[0], _NP_OF[self.dtype], writable=True)
+        _need("output", c, noutput_items)
+        check(self._L.mi355_sigsource_work(self._h, noutput_items, _hp(c)), "mi355_sigsource_work")
+        return noutput_items
+
+    testOpenCL = work
+
+    def work_device(self, noutput_items, input_items, output_items):
+        nb = int(noutput_items) * np.dtype(_NP_OF[self.dtype]).itemsize
+        check(self._L.mi355_sigsource_work_dev(self._h, noutput_items, _dp(output_items[0], nb, "output"), _torch_stream(self.device)),
+              "mi355_sigsource_work_dev")
+        return noutput_items
+
+
+class clCostasLoop(_Block):
+    """clCostasLoop::make(openCLPlatformType, devSelector, platformId, devId, loop_bw, order, setDebug=0) --
+    include/clenabled/clCostasLoop.h:52; order 2 (BPSK) or 4 (QPSK).  num_streams (not in the reference) runs one loop per stream
+    of an item-major multiplex, item i of stream s at [i * num_streams + s] -- the channelizer's output layout.  Output 0 is the
+    de-rotated stream; the optional output 1 is the loop frequency (float, rad/item) per item.  The loop state lives on the
+    device, so work_device() calls chain."""
+    _destroy = "mi355_costas_destroy"
+
+    def __init__(self, openCLPlatformType, devSelector, platformId, devId, loop_bw, order, setDebug=0, num_streams=1):
+        L = lib()
+        a, b = C.c_float(), C.c_float()
+        rc = L.mi355_costas_plan(float(loop_bw), int(order), C.byref(a), C.byref(b))
+        if rc == -1:
+            raise ValueError(L.mi355_last_error().decode())  # std::invalid_argument, lib/clCostasLoop_impl.cc:80-83
+        check(rc, "mi355_costas_plan")
+        super().__init__(openCLPlatformType, devSelector, platformId, devId, setDebug)
+        self.order, self.num_streams, self._bw = int(order), int(num_streams), float(loop_bw)
+        self._alpha, self._beta = a.value, b.value
+        check(self._L.mi355_costas_create(self._ctx, self._bw, self.order, self.num_streams, C.byref(self._h)), "mi355_costas_create")
+
+    def set_loop_bandwidth(self, loop_bw):
+        a, b = C.c_float(), C.c_float()
+        check(self._L.mi355_costas_set_loop_bandwidth(self._h, float(loop_bw)), "mi355_costas_set_loop_bandwidth")
+        check(self._L.mi355_costas_plan(float(loop_bw), self.order, C.byref(a), C.byref(b)), "mi355_costas_plan")
+        self._bw, self._alpha, self._beta = float(loop_bw), a.value, b.value
+
+    def get_loop_bandwidth(self):
+        return self._bw
+
+    def get_alpha(self):
+        return self._alpha
+
+    def get_beta(self):
+        return self._beta
+
+    def get_state(self):
+        """(phase, freq, error): float64 arrays of num_streams values; waits for the block's last call"""
+        st = [np.empty(self.num_streams, np.float64) for _ in range(3)]
+        check(self._L.mi355_costas_get_state(self._h, _hp(st[0]), _hp(st[1]), _hp(st[2])), "mi355_costas_get_state")
+        return tuple(st)
+
+    def set_state(self, phase=None, freq=None):
+        """phase / freq: a scalar (every stream) or num_streams values; None leaves that part as it is"""
+        arrs = [None if v is None else np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.float64), (self.num_streams,)))
+                for v in (phase, freq)]
+        check(self._L.mi355_costas_set_state(self._h, *[C.c_void_p() if a is None else _hp(a) for a in arrs]), "mi355_costas_set_state")
+
+    def get_phase(self):
+        p = self.get_state()[0]
+        return float(p[0]) if self.num_streams == 1 else p
+
+    def get_frequency(self):
+        f = self.get_state()[1]
+        return float(f[0]) if self.num_streams == 1 else f
+
+    def set_phase(self, phase):
+        self.set_state(phase=phase)
+
+    def set_frequency(self, freq):
+        self.set_state(freq=freq)
+
+    def work(self, noutput_items, input_items, output_items):
+        n = int(noutput_items) * self.num_streams
+        a = _host(input_items[0], np.complex64)
+        c = _host(output_items[0], np.complex64, writable=True)
+        _need("input", a, n)
+        _need("output", c, n)
+        fo = None
+        if len(output_items) > 1 and output_items[1] is not None:
+            fo = _host(output_items[1], np.float32, writable=True)
+            _need("frequency output", fo, n)
+        check(self._L.mi355_costas_work(self._h, noutput_items, _hp(a), _hp(c), _hp(fo) if fo is not None else C.c_void_p()),
+              "mi355_costas_work")
+        return noutput_items
+
+    testOpenCL = work
+
+    def work_device(self, noutput_items, input_items, output_items):
+        n = int(noutput_items) * self.num_streams
+        fo = C.c_void_p()
+        if len(output_items) > 1 and output_items[1] is not None:
+            fo = _dp(output_items[1], n * 4, "frequency output")
+        check(self._L.mi355_costas_work_dev(self._h, noutput_items, _dp(input_items[0], n * 8, "input"),
+                                            _dp(output_items[0], n * 8, "output"), fo, _torch_stream(self.device)),
+              "mi355_costas_work_dev")
+        return noutput_items

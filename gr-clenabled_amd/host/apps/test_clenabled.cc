@@ -492,11 +492,47 @@ static int xcorrelate_test(size_t n, int num_inputs, int maxsearch, bool cplx)
 #endif
 }
 
+// --loops-only: time per work() call and a known answer for the NCO and the carrier loop.  clSignalSource at samp_rate / 8 steps
+// pi/4 per item and every call of a multiple of 8 items starts at a multiple of 2 pi: items 1 and 2 are A (cos, sin)(pi/4) and
+// (0, A).  clCostasLoop gets one QPSK point turning at 0.01 rad/item: locked, the output rests on a constellation point
+// (+-1, +-1)/sqrt 2 and the loop frequency is the offset.
+static int loops_test(size_t n)
+{
+    n = (n + 7) / 8 * 8;
+    const float A = 2.5f;
+    std::vector<gr_complex> y(n);
+    gr_vector_const_void_star none;
+    gr_vector_void_star out = {y.data()};
+    auto src = clSignalSource::make(DTYPE_COMPLEX, OCLTYPE_GPU, OCLDEVICESELECTOR_SPECIFIC, 0, g_dev, 8000.0, 1, 1000.0, A);
+    double t = time_calls([&] { src->work((int)n, none, out); });
+    const float h = A * (float)M_SQRT1_2;
+    report("clSignalSource (complex, samp_rate / 8)", n, t,
+           close_to(y[0], gr_complex(A, 0), 1e-4f) && close_to(y[1], gr_complex(h, h), 1e-4f) && close_to(y[2], gr_complex(0, A), 1e-4f) &&
+               close_to(y[n - 1], gr_complex(h, -h), 1e-4f));
+    const double offset = 0.01;
+    std::vector<gr_complex> x(n);
+    for (size_t i = 0; i < n; i++) {
+        const double ph = M_PI / 4 + 0.3 + offset * (double)i;
+        x[i] = gr_complex((float)cos(ph), (float)sin(ph));
+    }
+    std::vector<float> f(n);
+    gr_vector_const_void_star in = {x.data()};
+    gr_vector_void_star out2 = {y.data(), f.data()};
+    auto loop = clCostasLoop::make(OCLTYPE_GPU, OCLDEVICESELECTOR_SPECIFIC, 0, g_dev, 0.0628f, 4);
+    t = time_calls([&] { loop->work((int)n, in, out2); });
+    const gr_complex last = y[n - 1];
+    const bool on_point = n >= 2048 && std::fabs(std::fabs(last.real()) - (float)M_SQRT1_2) < 0.02f &&
+                          std::fabs(std::fabs(last.imag()) - (float)M_SQRT1_2) < 0.02f;
+    report("clCostasLoop (order 4, one stream)", n, t,
+           on_point && std::fabs(f[n - 1] - offset) < 0.1 * offset && std::fabs(loop->get_frequency() - f[n - 1]) < 1e-6f);
+    return g_fail ? 1 : 0;
+}
+
 int main(int argc, char **argv)
 {
     size_t n = 8192;  // the reference's default block size
     int fft_size = 4096, ntaps = 65;
-    bool only_fft = false, only_xcorrelate = false, xc_complex = false;
+    bool only_fft = false, only_xcorrelate = false, xc_complex = false, only_loops = false;
     int xc_inputs = 2, xc_maxsearch = 512;
     for (int i = 1; i < argc; i++) {
         if (!strncmp(argv[i], "--device=", 9)) g_dev = atoi(argv[i] + 9);
@@ -505,6 +541,7 @@ int main(int argc, char **argv)
         else if (!strncmp(argv[i], "--ntaps=", 8)) ntaps = atoi(argv[i] + 8);
         else if (!strcmp(argv[i], "--fft-only")) only_fft = true;
         else if (!strcmp(argv[i], "--xcorrelate-only")) only_xcorrelate = true;
+        else if (!strcmp(argv[i], "--loops-only")) only_loops = true;
         else if (!strncmp(argv[i], "--num_inputs=", 13)) xc_inputs = atoi(argv[i] + 13);
         else if (!strncmp(argv[i], "--maxsearch=", 12)) xc_maxsearch = atoi(argv[i] + 12);
         else if (!strcmp(argv[i], "--input_complex")) xc_complex = true;
@@ -522,10 +559,15 @@ int main(int argc, char **argv)
         }
         else if (!strcmp(argv[i], "--help")) {
             printf("usage: %s [--device=N] [--iterations=N] [--fft-size=N] [--ntaps=N] [--fft-only] [block size]\n"
-                   "       %s --xcorrelate-only [--num_inputs=N] [--maxsearch=N] [--input_complex] [--iterations=N] [signal length]\n",
-                   argv[0], argv[0]);
+                   "       %s --xcorrelate-only [--num_inputs=N] [--maxsearch=N] [--input_complex] [--iterations=N] [signal length]\n"
+                   "       %s --loops-only [--iterations=N] [block size]\n",
+                   argv[0], argv[0], argv[0]);
             return 0;
         } else n = strtoull(argv[i], nullptr, 10);
+    }
+    if (only_loops) {
+        try { return loops_test(n); }
+        catch (const std::exception &e) { std::cerr << "error: " << e.what() << std::endl; return 2; }
     }
     if (only_xcorrelate) {
         try { return xcorrelate_test(n, xc_inputs, xc_maxsearch, xc_complex); }

@@ -42,5 +42,37 @@ public:
     virtual void wait() = 0;
 };
 
+// gr::clenabled::clSignalSource -- make() as the reference's include/clenabled/clSignalSource.h:49-50.  NCO / tone generator: no
+// inputs, one output of complex, float or int items; waveform 1 cos, 2 sin (complex items carry both).  The phase advances from
+// call to call and set_frequency() keeps it.  (The reference's per-block header of this name is not installed by this build yet.)
+class CLENABLED_API clSignalSource : virtual public gr::sync_block {
+public:
+    typedef std::shared_ptr<clSignalSource> sptr;
+    static sptr make(int idataType, int openCLPlatformType, int devSelector, int platformId, int devId, double samp_rate, int waveform,
+                     double freq, float amplitude, int setDebug = 0);
+    virtual void set_frequency(double frequency) = 0;  // lib/clSignalSource_impl.cc:251
+    virtual void set_phase(double angle_pos) = 0;
+    virtual double get_angle_pos() const = 0;   // phase of the next call's first item, radians
+    virtual double get_angle_rate() const = 0;  // 2 pi freq / samp_rate
+};
+
+// gr::clenabled::clCostasLoop -- make() as the reference's include/clenabled/clCostasLoop.h:52; order 2 (BPSK) or 4 (QPSK), anything
+// else throws std::invalid_argument (lib/clCostasLoop_impl.cc:80-83).  One complex input; output 0 the de-rotated stream, the
+// optional output 1 the loop frequency per item (float).  The reference inherits gr::blocks::control_loop; this class carries the
+// part of that interface a flowgraph uses itself.  (No per-block header of this name is installed by this build yet.)
+class CLENABLED_API clCostasLoop : virtual public gr::sync_block {
+public:
+    typedef std::shared_ptr<clCostasLoop> sptr;
+    static sptr make(int openCLPlatformType, int devSelector, int platformId, int devId, float loop_bw, int order, int setDebug = 0);
+    virtual void set_loop_bandwidth(float bw) = 0;
+    virtual float get_loop_bandwidth() const = 0;
+    virtual float get_alpha() const = 0;
+    virtual float get_beta() const = 0;
+    virtual float get_frequency() const = 0;  // these two wait for the block's last work() call
+    virtual float get_phase() const = 0;
+    virtual void set_frequency(float freq) = 0;
+    virtual void set_phase(float phase) = 0;
+};
+
 }  // namespace clenabled
 }  // namespace gr

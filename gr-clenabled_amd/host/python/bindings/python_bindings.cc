@@ -222,4 +222,27 @@ PYBIND11_MODULE(clenabled_python, m)
         })
 #endif
         ;
+
+    // NCO and carrier recovery (lib/clSignalSource_impl.cc, lib/clCostasLoop_impl.cc); work() of the source takes no inputs
+    py::class_<clSignalSource SYNC_BASES, std::shared_ptr<clSignalSource>>(m, "clSignalSource")
+        .def(py::init(&clSignalSource::make), py::arg("idataType"), py::arg("openCLPlatformType"), py::arg("devSelector"), py::arg("platformId"),
+             py::arg("devId"), py::arg("samp_rate"), py::arg("waveform"), py::arg("freq"), py::arg("amplitude"), py::arg("setDebug") = 0)
+        .def("set_frequency", &clSignalSource::set_frequency, py::arg("frequency"))
+        .def("set_phase", &clSignalSource::set_phase, py::arg("angle_pos"))
+        .def("get_angle_pos", &clSignalSource::get_angle_pos)
+        .def("get_angle_rate", &clSignalSource::get_angle_rate)
+        .def("work", &call_work<clSignalSource>, py::arg("noutput_items"), py::arg("input_items"), py::arg("output_items"));
+
+    py::class_<clCostasLoop SYNC_BASES, std::shared_ptr<clCostasLoop>>(m, "clCostasLoop")
+        .def(py::init(&clCostasLoop::make), py::arg("openCLPlatformType"), py::arg("devSelector"), py::arg("platformId"), py::arg("devId"),
+             py::arg("loop_bw"), py::arg("order"), py::arg("setDebug") = 0)
+        .def("set_loop_bandwidth", &clCostasLoop::set_loop_bandwidth, py::arg("bw"))
+        .def("get_loop_bandwidth", &clCostasLoop::get_loop_bandwidth)
+        .def("get_alpha", &clCostasLoop::get_alpha)
+        .def("get_beta", &clCostasLoop::get_beta)
+        .def("get_frequency", &clCostasLoop::get_frequency)
+        .def("get_phase", &clCostasLoop::get_phase)
+        .def("set_frequency", &clCostasLoop::set_frequency, py::arg("freq"))
+        .def("set_phase", &clCostasLoop::set_phase, py::arg("phase"))
+        .def("work", &call_work<clCostasLoop>, py::arg("noutput_items"), py::arg("input_items"), py::arg("output_items"));
 }

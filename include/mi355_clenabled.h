@@ -81,6 +81,8 @@ typedef struct mi355_xengine mi355_xengine;
 typedef struct mi355_elem    mi355_elem;
 typedef struct mi355_xcorr_fft mi355_xcorr_fft;
 typedef struct mi355_xcorr_td mi355_xcorr_td;
+typedef struct mi355_sigsource mi355_sigsource;
+typedef struct mi355_costas  mi355_costas;
 
 /* ---------------------------------------------------------------------------
  * Runtime: replaces GRCLBase::InitOpenCL / cleanup (lib/GRCLBase.cpp:17-369,
@@ -420,6 +422,69 @@ int mi355_xcorr_td_poll(mi355_xcorr_td *h, float *corr, int *lags);
 int mi355_xcorr_td_wait(mi355_xcorr_td *h);
 int mi355_xcorr_td_work_dev(mi355_xcorr_td *h, int nframes, const void *const *d_inputs, float *d_corr, int *d_lags,
                             float *d_curves, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * NCO / tone generator, replaces clSignalSource (lib/clSignalSource_impl.cc:113-237 kernels, 329-415 call), the fp64 branch:
+ *   make(idataType, openCLPlatformType, devSelector, platformId, devId, samp_rate, waveform, freq, amplitude, setDebug=0)
+ *                                                                               include/clenabled/clSignalSource.h:49-50
+ * dtype COMPLEX, FLOAT or INT; waveform 1 (cos) or 2 (sin); samp_rate != 0 (anything else: MI355_ERR_INVALID_ARG).
+ *     inc = 2 pi freq / samp_rate (double, 2 pi = 6.28318530717958647692);  A = (double)amplitude
+ *     item i of a call:  d = pos + inc * (double)i
+ *         complex  ((float)(cos d * A), (float)(sin d * A))         (whatever the waveform)
+ *         float    (float)(cos d * A) or (float)(sin d * A), by waveform
+ *         int      (int)(cos d * A) or (int)(sin d * A): evaluated in double and truncated toward zero (the reference's int
+ *                  kernel does its phase arithmetic in float)
+ *     after the call:  pos += inc * (double)(float)n;  if (pos > 2 pi || pos < -2 pi) pos = (pos/2pi - (double)(int)(pos/2pi)) * 2pi
+ * pos is host state handed to the kernel as an argument: _work_dev calls are stream-ordered and keep no device state.  Complex
+ * and float items are the float rounding of a double that is within a few double ulps of the formula (items off a thread's base
+ * item are one rotation of it); int items evaluate the formula itself.
+ *   _set_frequency keeps the phase; _set_phase sets pos; _get_state: pos and inc (either pointer may be NULL)
+ *   _work       host pointer, blocking;  _work_dev: device pointer aligned to the item size, enqueue only.  n == 0: no-op.
+ * Tuning aid, read once at _create: MI355_SIGSOURCE_LITERAL=1 evaluates every complex / float item literally (one sincos per item).
+ * ------------------------------------------------------------------------------------------------ */
+int mi355_sigsource_create(mi355_ctx *ctx, int dtype, double samp_rate, int waveform, double freq, float amplitude,
+                           mi355_sigsource **out);
+int mi355_sigsource_destroy(mi355_sigsource *h);
+int mi355_sigsource_set_frequency(mi355_sigsource *h, double freq);
+int mi355_sigsource_get_state(const mi355_sigsource *h, double *angle_pos, double *angle_rate);
+int mi355_sigsource_set_phase(mi355_sigsource *h, double angle_pos);
+int mi355_sigsource_work(mi355_sigsource *h, size_t n, void *out_host);
+int mi355_sigsource_work_dev(mi355_sigsource *h, size_t n, void *out_dev, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * BPSK / QPSK carrier recovery, replaces clCostasLoop (lib/clCostasLoop_impl.cc:112-232 kernel, 525-596 call), the fp64 + fma
+ * branch:  make(openCLPlatformType, devSelector, platformId, devId, loop_bw, order, setDebug=0)   clCostasLoop.h:52
+ * order 2 or 4 and loop_bw >= 0 (anything else: MI355_ERR_INVALID_ARG, the reference's invalid_argument at :80-83);
+ * num_streams 1 .. 4096 (anything else: MI355_ERR_UNSUPPORTED).  Gains as gr::blocks::control_loop, in float, widened to double
+ * (NOT cut to the six decimals of the reference's std::to_string, :136-137):
+ *     damp = sqrt(2)/2;  denom = 1 + 2 damp bw + bw^2;  alpha = 4 damp bw / denom;  beta = 4 bw^2 / denom
+ * Per stream the state (phase, freq, error) is three doubles in DEVICE memory, initially 0: consecutive calls chain with no host
+ * round trip.  Per item (re, im), all in double:
+ *     n_r = cos(-phase); n_i = sin(-phase)
+ *     o_r = fma(re, n_r, -(im n_i));  o_i = fma(re, n_i, im n_r);   out = ((float)o_r, (float)o_i)
+ *     e = order 2: o_r o_i;  order 4: (o_r > 0 ? 1 : -1) o_i - (o_i > 0 ? 1 : -1) o_r;      e = 0.5 (|e + 1| - |e - 1|)
+ *     freq = fma(beta, e, freq);  phase = phase + fma(alpha, e, freq)
+ *     if (phase > 2 pi || phase < -2 pi) phase = (phase/2pi - (double)(int)(phase/2pi)) * 2pi
+ *     freq = clamp(freq, -1, 1);   freq_out (when given) = (float)freq
+ * With several streams in / out / freq_out are item-major, stream s item i at [i * num_streams + s] (the channelizer's output
+ * layout); num_streams = 1 is the reference's block.  Any split of a stream into consecutive calls gives bit-identical output.
+ * Calls of one handle run in submission order, also when their streams differ (an event orders them).
+ *   _plan       validation and gains only (no device)
+ *   _get_state  num_streams doubles each (a NULL pointer is skipped); waits for the handle's last call
+ *   _set_state  num_streams doubles each, NULL: left as it is; waits for the handle's last call
+ *   _work       host pointers, blocking;  _work_dev: device pointers (in / out 8-byte, freq 4-byte aligned), enqueue only.
+ *               in and out must not overlap (in == out is MI355_ERR_INVALID_ARG).  nitems == 0: no-op.
+ * Tuning aid, read once at _create: MI355_COSTAS_ONE_LANE=1 runs a single stream through the several-streams kernel (one lane);
+ * a handle's kernel never changes, so the bit-identity under splitting holds either way.
+ * ------------------------------------------------------------------------------------------------ */
+int mi355_costas_plan(float loop_bw, int order, float *alpha, float *beta);
+int mi355_costas_create(mi355_ctx *ctx, float loop_bw, int order, int num_streams, mi355_costas **out);
+int mi355_costas_destroy(mi355_costas *h);
+int mi355_costas_set_loop_bandwidth(mi355_costas *h, float loop_bw);
+int mi355_costas_get_state(mi355_costas *h, double *phase, double *freq, double *error);
+int mi355_costas_set_state(mi355_costas *h, const double *phase, const double *freq);
+int mi355_costas_work(mi355_costas *h, size_t nitems, const void *in, void *out, float *freq_out);
+int mi355_costas_work_dev(mi355_costas *h, size_t nitems, const void *in_dev, void *out_dev, float *freq_dev, void *stream);
 
 #ifdef __cplusplus
 }
