@@ -55,6 +55,7 @@ def lib():
     vp, i, sz, f = C.c_void_p, C.c_int, C.c_size_t, C.c_float
     pp = C.POINTER(C.c_void_p)
     d, dp = C.c_double, C.POINTER(C.c_double)
+    ll, llp = C.c_longlong, C.POINTER(C.c_longlong)
     sigs = {
         "mi355_strerror": (C.c_char_p, [i]),
         "mi355_last_error": (C.c_char_p, []),
@@ -167,6 +168,18 @@ def lib():
         "mi355_costas_set_state": (i, [vp, vp, vp]),
         "mi355_costas_work": (i, [vp, sz, vp, vp, vp]),
         "mi355_costas_work_dev": (i, [vp, sz, vp, vp, vp, vp]),
+        "mi355_resampler_plan": (i, [i, i, i, i, ll, C.POINTER(i), llp, llp, C.POINTER(i)]),
+        "mi355_resampler_noutput_for": (ll, [i, i, i, i, ll]),
+        "mi355_resampler_create": (i, [vp, i, i, vp, i, i, pp]),
+        "mi355_resampler_destroy": (i, [vp]),
+        "mi355_resampler_set_taps": (i, [vp, vp, i]),
+        "mi355_resampler_ntaps": (i, [vp]),
+        "mi355_resampler_get_taps": (i, [vp, vp, i]),
+        "mi355_resampler_history": (i, [vp]),
+        "mi355_resampler_get_phase": (i, [vp, C.POINTER(i)]),
+        "mi355_resampler_set_phase": (i, [vp, i]),
+        "mi355_resampler_work": (i, [vp, ll, vp, vp, llp]),
+        "mi355_resampler_work_dev": (i, [vp, ll, vp, vp, llp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)  # AttributeError here = header/library mismatch: fail loudly

@@ -913,3 +913,104 @@ class clCostasLoop(_Block):
                                             _dp(output_items[0], n * 8, "output"), fo, _torch_stream(self.device)),
               "mi355_costas_work_dev")
         return noutput_items
+
+
+class clRationalResampler(_Block):
+    """Polyphase FIR with interpolation L and decimation M, the contract of GNU Radio's rational_resampler_ccf / ccc (beyond the
+    reference module): y = (taps * zero-stuff_L(x))[phase + m M].  L and M are used as given (not reduced by their gcd) and the
+    taps carry the gain L.  Complex taps are detected from the array's dtype.  history() = ceil(ntaps / L) taps per arm; the
+    input of a call is history-prefixed like clFilter's, a call returns (noutput, consumed) and the next call's input starts
+    `consumed` items later."""
+    _destroy = "mi355_resampler_destroy"
+
+    def __init__(self, openCLPlatformType, devSelector, platformId, devId, interpolation, decimation, taps, setDebug=0):
+        super().__init__(openCLPlatformType, devSelector, platformId, devId, setDebug)
+        self._interp, self._decim = int(interpolation), int(decimation)
+        t = self._taps_array(taps, None)
+        check(self._L.mi355_resampler_create(self._ctx, self._interp, self._decim, _hp(t), int(t.size), 1 if self._complex else 0,
+                                             C.byref(self._h)), "mi355_resampler_create")
+
+    def _taps_array(self, taps, complex_taps):
+        a = np.asarray(taps)
+        if complex_taps is None:
+            complex_taps = np.iscomplexobj(a)
+            self._complex = bool(complex_taps)
+        elif np.iscomplexobj(a) and not complex_taps:
+            raise TypeError("complex taps for a resampler created with real taps")
+        return np.ascontiguousarray(a, dtype=np.complex64 if complex_taps else np.float32).reshape(-1)
+
+    def taps(self):
+        n = self.ntaps()
+        out = np.empty(n, np.complex64 if self._complex else np.float32)
+        check(min(self._L.mi355_resampler_get_taps(self._h, _hp(out), n), 0), "mi355_resampler_get_taps")
+        return out
+
+    def ntaps(self):
+        return self._L.mi355_resampler_ntaps(self._h)
+
+    def set_taps(self, taps):
+        t = self._taps_array(taps, self._complex)
+        check(self._L.mi355_resampler_set_taps(self._h, _hp(t), int(t.size)), "mi355_resampler_set_taps")
+
+    def history(self):
+        return self._L.mi355_resampler_history(self._h)
+
+    def interpolation(self):
+        return self._interp
+
+    def decimation(self):
+        return self._decim
+
+    def phase(self):
+        c = C.c_int()
+        check(self._L.mi355_resampler_get_phase(self._h, C.byref(c)), "mi355_resampler_get_phase")
+        return c.value
+
+    def set_phase(self, phase):
+        check(self._L.mi355_resampler_set_phase(self._h, int(phase)), "mi355_resampler_set_phase")
+
+    def plan(self, noutput):
+        """(consumed, needed, phase_after) of a call of `noutput` items from the current phase; needed counts the history"""
+        nt, c = C.c_int(), C.c_int()
+        used, need = C.c_longlong(), C.c_longlong()
+        check(self._L.mi355_resampler_plan(self._interp, self._decim, self.ntaps(), self.phase(), int(noutput), C.byref(nt), C.byref(used),
+                                         C.byref(need), C.byref(c)), "mi355_resampler_plan")
+        return used.value, need.value, c.value
+
+    def noutput_for(self, navail):
+        """the most outputs a history-prefixed input of `navail` items allows from the current phase"""
+        n = self._L.mi355_resampler_noutput_for(self._interp, self._decim, self.ntaps(), self.phase(), int(navail))
+        if n < 0:
+            check(int(n), "mi355_resampler_noutput_for")
+        return int(n)
+
+    def work(self, noutput_items, input_items, output_items):
+        """input_items[0] is the history-prefixed buffer; returns (noutput_items, consumed)"""
+        x = _host(input_items[0], np.complex64)
+        need = self.plan(noutput_items)[1]
+        if x.size < need:
+            raise ValueError("resampler work(): need %d input items (history included), got %d" % (need, x.size))
+        y = _host(output_items[0], np.complex64, writable=True)
+        _need("output", y, noutput_items)
+        used = C.c_longlong()
+        check(self._L.mi355_resampler_work(self._h, int(noutput_items), _hp(x), _hp(y), C.byref(used)), "mi355_resampler_work")
+        return noutput_items, used.value
+
+    def work_device(self, noutput_items, input_items, output_items):
+        need = self.plan(noutput_items)[1]
+        t = input_items[0]
+        if t.is_cuda and t.numel() * t.element_size() < need * 8:
+            raise ValueError("resampler work_device(): need %d input items (history included), got %d"
+                             % (need, t.numel() * t.element_size() // 8))
+        used = C.c_longlong()
+        check(self._L.mi355_resampler_work_dev(self._h, int(noutput_items), _dp(t, need * 8, "input"),
+                                             _dp(output_items[0], int(noutput_items) * 8, "output"), C.byref(used),
+                                             _torch_stream(self.device)), "mi355_resampler_work_dev")
+        return noutput_items, used.value
+
+
+class clInterpFIRFilter(clRationalResampler):
+    """interp_fir_filter_ccf / ccc: clRationalResampler with decimation 1 -- `interpolation` outputs per input item."""
+
+    def __init__(self, openCLPlatformType, devSelector, platformId, devId, interpolation, taps, setDebug=0):
+        super().__init__(openCLPlatformType, devSelector, platformId, devId, interpolation, 1, taps, setDebug)

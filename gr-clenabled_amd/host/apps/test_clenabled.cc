@@ -528,11 +528,64 @@ static int loops_test(size_t n)
     return g_fail ? 1 : 0;
 }
 
+// --resampler-only: two impulses through (L, M) = (3, 2) must reproduce the arms, y[m] = hp[2 m] + 100 hp[2 m - 15] for taps
+// h[k] = k + 1 (the second impulse, at x[5], lands on the odd taps), with the stream offered to general_work() in two uneven
+// pieces chained by what the block consumed; then the time per general_work() call.
+static int resampler_test(size_t n)
+{
+#ifdef MI355_WITH_GNURADIO
+    (void)n;
+    printf("--resampler-only acts as the scheduler of the stand-alone build (what general_work() consumed)\n");
+    return 2;
+#else
+    const int L = 3, M = 2, K = 11;
+    std::vector<float> taps(K);
+    for (int k = 0; k < K; k++) taps[k] = (float)(k + 1);
+    auto rs = clRationalResampler::make(OCLTYPE_GPU, OCLDEVICESELECTOR_SPECIFIC, 0, g_dev, L, M, taps);
+    const int hist = (int)rs->history() - 1, nx = 64;
+    std::vector<gr_complex> x(hist + nx, gr_complex(0, 0)), y(nx * L / M + 8, gr_complex(-1, -1));
+    x[hist + 0] = gr_complex(1, 0);
+    x[hist + 5] = gr_complex(100, 0);
+    auto hp = [&](long q) { return q >= 0 && q < K ? taps[q] : 0.0f; };
+    long used = 0, made = 0;
+    bool ok = rs->history() == 4 && rs->interpolation() == L && rs->decimation() == M && rs->taps().size() == (size_t)K;
+    const auto t0 = std::chrono::steady_clock::now();
+    for (int offered : {hist + 7, hist + nx}) {  // items in the buffer from the read pointer, history included
+        gr_vector_int ni = {offered - (int)used};
+        gr_vector_const_void_star in = {x.data() + used};
+        gr_vector_void_star out = {y.data() + made};
+        rs->reset_consumed();
+        const int got = rs->general_work((int)(y.size() - made), ni, in, out);
+        used += rs->nitems_consumed(0);
+        made += got;
+    }
+    ok = ok && made == (long)nx * L / M && used == nx;
+    for (long m = 0; m < made; m++) ok = ok && close_to(y[m], gr_complex(hp(M * m) + 100.0f * hp(M * m - 5 * L), 0), 1e-4f);
+    const std::chrono::duration<double> dt = std::chrono::steady_clock::now() - t0;
+    report("clRationalResampler (3/2, impulse -> arms)", (size_t)made, dt.count() / 2, ok);
+    n = (n + L - 1) / L * L;  // a multiple of L outputs: every call starts at the same phase
+    std::vector<float> lp(97, 1.0f / 97);
+    auto rt = clRationalResampler::make(OCLTYPE_GPU, OCLDEVICESELECTOR_SPECIFIC, 0, g_dev, L, M, lp);
+    gr_vector_int need(1, 0);
+    rt->forecast((int)n, need);
+    std::vector<gr_complex> xi(need[0], gr_complex(1.0f, 0.5f)), yo(n);
+    gr_vector_const_void_star in = {xi.data()};
+    gr_vector_void_star out = {yo.data()};
+    int got = 0;
+    const double t = time_calls([&] { got = rt->general_work((int)n, need, in, out); });
+    // a constant input: every output is the input times the sum of its arm (33, 32, 32 taps of 1/97)
+    report("clRationalResampler (3/2, 97 taps)", n, t,
+           got == (int)n && close_to(yo[0], gr_complex(33.0f / 97, 16.5f / 97), 1e-5f) && close_to(yo[n - 1], gr_complex(1.0f, 0.5f) * (yo[n - 1].real()), 1e-5f) &&
+               std::fabs(yo[n - 1].real() * 97 - std::round(yo[n - 1].real() * 97)) < 1e-3f);
+    return g_fail ? 1 : 0;
+#endif
+}
+
 int main(int argc, char **argv)
 {
     size_t n = 8192;  // the reference's default block size
     int fft_size = 4096, ntaps = 65;
-    bool only_fft = false, only_xcorrelate = false, xc_complex = false, only_loops = false;
+    bool only_fft = false, only_xcorrelate = false, xc_complex = false, only_loops = false, only_resampler = false;
     int xc_inputs = 2, xc_maxsearch = 512;
     for (int i = 1; i < argc; i++) {
         if (!strncmp(argv[i], "--device=", 9)) g_dev = atoi(argv[i] + 9);
@@ -542,6 +595,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--fft-only")) only_fft = true;
         else if (!strcmp(argv[i], "--xcorrelate-only")) only_xcorrelate = true;
         else if (!strcmp(argv[i], "--loops-only")) only_loops = true;
+        else if (!strcmp(argv[i], "--resampler-only")) only_resampler = true;
         else if (!strncmp(argv[i], "--num_inputs=", 13)) xc_inputs = atoi(argv[i] + 13);
         else if (!strncmp(argv[i], "--maxsearch=", 12)) xc_maxsearch = atoi(argv[i] + 12);
         else if (!strcmp(argv[i], "--input_complex")) xc_complex = true;
@@ -560,13 +614,18 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--help")) {
             printf("usage: %s [--device=N] [--iterations=N] [--fft-size=N] [--ntaps=N] [--fft-only] [block size]\n"
                    "       %s --xcorrelate-only [--num_inputs=N] [--maxsearch=N] [--input_complex] [--iterations=N] [signal length]\n"
-                   "       %s --loops-only [--iterations=N] [block size]\n",
-                   argv[0], argv[0], argv[0]);
+                   "       %s --loops-only [--iterations=N] [block size]\n"
+                   "       %s --resampler-only [--iterations=N] [block size]\n",
+                   argv[0], argv[0], argv[0], argv[0]);
             return 0;
         } else n = strtoull(argv[i], nullptr, 10);
     }
     if (only_loops) {
         try { return loops_test(n); }
+        catch (const std::exception &e) { std::cerr << "error: " << e.what() << std::endl; return 2; }
+    }
+    if (only_resampler) {
+        try { return resampler_test(n); }
         catch (const std::exception &e) { std::cerr << "error: " << e.what() << std::endl; return 2; }
     }
     if (only_xcorrelate) {

@@ -74,5 +74,23 @@ public:
     virtual void set_phase(float phase) = 0;
 };
 
+// gr::clenabled::clRationalResampler -- polyphase FIR with interpolation L and decimation M, the contract of GNU Radio's
+// rational_resampler_ccf (make) / _ccc (make_ccc); decimation 1 is interp_fir_filter.  Beyond the reference module.  A general
+// block: history ceil(ntaps / L), relative rate L / M, output multiple 1; L and M are used as given (not reduced by their gcd)
+// and the taps carry the gain L.  taps() reports real taps with a zero imaginary part; set_taps() keeps the resampling phase.
+// (No per-block header of this name is installed by this build yet.)
+class CLENABLED_API clRationalResampler : virtual public gr::block {
+public:
+    typedef std::shared_ptr<clRationalResampler> sptr;
+    static sptr make(int openCLPlatformType, int devSelector, int platformId, int devId, int interpolation, int decimation,
+                     const std::vector<float> &taps, int setDebug = 0);
+    static sptr make_ccc(int openCLPlatformType, int devSelector, int platformId, int devId, int interpolation, int decimation,
+                         const std::vector<gr_complex> &taps, int setDebug = 0);
+    virtual std::vector<gr_complex> taps() const = 0;
+    virtual void set_taps(const std::vector<gr_complex> &taps) = 0;  // a block made with real taps refuses a non-zero imaginary part
+    virtual int interpolation() const = 0;
+    virtual int decimation() const = 0;
+};
+
 }  // namespace clenabled
 }  // namespace gr

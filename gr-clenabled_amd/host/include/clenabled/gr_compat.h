@@ -62,6 +62,7 @@ class basic_block_shim {
     io_signature::sptr d_in, d_out;
     unsigned d_history = 1;
     int d_output_multiple = 1;
+    uint64_t d_rate_interp = 1, d_rate_decim = 1;
     std::vector<long> d_consumed;  // per input, since the last reset_consumed()
     std::vector<std::string> d_out_ports;
     std::deque<shim_message> d_messages;
@@ -80,6 +81,9 @@ public:
     void set_history(unsigned h) { d_history = h; }
     int output_multiple() const { return d_output_multiple; }
     void set_output_multiple(int m) { d_output_multiple = m; }
+    void set_relative_rate(uint64_t interpolation, uint64_t decimation) { d_rate_interp = interpolation; d_rate_decim = decimation; }
+    uint64_t relative_rate_i() const { return d_rate_interp; }
+    uint64_t relative_rate_d() const { return d_rate_decim; }
     virtual bool start() { return true; }
     virtual bool stop() { return true; }
     // general_work() side of the contract

@@ -245,4 +245,42 @@ PYBIND11_MODULE(clenabled_python, m)
         .def("set_frequency", &clCostasLoop::set_frequency, py::arg("freq"))
         .def("set_phase", &clCostasLoop::set_phase, py::arg("phase"))
         .def("work", &call_work<clCostasLoop>, py::arg("noutput_items"), py::arg("input_items"), py::arg("output_items"));
+
+    // polyphase interpolating / rational-rate FIR (lib/clRationalResampler_impl.cc).  Complex taps construct the _ccc form.  general_work()
+    // is offered whatever the input array holds (history included) and returns (produced, consumed): the block decides how many
+    // outputs that input allows, as under the scheduler.
+    py::class_<clRationalResampler BLOCK_BASES, std::shared_ptr<clRationalResampler>>(m, "clRationalResampler")
+        .def(py::init(&clRationalResampler::make), py::arg("openCLPlatformType"), py::arg("devSelector"), py::arg("platformId"), py::arg("devId"),
+             py::arg("interpolation"), py::arg("decimation"), py::arg("taps"), py::arg("setDebug") = 0)
+        .def_static("make_ccc", &clRationalResampler::make_ccc, py::arg("openCLPlatformType"), py::arg("devSelector"), py::arg("platformId"),
+                    py::arg("devId"), py::arg("interpolation"), py::arg("decimation"), py::arg("taps"), py::arg("setDebug") = 0)
+        .def("taps", &clRationalResampler::taps)
+        .def("set_taps", &clRationalResampler::set_taps, py::arg("taps"))
+        .def("interpolation", &clRationalResampler::interpolation)
+        .def("decimation", &clRationalResampler::decimation)
+        .def("history", [](clRationalResampler &b) { return b.history(); })
+        .def("forecast",
+             [](clRationalResampler &b, int noutput_items) {
+                 gr_vector_int req(1, 0);
+                 b.forecast(noutput_items, req);
+                 return req[0];
+             },
+             py::arg("noutput_items"))
+#ifndef MI355_WITH_GNURADIO
+        // stand-alone build only: consume_each() outside a flowgraph has nothing to report to
+        .def("general_work",
+             [](clRationalResampler &b, int noutput_items, const std::vector<py::array> &in, std::vector<py::array> out) {
+                 need(noutput_items >= 0, "noutput_items is negative");
+                 need(in.size() == 1 && out.size() == 1, "one input and one output");
+                 auto i = in_ptrs(in);
+                 auto o = out_ptrs(out);
+                 gr_vector_int n(1, (int)((size_t)in[0].nbytes() / sizeof(gr_complex)));
+                 need((size_t)out[0].nbytes() >= (size_t)noutput_items * sizeof(gr_complex), "output 0 holds fewer than noutput_items items");
+                 const long before = b.nitems_consumed(0);
+                 const int produced = b.general_work(noutput_items, n, i, o);
+                 return py::make_tuple(produced, b.nitems_consumed(0) - before);
+             },
+             py::arg("noutput_items"), py::arg("input_items"), py::arg("output_items"))
+#endif
+        ;
 }

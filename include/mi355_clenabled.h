@@ -486,6 +486,52 @@ int mi355_costas_set_state(mi355_costas *h, const double *phase, const double *f
 int mi355_costas_work(mi355_costas *h, size_t nitems, const void *in, void *out, float *freq_out);
 int mi355_costas_work_dev(mi355_costas *h, size_t nitems, const void *in_dev, void *out_dev, float *freq_dev, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Polyphase FIR with interpolation L and decimation M: clRationalResampler (M = 1: clInterpFIRFilter).  Beyond the reference
+ * module, which has no resampler; the contract is GNU Radio's rational_resampler_ccf / ccc (interp_fir_filter_ccf / ccc at M = 1).
+ * Taps h[0..K) real or complex, designed for L: L and M are used as given, NOT reduced by their gcd, and there is no gain
+ * compensation (the taps carry the gain L).
+ *     nt = ceil(K / L)   taps per arm = history();  hp = h zero-padded to nt L;  arm p = hp[p + L j], j = 0 .. nt-1
+ * The input is complex64 and history-prefixed as clFilter's: in[nt-1] is x[0] of the call.  The handle's only state is the phase
+ * c in [0, L), 0 at create, kept on the host (a kernel argument).  Output m = 0 .. n-1 of a call:
+ *     q = c + m M;  p = q mod L;  b = q div L;     y[m] = sum_{j=0}^{nt-1} hp[p + L j] in[nt-1 + b - j]
+ * and afterwards
+ *     consumed = (c + n M) div L;  c' = (c + n M) mod L;  needed = n == 0 ? 0 : nt + (c + (n-1) M) div L   (items read)
+ * The next call's `in` is this call's in + consumed.  All position arithmetic is 64-bit.  An output reads exactly the nt samples
+ * in[b .. b+nt) and is one chain of float FMAs over them in an order fixed by its arm: any split of a stream into calls and any
+ * 8-byte alignment of the buffers give the same bits.
+ * Limits: 1 <= L, M <= 65536 and K >= 1 (smaller: MI355_ERR_INVALID_ARG, larger: MI355_ERR_UNSUPPORTED); nt L <= 1048576 table
+ * entries (beyond: MI355_ERR_UNSUPPORTED, the reason in mi355_last_error()).
+ *   _plan         the arithmetic above, no device (a block's forecast()); any output pointer may be NULL
+ *   _noutput_for  largest n with needed(n) <= navail_with_history:
+ *                 0 if navail < nt, else floor(((navail-nt+1) L - 1 - phase) / M) + 1;  a negative MI355_ERR_* on bad arguments
+ *   _set_taps     keeps the phase; history() may change
+ *   _set_phase    0 <= phase < L
+ *   _work         host pointers, blocking (stages through device buffers of the handle)
+ *   _work_dev     device pointers (8-byte aligned), enqueue only, allocates nothing
+ *                 both advance the phase and report `consumed` (may be NULL); in and out must not overlap
+ *                 (MI355_ERR_INVALID_ARG); noutput == 0 is a no-op.
+ * Which kernel serves a handle is fixed at _create / _set_taps and named in that call's INFO line (debug contexts).
+ * Tuning aids, read at _create / _set_taps: MI355_RESAMPLER_PLAIN=1 gives the handle the fallback kernel, MI355_RESAMPLER_GENERAL=1
+ * the general kernel where the interpolation kernel would serve (comparison variants; all three give the same bits).
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct mi355_resampler mi355_resampler;
+int mi355_resampler_plan(int interpolation, int decimation, int ntaps, int phase, long long noutput, int *taps_per_arm,
+                         long long *consumed, long long *needed, int *phase_after);
+long long mi355_resampler_noutput_for(int interpolation, int decimation, int ntaps, int phase, long long navail_with_history);
+int mi355_resampler_create(mi355_ctx *ctx, int interpolation, int decimation, const void *taps, int ntaps, int complex_taps,
+                           mi355_resampler **out);
+int mi355_resampler_destroy(mi355_resampler *h);
+int mi355_resampler_set_taps(mi355_resampler *h, const void *taps, int ntaps);
+int mi355_resampler_ntaps(const mi355_resampler *h);
+int mi355_resampler_get_taps(const mi355_resampler *h, void *taps_out, int cap);
+int mi355_resampler_history(const mi355_resampler *h);
+int mi355_resampler_get_phase(const mi355_resampler *h, int *phase);
+int mi355_resampler_set_phase(mi355_resampler *h, int phase);
+int mi355_resampler_work(mi355_resampler *h, long long noutput, const void *in_with_history, void *out, long long *consumed);
+int mi355_resampler_work_dev(mi355_resampler *h, long long noutput, const void *in_with_history, void *out, long long *consumed,
+                             void *stream);
+
 #ifdef __cplusplus
 }
 #endif
