@@ -180,6 +180,18 @@ def lib():
         "mi355_resampler_set_phase": (i, [vp, i]),
         "mi355_resampler_work": (i, [vp, ll, vp, vp, llp]),
         "mi355_resampler_work_dev": (i, [vp, ll, vp, vp, llp, vp]),
+        "mi355_synth_plan": (i, [i, i, i, ll, C.POINTER(i), llp, llp]),
+        "mi355_synth_create": (i, [vp, vp, i, i, vp, i, pp]),
+        "mi355_synth_destroy": (i, [vp]),
+        "mi355_synth_set_taps": (i, [vp, vp, i]),
+        "mi355_synth_ntaps": (i, [vp]),
+        "mi355_synth_get_taps": (i, [vp, vp, i]),
+        "mi355_synth_taps_per_arm": (i, [vp]),
+        "mi355_synth_num_channels": (i, [vp]),
+        "mi355_synth_nmap": (i, [vp]),
+        "mi355_synth_route": (C.c_char_p, [vp]),
+        "mi355_synth_work": (i, [vp, ll, vp, vp]),
+        "mi355_synth_work_dev": (i, [vp, ll, vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)  # AttributeError here = header/library mismatch: fail loudly

@@ -1014,3 +1014,81 @@ class clInterpFIRFilter(clRationalResampler):
 
     def __init__(self, openCLPlatformType, devSelector, platformId, devId, interpolation, taps, setDebug=0):
         super().__init__(openCLPlatformType, devSelector, platformId, devId, interpolation, 1, taps, setDebug)
+
+
+class clPolyphaseSynthesizer(_Block):
+    """Critically sampled inverse-DFT polyphase synthesis bank, the counterpart of clPolyphaseChannelizer (beyond the reference
+    module; the contract is in include/mi355_clenabled.h).  The input is the channelizer's item-major multiplex -- frames of nmap
+    items, slot q feeding channel ch_map[q] (None: all num_channels channels in order) -- history-prefixed with
+    history() = (taps_per_arm() - 1) * nmap items; a call for nframes frames writes nframes * num_channels items and the next
+    call's input starts nframes * nmap items later.  The taps carry the gain."""
+    _destroy = "mi355_synth_destroy"
+
+    def __init__(self, openCLPlatformType, devSelector, platformId, devId, taps, num_channels, ch_map=None, setDebug=0):
+        super().__init__(openCLPlatformType, devSelector, platformId, devId, setDebug)
+        t = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
+        self._M = int(num_channels)
+        if ch_map is None:
+            m, mp, self._nmap = None, C.c_void_p(), self._M
+        else:
+            m = np.ascontiguousarray(ch_map, dtype=np.int32).reshape(-1)
+            mp, self._nmap = _hp(m), int(m.size)
+        check(self._L.mi355_synth_create(self._ctx, _hp(t), int(t.size), self._M, mp, self._nmap, C.byref(self._h)), "mi355_synth_create")
+
+    def taps(self):
+        n = self.ntaps()
+        out = np.empty(n, np.float32)
+        check(min(self._L.mi355_synth_get_taps(self._h, _hp(out), n), 0), "mi355_synth_get_taps")
+        return out
+
+    def ntaps(self):
+        return self._L.mi355_synth_ntaps(self._h)
+
+    def set_taps(self, taps):
+        t = np.ascontiguousarray(taps, dtype=np.float32).reshape(-1)
+        check(self._L.mi355_synth_set_taps(self._h, _hp(t), int(t.size)), "mi355_synth_set_taps")
+
+    def taps_per_arm(self):
+        return self._L.mi355_synth_taps_per_arm(self._h)
+
+    def num_channels(self):
+        return self._M
+
+    def nmap(self):
+        return self._nmap
+
+    def history(self):
+        return (self.taps_per_arm() - 1) * self._nmap
+
+    def route(self):
+        return self._L.mi355_synth_route(self._h).decode()
+
+    def plan(self, nframes):
+        """(ninput_items, noutput_items) of a call of `nframes` frames; ninput_items counts the history"""
+        nt = C.c_int()
+        nin, nout = C.c_longlong(), C.c_longlong()
+        check(self._L.mi355_synth_plan(self.ntaps(), self._M, self._nmap, int(nframes), C.byref(nt), C.byref(nin), C.byref(nout)),
+              "mi355_synth_plan")
+        return nin.value, nout.value
+
+    def general_work(self, noutput_items, ninput_items, input_items, output_items):
+        """host buffers; noutput_items is rounded down to whole frames of num_channels items; returns (produced, consumed)"""
+        nframes = int(noutput_items) // self._M
+        if nframes == 0:
+            return 0, 0
+        nin, nout = self.plan(nframes)
+        x = _host(input_items[0], np.complex64)
+        if x.size < nin:
+            raise ValueError("synthesizer general_work(): need %d input items (history included), got %d" % (nin, x.size))
+        y = _host(output_items[0], np.complex64, writable=True)
+        _need("output", y, nout)
+        check(self._L.mi355_synth_work(self._h, nframes, _hp(x), _hp(y)), "mi355_synth_work")
+        return nout, nframes * self._nmap
+
+    def work_device(self, nframes, input_items, output_items):
+        if int(nframes) == 0:
+            return 0
+        nin, nout = self.plan(nframes)
+        check(self._L.mi355_synth_work_dev(self._h, int(nframes), _dp(input_items[0], nin * 8, "input"),
+                                           _dp(output_items[0], nout * 8, "output"), _torch_stream(self.device)), "mi355_synth_work_dev")
+        return nout

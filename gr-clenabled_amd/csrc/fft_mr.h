@@ -42,6 +42,17 @@ int mi355_fft_mr_launch(const MrPlan &plan, mi355_ctx *ctx, int sign, const void
 // K floats on the device, out = nsteps x M complex.  _ok: this plan / tap count / call size has the fused form (sign: the plan's direction, +1 only).
 bool mi355_fft_mr_pfb_ok(const MrPlan &plan, int sign, int K, int M, int nsteps);
 int mi355_fft_mr_pfb_launch(const MrPlan &plan, mi355_ctx *ctx, const void *in, void *out, const float *taps, int K, int M, int nsteps, hipStream_t st);
+// clPolyphaseSynthesizer's M-point transform + per-phase FIR across frames in ONE kernel (k_synth_mr, fft_mr.hip): in = the block's input (T - 1
+// history frames of nmap items first), taps_pad = T x M floats on the device (zero padded), ch_map = nmap ints on the device or nullptr for the
+// identity, out = nframes x M complex.  _ok: this plan (sign +1 only) and arm length have the fused form; it fills the geometry.
+struct MrSynthGeo {
+    int threads = 0, frames = 0;   // workgroup size; frames per tile
+    int nreg = 0, rs = 0;          // LDS ring: regions of one tile each, slots per region
+    int taps_lds = 0, lds_bytes = 0;
+};
+bool mi355_fft_mr_synth_ok(const MrPlan &plan, int sign, int M, int T, MrSynthGeo *g);
+int mi355_fft_mr_synth_launch(const MrPlan &plan, const MrSynthGeo &g, mi355_ctx *ctx, const void *in, void *out, const float *taps_pad,
+                              const int *ch_map, int nmap, int T, long long nframes, hipStream_t st);
 struct mi355_fft;
 const MrPlan *mi355_fft_mr_plan_of(const mi355_fft *h, int *sign);  // (fft.hip) the handle's one-pass mixed-radix plan, nullptr if it has none
 

@@ -21,6 +21,7 @@
 #include <utility>
 
 #include "fft_core.hpp"
+#include "synth_fir.hpp"
 
 using namespace fftc;
 
@@ -503,6 +504,98 @@ __global__ __launch_bounds__(512) void k_pfb_mr(const MrArgs a, const PfbMr f)
 
 
 // ------------------------------------------------------------------------------------------------------------------------------
+// clPolyphaseSynthesizer with such a channel count: the M-point backward transform of every input frame AND the per-phase FIR across frames
+// in one kernel (the contract: include/mi355_clenabled.h; the power-of-two twin: synth.hip).  A workgroup owns a run of `per` consecutive
+// tiles of F frames.  The LDS holds a ring of nreg regions of one tile each (rs slots, the layout of the passes: value i at slot(i)): a tile's
+// items are scattered through ch_map into its zeroed region (identity map: copied), transformed in place by the passes of k_fft_mr -- the last
+// one as an LDS -> LDS pass, which leaves value r of frame e at e M + r -- and filtered by synthf::fir_tile, which reaches T - 1 frames back into
+// the older regions.  A run starts nreg - 1 tiles early, transform only: every frame is transformed once per run, the (nreg - 1) F >= T - 1
+// frames in front of a run twice.  A frame's transform does not depend on its place in the tile, and an output is one fmaf chain: any split
+// of a stream into calls gives the same bits.
+struct SynMr {
+    const c32 *in;
+    f2v *out;
+    const float *taps;   // T x M, zero padded: tap p of phase r at p M + r
+    const int *ch_map;   // nullptr: the identity over all M channels
+    int nmap, T, nreg, rs, taps_lds, per;
+    long long nframes, nin_items, ntiles;
+    unsigned m_M;
+};
+
+template <int SIGN>
+__global__ __launch_bounds__(1024) void k_synth_mr(const MrArgs a, const SynMr f)
+{
+    extern __shared__ __attribute__((aligned(16))) c32 mr_lds[];
+    const int tid0 = threadIdx.x, TH = blockDim.x, F = a.frames, M = a.n, tot = F * M;
+    float *tl = (float *)(mr_lds + (size_t)f.nreg * f.rs);
+    if (f.taps_lds)
+        for (int i = tid0; i < f.T * M; i += TH) tl[i] = f.taps[i];
+    synthf::FirArgs fa;
+    fa.M = M; fa.T = f.T; fa.F = F; fa.nreg = f.nreg; fa.rs = f.rs; fa.m_M = f.m_M;
+#define MR_PASS(MODE, P)                                                                        \
+    switch (a.pass[P].radix) {                                                                  \
+    case 2: mr_pass<2, SIGN, MODE>(a, a.pass[P], lds, tid, group); break;                       \
+    case 3: mr_pass<3, SIGN, MODE>(a, a.pass[P], lds, tid, group); break;                       \
+    case 4: mr_pass<4, SIGN, MODE>(a, a.pass[P], lds, tid, group); break;                       \
+    case 5: mr_pass<5, SIGN, MODE>(a, a.pass[P], lds, tid, group); break;                       \
+    case 7: mr_pass<7, SIGN, MODE>(a, a.pass[P], lds, tid, group); break;                       \
+    case 6: mr_pass<6, SIGN, MODE>(a, a.pass[P], lds, tid, group); break;                       \
+    case 9: mr_pass<9, SIGN, MODE>(a, a.pass[P], lds, tid, group); break;                       \
+    case 10: mr_pass<10, SIGN, MODE>(a, a.pass[P], lds, tid, group); break;                     \
+    case 11: mr_pass<11, SIGN, MODE>(a, a.pass[P], lds, tid, group); break;                     \
+    case 13: mr_pass<13, SIGN, MODE>(a, a.pass[P], lds, tid, group); break;                     \
+    case 12: mr_pass<12, SIGN, MODE>(a, a.pass[P], lds, tid, group); break;                     \
+    case 14: mr_pass<14, SIGN, MODE>(a, a.pass[P], lds, tid, group); break;                     \
+    case 15: mr_pass<15, SIGN, MODE>(a, a.pass[P], lds, tid, group); break;                     \
+    case 8: mr_pass<8, SIGN, MODE>(a, a.pass[P], lds, tid, group); break;                       \
+    default: mr_pass<16, SIGN, MODE>(a, a.pass[P], lds, tid, group); break;                     \
+    }
+    const long long t0 = (long long)blockIdx.x * f.per, t1 = t0 + f.per < f.ntiles ? t0 + f.per : f.ntiles;
+    int reg = 0;
+    for (long long t = t0 - (f.nreg - 1); t < t1; t++) {
+        c32 *lds = mr_lds + (size_t)reg * f.rs;
+        __syncthreads();  // the last tile's filter has read the region this tile overwrites; the first time: the taps are written
+        if (f.ch_map) {
+            for (int i = tid0; i < tot; i += TH) lds[slot(i)] = mk(0.f, 0.f);
+            __syncthreads();
+        }
+        // the tile's newest input frames: output frame l needs input frames l .. l + T - 1 of the history-prefixed stream
+        const long long base = (t * F + (f.T - 1)) * f.nmap;
+        for (int i = tid0; i < F * f.nmap; i += TH) {
+            const long long gi = base + i;
+            const bool live = gi >= 0 && gi < f.nin_items;
+            c32 x = mk(0.f, 0.f);
+            if (live) {
+                const f2v v = __builtin_nontemporal_load((const f2v *)f.in + gi);
+                x = mk(v.x, v.y);
+            }
+            if (f.ch_map) {
+                const unsigned fr = (unsigned)i / (unsigned)f.nmap, q = (unsigned)i - fr * (unsigned)f.nmap;
+                if (live) lds[slot((int)fr * M + f.ch_map[q])] = x;
+            } else {
+                lds[slot(i)] = x;
+            }
+        }
+        __syncthreads();
+        int tid = tid0;
+        asm volatile("" : "+v"(tid));  // (as in k_fft_mr: keeps the passes' index arithmetic out of the loop-invariant registers)
+        const long long group = 0;
+        MR_PASS(3, 0)
+        for (int p = 1; p < a.npass; p++) { MR_PASS(1, p) }  // every pass ends with a barrier; the last leaves value r of frame e at e M + r
+        if (t >= t0) {
+            const long long left = f.nframes - t * F;
+            const int nvalid = left < F ? (int)left : F;
+            synthf::v2f *o = (synthf::v2f *)f.out + (size_t)t * F * M;
+            if (f.taps_lds) synthf::fir_tile<synthf::Pad32, 4>(mr_lds, fa, reg, tl, o, nvalid, tid0, TH);
+            else synthf::fir_tile<synthf::Pad32, 4>(mr_lds, fa, reg, f.taps, o, nvalid, tid0, TH);
+        }
+        reg = reg + 1 == f.nreg ? 0 : reg + 1;
+    }
+#undef MR_PASS
+}
+
+
+// ------------------------------------------------------------------------------------------------------------------------------
 // Longer lengths of the same kind (15361 ... 921600 points, N = N1 x N2 with both factors 6 ... 960): two passes over HBM, the scheme of
 // k_fft_tile in fft.hip with the mixed-radix passes inside.  A workgroup takes sixteen neighbouring columns of a matrix with n rows
 // (one 128-byte piece per row), transforms the sixteen columns in LDS and stores
@@ -954,6 +1047,90 @@ int mi355_fft_mr_pfb_launch(const MrPlan &plan, mi355_ctx *ctx, const void *in, 
 #define PFB_MR(PM) hipLaunchKernelGGL((k_pfb_mr<1, PM, FS>), dim3((unsigned)grid), dim3(th), lds_bytes, st, a, f)
     if (pmax == 8) PFB_MR(8); else if (pmax == 16) PFB_MR(16); else PFB_MR(32);
 #undef PFB_MR
+    MI355_HIP(hipGetLastError());
+    return MI355_OK;
+}
+
+// clPolyphaseSynthesizer, transform + per-phase FIR in one kernel (k_synth_mr).  Geometry: the smallest workgroup of at least 256 threads that
+// holds a frame, then the largest tile F (at most 64 frames and 8192 values, and what the threads hold) whose ring of 1 + ceil((T - 1) / F)
+// regions fits the 160 KiB of LDS; the T x M taps follow the ring when they fit as well, else they are read through the caches.
+// false: no tile fits (arms too long) or the plan is not a sign +1 plan of M points -- the caller runs its two kernels.
+bool mi355_fft_mr_synth_ok(const MrPlan &plan, int sign, int M, int T, MrSynthGeo *g)
+{
+    if (!plan.n || plan.n != M || sign <= 0 || plan.npass < 1 || T < 1) return false;
+    int th = 256;
+    if ((long long)th * plan.per_thread < M) th = (int)(((long long)M + plan.per_thread - 1) / plan.per_thread + 63) / 64 * 64;
+    if (th > 1024) return false;
+    long long fmax = (long long)th * plan.per_thread / M;
+    if (fmax > 64) fmax = 64;
+    if (fmax > 8192 / M) fmax = 8192 / M > 1 ? 8192 / M : 1;
+    for (int F = (int)fmax; F >= 1; F--) {
+        const long long nreg = 1 + ((long long)T - 1 + F - 1) / F, rs = lds_bytes_for(M, F) / 8, ring = nreg * rs * 8;
+        if (ring > 160 * 1024) continue;
+        g->threads = th;
+        g->frames = F;
+        g->nreg = (int)nreg;
+        g->rs = (int)rs;
+        g->taps_lds = ring + (long long)T * M * 4 <= 160 * 1024;
+        g->lds_bytes = (int)(ring + (g->taps_lds ? (long long)T * M * 4 : 0));
+        return true;
+    }
+    return false;
+}
+
+int mi355_fft_mr_synth_launch(const MrPlan &plan, const MrSynthGeo &g, mi355_ctx *ctx, const void *in, void *out, const float *taps_pad,
+                              const int *ch_map, int nmap, int T, long long nframes, hipStream_t st)
+{
+    if (nframes <= 0) return MI355_OK;
+    const int M = plan.n, F = g.frames;
+    const int cus = ctx->num_cus > 0 ? ctx->num_cus : 256;
+    int per_cu = (160 * 1024) / g.lds_bytes;
+    if (per_cu > 2048 / g.threads) per_cu = 2048 / g.threads;
+    if (per_cu < 1) per_cu = 1;
+    const long long ntiles = (nframes + F - 1) / F, cap = (long long)cus * per_cu;
+    // a run re-transforms nreg - 1 tiles: runs of at least four times that while there are tiles to share out
+    const long long minrun = g.nreg > 1 ? 4LL * (g.nreg - 1) : 1;
+    long long grid = (ntiles + minrun - 1) / minrun;
+    if (grid > cap) grid = cap;
+    const long long per = (ntiles + grid - 1) / grid;
+    grid = (ntiles + per - 1) / per;
+    MrArgs a;
+    a.in = nullptr;
+    a.out = nullptr;
+    a.window = nullptr;
+    a.tw = (const c32 *)plan.d_tw;
+    a.n = M;
+    a.nframes = 0;
+    a.frames = F;
+    a.npass = plan.npass;
+    a.in_rot = a.out_rot = a.real_in = 0;
+    a.ngroups = 0;
+    for (int p = 0; p < plan.npass; p++) a.pass[p] = plan.pass[p];
+    SynMr f;
+    f.in = (const c32 *)in;
+    f.out = (f2v *)out;
+    f.taps = taps_pad;
+    f.ch_map = ch_map;
+    f.nmap = nmap;
+    f.T = T;
+    f.nreg = g.nreg;
+    f.rs = g.rs;
+    f.taps_lds = g.taps_lds;
+    f.per = (int)per;
+    f.nframes = nframes;
+    f.nin_items = ((long long)T - 1 + nframes) * nmap;
+    f.ntiles = ntiles;
+    f.m_M = magic(M);
+    if (g.lds_bytes > 48 * 1024) {  // (said once per device)
+        static std::map<int, bool> lds_ok;
+        static std::mutex lds_ok_lock;
+        std::lock_guard<std::mutex> lk(lds_ok_lock);
+        if (!lds_ok[ctx->device]) {
+            MI355_HIP(hipFuncSetAttribute((const void *)k_synth_mr<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            lds_ok[ctx->device] = true;
+        }
+    }
+    hipLaunchKernelGGL((k_synth_mr<1>), dim3((unsigned)grid), dim3(g.threads), (size_t)g.lds_bytes, st, a, f);
     MI355_HIP(hipGetLastError());
     return MI355_OK;
 }

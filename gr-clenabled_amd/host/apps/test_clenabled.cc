@@ -581,21 +581,111 @@ static int resampler_test(size_t n)
 #endif
 }
 
+// --synth-only: 12 channels (mixed radix) and 64 channels (power of two), a partial map, through general_work() in two uneven
+// pieces chained by what the block consumed, against a host loop over the contract's two formulas in double; then the time per
+// general_work() call at 64 channels.
+#ifndef MI355_WITH_GNURADIO
+static bool synth_case(int M, int K, const std::vector<int> &map, int nframes)
+{
+    const int nmap = map.empty() ? M : (int)map.size(), T = (K + M - 1) / M;
+    std::vector<float> taps(K);
+    for (int k = 0; k < K; k++) taps[k] = (float)(std::sin(0.37 * k + 0.2) / M);
+    auto sy = clPolyphaseSynthesizer::make(OCLTYPE_GPU, OCLDEVICESELECTOR_SPECIFIC, 0, g_dev, taps, M, map);
+    bool ok = sy->taps_per_arm() == T && sy->nmap() == nmap && sy->num_channels() == M && (int)sy->history() == (T - 1) * nmap + 1 &&
+              sy->taps().size() == (size_t)K && !sy->route().empty();
+    const int nin_frames = T - 1 + nframes;
+    std::vector<gr_complex> x((size_t)nin_frames * nmap), y((size_t)nframes * M, gr_complex(-1, -1));
+    for (size_t i = 0; i < x.size(); i++) x[i] = gr_complex((float)std::cos(0.11 * i), (float)std::sin(0.23 * i + 1.0));
+    long used = 0, made = 0;
+    for (int frames_offered : {3, nframes}) {  // frames in the buffer behind the history, from the start of the stream
+        gr_vector_int ni = {(T - 1 + frames_offered) * nmap - (int)used};
+        gr_vector_const_void_star in = {x.data() + used};
+        gr_vector_void_star out = {y.data() + made};
+        sy->reset_consumed();
+        const int got = sy->general_work((int)(y.size() - made) + M / 2, ni, in, out);  // room that is no multiple of M: whole frames only
+        used += sy->nitems_consumed(0);
+        made += got;
+    }
+    ok = ok && made == (long)nframes * M && used == (long)nframes * nmap;
+    // host loop: V per input frame, then the FIR over frames
+    std::vector<std::complex<double>> V((size_t)nin_frames * M);
+    for (int f = 0; f < nin_frames; f++)
+        for (int r = 0; r < M; r++) {
+            std::complex<double> s(0, 0);
+            for (int q = 0; q < nmap; q++) {
+                const int c = map.empty() ? q : map[q];
+                const double a = 2.0 * M_PI * (double)((long)r * c % M) / M;
+                s += std::complex<double>(x[(size_t)f * nmap + q]) * std::complex<double>(std::cos(a), std::sin(a));
+            }
+            V[(size_t)f * M + r] = s;
+        }
+    double worst = 0, scale = 0;
+    for (int l = 0; l < nframes && l * (long)M < made; l++)
+        for (int r = 0; r < M; r++) {
+            std::complex<double> s(0, 0);
+            for (int p = 0; p < T; p++) {
+                const int k = r + M * p;
+                if (k < K) s += (double)taps[k] * V[(size_t)(l + T - 1 - p) * M + r];
+            }
+            worst = std::max(worst, std::abs(s - std::complex<double>(y[(size_t)l * M + r])));
+            scale = std::max(scale, std::abs(s));
+        }
+    return ok && scale > 0 && worst <= 1e-5 * scale;
+}
+#endif
+
+static int synth_test(size_t n)
+{
+#ifdef MI355_WITH_GNURADIO
+    (void)n;
+    printf("--synth-only acts as the scheduler of the stand-alone build (what general_work() consumed)\n");
+    return 2;
+#else
+    auto t0 = std::chrono::steady_clock::now();
+    bool ok = synth_case(12, 41, {7, 0, 3, 11, 4}, 150);
+    std::chrono::duration<double> dt = std::chrono::steady_clock::now() - t0;
+    report("clPolyphaseSynthesizer (12 channels, 5 fed, 4 per arm)", 150 * 12, dt.count(), ok);
+    t0 = std::chrono::steady_clock::now();
+    ok = synth_case(64, 8 * 64 - 33, {}, 200);
+    dt = std::chrono::steady_clock::now() - t0;
+    report("clPolyphaseSynthesizer (64 channels, 8 per arm)", 200 * 64, dt.count(), ok);
+    const int M = 64, T = 8;
+    n = (std::max<size_t>(n, M) + M - 1) / M * M;
+    std::vector<float> lp((size_t)T * M, 1.0f / M);
+    auto sy = clPolyphaseSynthesizer::make(OCLTYPE_GPU, OCLDEVICESELECTOR_SPECIFIC, 0, g_dev, lp, M);
+    gr_vector_int need(1, 0);
+    sy->forecast((int)n, need);
+    // channel 0 alone carries a constant: every output is that constant times the sum of its arm, T / M
+    std::vector<gr_complex> xi(need[0], gr_complex(0, 0)), yo(n);
+    for (size_t i = 0; i < xi.size(); i += M) xi[i] = gr_complex(1.0f, 0.5f);
+    gr_vector_const_void_star in = {xi.data()};
+    gr_vector_void_star out = {yo.data()};
+    int got = 0;
+    const double t = time_calls([&] { got = sy->general_work((int)n, need, in, out); });
+    report("clPolyphaseSynthesizer (64 channels, 8 per arm, timing)", n, t,
+           got == (int)n && need[0] == (int)((T - 1 + n / M) * M) && close_to(yo[0], gr_complex(T * 1.0f / M, T * 0.5f / M), 1e-5f) &&
+               close_to(yo[n - 1], gr_complex(T * 1.0f / M, T * 0.5f / M), 1e-5f));
+    return g_fail ? 1 : 0;
+#endif
+}
+
 int main(int argc, char **argv)
 {
     size_t n = 8192;  // the reference's default block size
     int fft_size = 4096, ntaps = 65;
-    bool only_fft = false, only_xcorrelate = false, xc_complex = false, only_loops = false, only_resampler = false;
+    bool only_fft = false, only_xcorrelate = false, xc_complex = false, only_loops = false, only_resampler = false, only_synth = false;
     int xc_inputs = 2, xc_maxsearch = 512;
     for (int i = 1; i < argc; i++) {
         if (!strncmp(argv[i], "--device=", 9)) g_dev = atoi(argv[i] + 9);
         else if (!strncmp(argv[i], "--iterations=", 13)) g_iter = atoi(argv[i] + 13);
+        else if (!strcmp(argv[i], "--iterations") && i + 1 < argc) g_iter = atoi(argv[++i]);
         else if (!strncmp(argv[i], "--fft-size=", 11)) fft_size = atoi(argv[i] + 11);
         else if (!strncmp(argv[i], "--ntaps=", 8)) ntaps = atoi(argv[i] + 8);
         else if (!strcmp(argv[i], "--fft-only")) only_fft = true;
         else if (!strcmp(argv[i], "--xcorrelate-only")) only_xcorrelate = true;
         else if (!strcmp(argv[i], "--loops-only")) only_loops = true;
         else if (!strcmp(argv[i], "--resampler-only")) only_resampler = true;
+        else if (!strcmp(argv[i], "--synth-only")) only_synth = true;
         else if (!strncmp(argv[i], "--num_inputs=", 13)) xc_inputs = atoi(argv[i] + 13);
         else if (!strncmp(argv[i], "--maxsearch=", 12)) xc_maxsearch = atoi(argv[i] + 12);
         else if (!strcmp(argv[i], "--input_complex")) xc_complex = true;
@@ -615,8 +705,9 @@ int main(int argc, char **argv)
             printf("usage: %s [--device=N] [--iterations=N] [--fft-size=N] [--ntaps=N] [--fft-only] [block size]\n"
                    "       %s --xcorrelate-only [--num_inputs=N] [--maxsearch=N] [--input_complex] [--iterations=N] [signal length]\n"
                    "       %s --loops-only [--iterations=N] [block size]\n"
-                   "       %s --resampler-only [--iterations=N] [block size]\n",
-                   argv[0], argv[0], argv[0], argv[0]);
+                   "       %s --resampler-only [--iterations=N] [block size]\n"
+                   "       %s --synth-only [--iterations N] [block size]\n",
+                   argv[0], argv[0], argv[0], argv[0], argv[0]);
             return 0;
         } else n = strtoull(argv[i], nullptr, 10);
     }
@@ -626,6 +717,10 @@ int main(int argc, char **argv)
     }
     if (only_resampler) {
         try { return resampler_test(n); }
+        catch (const std::exception &e) { std::cerr << "error: " << e.what() << std::endl; return 2; }
+    }
+    if (only_synth) {
+        try { return synth_test(n); }
         catch (const std::exception &e) { std::cerr << "error: " << e.what() << std::endl; return 2; }
     }
     if (only_xcorrelate) {

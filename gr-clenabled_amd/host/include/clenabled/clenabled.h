@@ -92,5 +92,24 @@ public:
     virtual int decimation() const = 0;
 };
 
+// gr::clenabled::clPolyphaseSynthesizer -- critically sampled inverse-DFT polyphase synthesis bank, the counterpart of
+// clPolyphaseChannelizer: the input stream is that block's item-major multiplex (frames of nmap = ch_map.size() items, slot q
+// feeding channel ch_map[q]; an empty ch_map: all num_channels channels in order), the output the wideband stream.  Beyond the
+// reference module; the contract is in mi355_clenabled.h.  A general block: history (taps_per_arm - 1) nmap + 1, relative rate
+// num_channels / nmap, output multiple num_channels; it consumes whole frames only and the taps carry the gain.
+// (No per-block header of this name is installed by this build yet.)
+class CLENABLED_API clPolyphaseSynthesizer : virtual public gr::block {
+public:
+    typedef std::shared_ptr<clPolyphaseSynthesizer> sptr;
+    static sptr make(int openCLPlatformType, int devSelector, int platformId, int devId, const std::vector<float> &taps, int num_channels,
+                     const std::vector<int> &ch_map = std::vector<int>(), int setDebug = 0);
+    virtual std::vector<float> taps() const = 0;
+    virtual void set_taps(const std::vector<float> &taps) = 0;  // may change taps_per_arm, and with it the history
+    virtual int taps_per_arm() const = 0;
+    virtual int num_channels() const = 0;
+    virtual int nmap() const = 0;
+    virtual std::string route() const = 0;
+};
+
 }  // namespace clenabled
 }  // namespace gr

@@ -283,4 +283,41 @@ PYBIND11_MODULE(clenabled_python, m)
              py::arg("noutput_items"), py::arg("input_items"), py::arg("output_items"))
 #endif
         ;
+
+    // polyphase synthesis bank (lib/clPolyphaseSynthesizer_impl.cc).  general_work() is offered whatever the input array holds (history
+    // included) and returns (produced, consumed): whole frames only, as under the scheduler.
+    py::class_<clPolyphaseSynthesizer BLOCK_BASES, std::shared_ptr<clPolyphaseSynthesizer>>(m, "clPolyphaseSynthesizer")
+        .def(py::init(&clPolyphaseSynthesizer::make), py::arg("openCLPlatformType"), py::arg("devSelector"), py::arg("platformId"), py::arg("devId"),
+             py::arg("taps"), py::arg("num_channels"), py::arg("ch_map") = std::vector<int>(), py::arg("setDebug") = 0)
+        .def("taps", &clPolyphaseSynthesizer::taps)
+        .def("set_taps", &clPolyphaseSynthesizer::set_taps, py::arg("taps"))
+        .def("taps_per_arm", &clPolyphaseSynthesizer::taps_per_arm)
+        .def("num_channels", &clPolyphaseSynthesizer::num_channels)
+        .def("nmap", &clPolyphaseSynthesizer::nmap)
+        .def("route", &clPolyphaseSynthesizer::route)
+        .def("history", [](clPolyphaseSynthesizer &b) { return b.history(); })
+        .def("forecast",
+             [](clPolyphaseSynthesizer &b, int noutput_items) {
+                 gr_vector_int req(1, 0);
+                 b.forecast(noutput_items, req);
+                 return req[0];
+             },
+             py::arg("noutput_items"))
+#ifndef MI355_WITH_GNURADIO
+        // stand-alone build only: consume_each() outside a flowgraph has nothing to report to
+        .def("general_work",
+             [](clPolyphaseSynthesizer &b, int noutput_items, const std::vector<py::array> &in, std::vector<py::array> out) {
+                 need(noutput_items >= 0, "noutput_items is negative");
+                 need(in.size() == 1 && out.size() == 1, "one input and one output");
+                 auto i = in_ptrs(in);
+                 auto o = out_ptrs(out);
+                 gr_vector_int n(1, (int)((size_t)in[0].nbytes() / sizeof(gr_complex)));
+                 need((size_t)out[0].nbytes() >= (size_t)noutput_items * sizeof(gr_complex), "output 0 holds fewer than noutput_items items");
+                 const long before = b.nitems_consumed(0);
+                 const int produced = b.general_work(noutput_items, n, i, o);
+                 return py::make_tuple(produced, b.nitems_consumed(0) - before);
+             },
+             py::arg("noutput_items"), py::arg("input_items"), py::arg("output_items"))
+#endif
+        ;
 }

@@ -532,6 +532,51 @@ int mi355_resampler_work(mi355_resampler *h, long long noutput, const void *in_w
 int mi355_resampler_work_dev(mi355_resampler *h, long long noutput, const void *in_with_history, void *out, long long *consumed,
                              void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Polyphase synthesis bank: clPolyphaseSynthesizer, the counterpart of clPolyphaseChannelizer (mi355_pfb_*) in its critically
+ * sampled form.  Beyond the reference module, which has no synthesizer; the role is that of GNU Radio's pfb_synthesizer_ccf at one
+ * sample per channel per frame (no sample-for-sample parity with it is claimed; this comment is the contract).
+ *     M = num_channels;  K = ntaps real taps g[0..K);  T = ceil(K / M) taps per arm;  g zero-padded to T M
+ *     ch_map[0..nmap): input slot q feeds channel ch_map[q]; 1 <= nmap <= M, entries in [0, M) and distinct (a duplicate is
+ *     MI355_ERR_INVALID_ARG); channels no slot feeds are zero.  ch_map == NULL: slot q feeds channel q.
+ * The input is one complex64 stream of item-major frames of nmap items, U_f[q] = in[f nmap + q] -- what mi355_pfb_work_dev writes --
+ * and history-prefixed: T - 1 old frames come first.  A call for nframes frames reads (T - 1 + nframes) nmap items and writes
+ * nframes M items; l = 0 .. nframes-1, r = 0 .. M-1:
+ *     V_f[r]     = sum_q U_f[q] exp(+2 pi i r ch_map[q] / M)               (backward DFT, scale 1, as in the channelizer)
+ *     y[l M + r] = sum_{p=0}^{T-1} g[r + M p] V_{(l + T - 1) - p}[r]       (one float FMA chain per component, p ascending from +0)
+ * The next call's `in` is this call's in + nframes nmap.  No device state and no gain compensation: the taps carry the gain.  The
+ * oversampled (2x) form is not offered.
+ * Limits: 1 <= M <= 4096, K >= 1, T M <= 1048576, nframes >= 0; in and out 8-byte aligned and not overlapping.  Below a range:
+ * MI355_ERR_INVALID_ARG; above: MI355_ERR_UNSUPPORTED with the reason in mi355_last_error().
+ * Routes, fixed at _create / _set_taps and named by _route() ("fused pow2 M=64 T=8 tile=64", "fused mixed-radix M=12 T=4 tile=64",
+ * "generic"): one fused kernel (transform, then the FIR over frames that stay in LDS) for M = 8 .. 4096 a power of two and for
+ * M = 2^a 3^b 5^c 7^d 11^e 13^f, as long as T - 1 frames fit the LDS ring; two kernels and a workspace of the handle otherwise.
+ * A transformed frame does not depend on its place in a tile or a call and an output is one chain over exactly its T frames: any
+ * split of a stream into calls and any 8-byte alignment give the same bits within a route; between routes the tolerance holds.
+ * MI355_SYNTH_GENERIC=1, read at _create, gives the handle the generic route; MI355_SYNTH_TAPS_GLOBAL=1, read at _create / _set_taps,
+ * makes the power-of-two kernel read its taps through the caches where they would fit the LDS (comparison variants, same bits).
+ *   _plan      the arithmetic above, no device; any output pointer may be NULL
+ *   _create    everything that can be told without a device is checked before ctx is touched
+ *   _set_taps  may change T, and with it the history (T - 1) nmap
+ *   _route     valid until the next _set_taps / _destroy of the handle
+ *   _work      host pointers, blocking (stages through device buffers of the handle)
+ *   _work_dev  device pointers, enqueue only (the generic route sizes its workspace on the first call); nframes == 0 is a no-op
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct mi355_synth mi355_synth;
+int mi355_synth_plan(int ntaps, int num_channels, int nmap, long long nframes, int *taps_per_arm, long long *ninput_items,
+                     long long *noutput_items);
+int mi355_synth_create(mi355_ctx *ctx, const float *taps, int ntaps, int num_channels, const int *ch_map, int nmap, mi355_synth **out);
+int mi355_synth_destroy(mi355_synth *h);
+int mi355_synth_set_taps(mi355_synth *h, const float *taps, int ntaps);
+int mi355_synth_ntaps(const mi355_synth *h);
+int mi355_synth_get_taps(const mi355_synth *h, float *taps_out, int cap);
+int mi355_synth_taps_per_arm(const mi355_synth *h);
+int mi355_synth_num_channels(const mi355_synth *h);
+int mi355_synth_nmap(const mi355_synth *h);
+const char *mi355_synth_route(const mi355_synth *h);
+int mi355_synth_work(mi355_synth *h, long long nframes, const void *in_with_history, void *out);
+int mi355_synth_work_dev(mi355_synth *h, long long nframes, const void *in_with_history, void *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
