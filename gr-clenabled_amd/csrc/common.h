@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <atomic>
 #include <chrono>
 #include <mutex>
 #include <new>
@@ -32,6 +33,20 @@ void mi355_set_error(const char *fmt, ...);
 // one diagnostics line to the registered sink (mi355_set_log_callback) or, by default, to stderr; DEBUG / INFO lines are
 // dropped unless the context was created with debug != 0 (the reference's setDebug)
 void mi355_log(const mi355_ctx *ctx, int level, const char *fmt, ...) __attribute__((format(printf, 3, 4)));
+
+// A switch that is read once per process at launch time says so the first time a non-default value is acted on under a debug context:
+// one INFO line, "switch NAME: what runs instead" (how tests/test_switches_once_gpu.py knows that the switch reached the code it names).
+#define MI355_SWITCH_NOTE(ctx, name, what)                                                                   \
+    do {                                                                                                     \
+        static std::atomic<bool> said__{false};                                                              \
+        if ((ctx) && (ctx)->debug && !said__.exchange(true)) mi355_log((ctx), MI355_LOG_INFO, "switch %s: %s", name, what); \
+    } while (0)
+
+// the same for a switch that is read per call: `cond` (which may call getenv) is only evaluated under a debug context
+#define MI355_SWITCH_NOTE_IF(ctx, cond, name, what)                                  \
+    do {                                                                             \
+        if ((ctx) && (ctx)->debug && (cond)) MI355_SWITCH_NOTE(ctx, name, what);     \
+    } while (0)
 
 #define MI355_HIP(call)                                                                  \
     do {                                                                                 \
@@ -99,9 +114,10 @@ static inline int mi355_balanced_grid(const mi355_ctx *ctx, long long units, int
 // kernel reads and writes the pinned staging buffers across PCIe itself -- one launch and one synchronisation per call
 // (8192-item clMathOp.work(): 58 us -> 23 us on MI355X).  MI355_NO_DIRECT=1 disables it.
 constexpr size_t kDirectBytes = 512u << 10;
-static inline bool mi355_direct_ok(size_t max_buffer_bytes)
+static inline bool mi355_direct_ok(size_t max_buffer_bytes, const mi355_ctx *ctx = nullptr)
 {
     static const bool off = getenv("MI355_NO_DIRECT") != nullptr;
+    if (off && max_buffer_bytes <= kDirectBytes) MI355_SWITCH_NOTE(ctx, "MI355_NO_DIRECT", "staged copies for a call the direct path would take");
     return !off && max_buffer_bytes <= kDirectBytes;
 }
 // Completion wait of such a call (one kernel of a few microseconds): poll the stream for a bounded time, then sleep on it.
@@ -114,13 +130,19 @@ hipError_t mi355_direct_sync(hipStream_t st);
 // (MI355_COPY_THREADS, default 7 helpers; 0 = the calling thread alone), streaming stores (MI355_COPY_STREAM=0: plain memcpy).  If the pool is busy with another block's copy the caller just
 // copies alone.
 void mi355_copy(void *dst, const void *src, size_t bytes);
+// says once (MI355_SWITCH_NOTE) which of MI355_COPY_THREADS=0 / MI355_COPY_STREAM=0 these copies run with
+void mi355_copy_notes(const mi355_ctx *ctx);
 // Staging chunk of a large host call of `total` bytes per buffer: 8 MiB pieces keep both DMA directions busy (40 GB/s each way of
 // the 48 this link carries with unbounded transfers); a call of only a few MiB is cut into >= 6 pieces of >= 1 MiB so that its
 // copy-in, transfers and copy-out overlap at all (one 8 MiB piece ran them strictly one after the other).  MI355_CHUNK_MB overrides.
-static inline size_t mi355_chunk_bytes(size_t total)
+static inline size_t mi355_chunk_bytes(size_t total, const mi355_ctx *ctx = nullptr)
 {
     static const size_t forced = getenv("MI355_CHUNK_MB") ? (size_t)atoi(getenv("MI355_CHUNK_MB")) << 20 : 0;
-    if (forced) return forced;
+    if (ctx && ctx->debug) mi355_copy_notes(ctx);
+    if (forced) {
+        MI355_SWITCH_NOTE(ctx, "MI355_CHUNK_MB", "forced staging chunk");
+        return forced;
+    }
     size_t c = total / 6;
     if (c > ((size_t)8 << 20)) c = (size_t)8 << 20;
     if (c < ((size_t)1 << 20)) c = (size_t)1 << 20;

@@ -217,7 +217,7 @@ extern "C" int mi355_elem_work(mi355_elem *h, size_t n, const void *in0, const v
     hipStream_t st = h->ctx->stream[0];
     const void *ins[2] = {in0, in1};
     void *outs[2] = {out0, out1};
-    if (mi355_direct_ok(items * 8)) {  // small call: the kernel works on the pinned staging itself (common.h)
+    if (mi355_direct_ok(items * 8, h->ctx)) {  // small call: the kernel works on the pinned staging itself (common.h)
         for (int i = 0; i < h->sh.nin; i++) mi355_copy(h->h_in[i], ins[i], items * h->sh.in_sz[i]);
         int rc = launch_elem(h, n, h->h_in[0], h->h_in[1], h->h_out[0], h->h_out[1], st);
         if (rc) return rc;

@@ -619,6 +619,7 @@ int launch_s(mi355_ctx *ctx, int sign, const void *in, void *out, const float *w
             return MI355_OK;
         }
     }
+    if constexpr (N == 32768) MI355_SWITCH_NOTE(ctx, "MI355_FFT_32768_IN_REGISTERS", "k_fft_s<32768> instead of k_fft_32k");
 #define LAUNCH_S(SG, RL) hipLaunchKernelGGL((k_fft_s<N, SG, RL>), dim3(grid), dim3(256), 0, st, in, (c32 *)out, window, (const c32 *)tw, nframes, shift)
     if (sign < 0) { if (real_in) LAUNCH_S(-1, true); else LAUNCH_S(-1, false); }
     else          { if (real_in) LAUNCH_S(1, true);  else LAUNCH_S(1, false); }
@@ -1144,6 +1145,7 @@ int launch_n(mi355_ctx *ctx, int sign, const void *in, void *out, const float *w
     if constexpr (N >= 16 && N <= 1024) {
         // MI355_FFT_WAVE_GEO=1: one-wave workgroups (no workgroup barriers); measured slower for N >= 256, off by default
         static const bool wave = getenv("MI355_FFT_WAVE_GEO") ? atoi(getenv("MI355_FFT_WAVE_GEO")) != 0 : false;
+        if (wave) MI355_SWITCH_NOTE(ctx, "MI355_FFT_WAVE_GEO", "k_fft in one-wave workgroups");
         if (wave) return launch_g<N, GeoW<N>>(ctx, sign, in, out, window, tw, nframes, shift, real_in, st, claims);
     }
     if constexpr (N == 32768) return launch_s<N>(ctx, sign, in, out, window, tw, nframes, shift, real_in, st);
@@ -1151,6 +1153,7 @@ int launch_n(mi355_ctx *ctx, int sign, const void *in, void *out, const float *w
         // MI355_FFT_WHOLE_FRAME=1 selects the whole-frame kernel (512/1024 threads, frame image in LDS) for comparison
         static const bool whole = getenv("MI355_FFT_WHOLE_FRAME") ? atoi(getenv("MI355_FFT_WHOLE_FRAME")) != 0 : false;
         if (!whole) return launch_s<N>(ctx, sign, in, out, window, tw, nframes, shift, real_in, st);
+        MI355_SWITCH_NOTE(ctx, "MI355_FFT_WHOLE_FRAME", "k_fft with the whole frame in LDS instead of k_fft_s");
     }
     if constexpr (N != 32768) return launch_g<N, Geo<N>>(ctx, sign, in, out, window, tw, nframes, shift, real_in, st, claims);
 }
@@ -1383,6 +1386,7 @@ int launch_bluestein(mi355_fft *h, const void *in, void *out, int nframes, hipSt
         case 16384: return launch_chirpz_m<16384>(h, in, out, nframes, st);
         }
     }
+    if (!fused && M >= 256 && M <= 16384) MI355_SWITCH_NOTE(h->ctx, "MI355_CHIRPZ_FUSED", "the five-launch chirp-z path instead of k_chirpz");
     // bound the work buffers to 2 x 128 MiB
     size_t chunk = (128u << 20) / ((size_t)M * 8);
     if (chunk < 1) chunk = 1;
@@ -1451,6 +1455,7 @@ int launch_tile(mi355_fft *h, const void *in, c32 *out, const c32 *twR, int ld, 
         // 1024 rows: half the threads, two transforms each, the next tile fetched under the transform (2^20 points 540 -> 517 us, 2^19 500 -> 485
         // on one box; the same form at 512 rows, where two workgroups share the CU anyway, measured 3 % slower and is not instantiated)
         static const bool half = getenv("MI355_FFT_TILE_HALF") ? atoi(getenv("MI355_FFT_TILE_HALF")) != 0 : true;
+        if (!half) MI355_SWITCH_NOTE(h->ctx, "MI355_FFT_TILE_HALF", "k_fft_tile with one thread per sixteen values instead of k_fft_tile_h");
         if (half) {
 #define TILEH(SG, RL)                                                                                                           \
     do {                                                                                                                        \
@@ -1496,6 +1501,7 @@ int launch_big(mi355_fft *h, const void *in, void *out, int nframes, hipStream_t
 {
     const int N = h->n, S = N / 4096;
     static const size_t ws_mb = getenv("MI355_FFT_WS_MB") ? (size_t)atoi(getenv("MI355_FFT_WS_MB")) : 256;
+    if (ws_mb != 256) MI355_SWITCH_NOTE(h->ctx, "MI355_FFT_WS_MB", "another workspace bound for the multi-pass sizes");
     size_t chunk = (ws_mb << 20) / ((size_t)N * 8);  // workspace bounded to 256 MiB
     if (chunk < 1) chunk = 1;
     if (chunk > (size_t)nframes) chunk = (size_t)nframes;
@@ -2019,7 +2025,7 @@ extern "C" int mi355_fft_work(mi355_fft *h, int nvec, const void *const *in_stre
     std::lock_guard<std::mutex> g(h->ctx->lock);
     MI355_HIP(hipSetDevice(h->ctx->device));
     const size_t isz = mi355_dtype_size(h->dtype), in_frame = isz * (size_t)h->n, out_frame = 8 * (size_t)h->n;
-    size_t chunk_frames = mi355_chunk_bytes((size_t)nvec * out_frame) / out_frame;
+    size_t chunk_frames = mi355_chunk_bytes((size_t)nvec * out_frame, h->ctx) / out_frame;
     if (chunk_frames < 1) chunk_frames = 1;
     size_t first = (size_t)nvec < chunk_frames ? (size_t)nvec : chunk_frames;
     size_t inb = first * in_frame;
@@ -2027,7 +2033,7 @@ extern "C" int mi355_fft_work(mi355_fft *h, int nvec, const void *const *in_stre
     int rc = h->pipe.ensure(1, &inb, first * out_frame, nslots);
     if (rc) return rc;
     HostPipe &p = h->pipe;
-    if ((size_t)nvec <= chunk_frames && mi355_direct_ok((size_t)nvec * out_frame)) {
+    if ((size_t)nvec <= chunk_frames && mi355_direct_ok((size_t)nvec * out_frame, h->ctx)) {
         // small call: the kernels work on the pinned staging themselves (see common.h); streams one after the other
         hipStream_t st = h->ctx->stream[0];
         for (int s_i = 0; s_i < h->nstreams; s_i++) {

@@ -924,9 +924,12 @@ int launch_with(const MrPlan &plan, int threads, int frames, mi355_ctx *ctx, int
     for (int p = 0; p < plan.npass; p++) a.pass[p] = plan.pass[p];
     static const bool no_copy_out = getenv("MI355_FFT_MR_NO_COPY_OUT") != nullptr;
     static const int copy_ns = getenv("MI355_FFT_MR_COPY_OUT_NS") ? atoi(getenv("MI355_FFT_MR_COPY_OUT_NS")) : 32;  // (runs under 256 bytes; 120 points 455 -> 290 us per 2^26 samples, 1000 points and up: the last pass own stores are as fast or faster)
+    if (no_copy_out) MI355_SWITCH_NOTE(ctx, "MI355_FFT_MR_NO_COPY_OUT", "k_fft_mr with the passes' own loads and stores");
+    if (copy_ns != 32) MI355_SWITCH_NOTE(ctx, "MI355_FFT_MR_COPY_OUT_NS", "another run length below which k_fft_mr stores through LDS");
     a.copy_out = plan.pass[plan.npass - 1].ns < copy_ns && !no_copy_out;
     a.m_n = magic(plan.n);
     static const int copy_nb = getenv("MI355_FFT_MR_COPY_IN_NB") ? atoi(getenv("MI355_FFT_MR_COPY_IN_NB")) : 16;
+    if (copy_nb != 16) MI355_SWITCH_NOTE(ctx, "MI355_FFT_MR_COPY_IN_NB", "another run length below which k_fft_mr loads through LDS");
     a.copy_in = plan.pass[0].nb < copy_nb && !no_copy_out;
     const int cus = ctx->num_cus > 0 ? ctx->num_cus : 256;
     const int lds_bytes = lds_bytes_for(plan.n, frames);
@@ -981,6 +984,7 @@ int mi355_fft_mr_pfb_launch(const MrPlan &plan, mi355_ctx *ctx, const void *in, 
     const int P = (K + M - 1) / M;
     static const int th_env = getenv("MI355_PFB_MR_THREADS") ? atoi(getenv("MI355_PFB_MR_THREADS")) : 0;
     auto ranges_of = [&](int th) { const long long byv = (long long)th * plan.per_thread / (FS * M); const int byt = th / M; return (int)(byv < byt ? byv : byt); };
+    if (th_env) MI355_SWITCH_NOTE(ctx, "MI355_PFB_MR_THREADS", "k_pfb_mr with a forced workgroup size");
     int th = 512;  // (256 threads, three workgroups per CU: 268 against 226 us at 100 channels, 262 / 251 at 20, 274 / 262 at 200)
     if (th_env >= 64 && th_env <= 512 && th_env % 64 == 0 && ranges_of(th_env) >= 1) th = th_env;
     const int Q = ranges_of(th);
@@ -992,6 +996,7 @@ int mi355_fft_mr_pfb_launch(const MrPlan &plan, mi355_ctx *ctx, const void *in, 
     const int pmax = P <= 8 ? 8 : P <= 16 ? 16 : 32;
     const int lds_bytes = (tw_lds + ntw) * 8 + pmax * M * 4;
     static const int wg_env = getenv("MI355_PFB_MR_WG_PER_CU") ? atoi(getenv("MI355_PFB_MR_WG_PER_CU")) : 0;
+    if (wg_env > 0) MI355_SWITCH_NOTE(ctx, "MI355_PFB_MR_WG_PER_CU", "k_pfb_mr with a forced number of workgroups per CU");
     // workgroups a CU holds: 117 / 133 / 165 registers per thread at 8 / 16 / 32 taps per arm = 4 / 3 / 3 waves per SIMD
     int per_cu = wg_env > 0 ? wg_env : (pmax == 8 ? 16 : 12) / (th / 64);
     if (per_cu > (160 * 1024) / lds_bytes) per_cu = (160 * 1024) / lds_bytes;

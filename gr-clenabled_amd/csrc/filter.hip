@@ -1191,19 +1191,23 @@ int launch_ols_g(mi355_filter *h, size_t nout, const void *in, void *out, hipStr
             MI355_HIP(hipGetLastError());
             return MI355_OK;
         }
+        if (h->nseg > 1 && !one_pass) MI355_SWITCH_NOTE(h->ctx, "MI355_OLS_PART_ONE_PASS", "k_ols, one accumulating pass per segment, instead of k_ols_part");
         if (h->nseg > 1 && one_pass) {
             const int s0 = (h->seg_len - 1 + 15) & ~15;
             const int L = (NF - s0) & ~15;
             const long long nblocks = (n_y + L - 1) / L, ngroups = (nblocks + F - 1) / F;
             if (nblocks > 0x7fffffffLL) { mi355_set_error("work() call too large"); return MI355_ERR_INVALID_ARG; }
             long long grid = mi355_balanced_grid(h->ctx, ngroups, 2, 2);
+            const int part_xcd_map = getenv("MI355_OLS_PART_XCD_MAP") ? atoi(getenv("MI355_OLS_PART_XCD_MAP")) : 1;
+            if (!part_xcd_map) MI355_SWITCH_NOTE(h->ctx, "MI355_OLS_PART_XCD_MAP", "k_ols_part with its groups in plain order");
             hipLaunchKernelGGL((k_ols_part<G>), dim3((unsigned)grid), dim3(TH), 0, st, (const c32 *)in, (c32 *)out, (const c32 *)h->d_H,
                                (const c32 *)h->d_twf, h->ntaps, h->nseg, h->seg_len, h->seg_first, h->decim, L, s0, n_y, (int)ngroups,
-                               getenv("MI355_OLS_PART_XCD_MAP") ? atoi(getenv("MI355_OLS_PART_XCD_MAP")) : 1);
+                               part_xcd_map);
             MI355_HIP(hipGetLastError());
             return MI355_OK;
         }
     }
+    if (!align_stores) MI355_SWITCH_NOTE(h->ctx, "MI355_OLS_ALIGN", "k_ols blocks that start storing at ntaps - 1");
     for (int sgm = 0; sgm < h->nseg; sgm++) {
         // segment sgm of a partitioned filter (nseg == 1: the whole filter): its taps, and where its input starts --
         // in_p[i] = in[i + (segments after this one) * seg_len], see upload_taps
@@ -1215,6 +1219,8 @@ int launch_ols_g(mi355_filter *h, size_t nout, const void *in, void *out, hipStr
         const int s0 = align_stores ? ((tn - 1 + 15) & ~15) : tn - 1;  // first stored output of a block (see the kernel)
         int L = NF - s0;
         if (L > 16 && !getenv("MI355_OLS_RAGGED_L")) L &= ~15;
+        else if (L > 16 && (L & 15)) MI355_SWITCH_NOTE(h->ctx, "MI355_OLS_RAGGED_L", "k_ols with a block length that is no multiple of 16");
+        if (xcd_map) MI355_SWITCH_NOTE(h->ctx, "MI355_OLS_XCD_MAP", "k_ols with XCD-contiguous groups");
         const long long nblocks = (n_y + L - 1) / L;
         const long long ngroups = (nblocks + F - 1) / F;
         if (nblocks > 0x7fffffffLL) { mi355_set_error("work() call too large"); return MI355_ERR_INVALID_ARG; }
@@ -1295,11 +1301,19 @@ int launch_filter(mi355_filter *h, size_t nout, const void *in, void *out, hipSt
     double r_po = h->decim / (h->ntaps * c_po);
     // test switches, read per call: MI355_FIR_DEC_KERNEL = per_output | lds | all forces one of the three where it applies
     const bool lds_off = getenv("MI355_FIR_DEC_LDS_OFF") != nullptr;
+    if (lds_off && h->ntaps <= kDlSpan / 2 && h->decim > dmax) MI355_SWITCH_NOTE(h->ctx, "MI355_FIR_DEC_LDS_OFF", "no LDS-staged decimator (k_fir_dec2 / k_fir_dec_lds)");
+    MI355_SWITCH_NOTE_IF(h->ctx, h->decim % 2 && h->decim > dmax && getenv("MI355_FIR_DEC2_EVEN_ONLY"), "MI355_FIR_DEC2_EVEN_ONLY", "k_fir_dec2 for even decimations only");
+    MI355_SWITCH_NOTE_IF(h->ctx, h->decim >= 3 && h->decim <= 5 && h->ntaps >= 16 && getenv("MI355_FIR_DEC2_FROM_6"), "MI355_FIR_DEC2_FROM_6",
+                         "decimations 3 ... 5 on the kernels that compute every output");
     if (const char *force = getenv("MI355_FIR_DEC_KERNEL")) {
         if (!strcmp(force, "per_output")) r_po = 1e30;
         else if (!strcmp(force, "lds")) r_po = r_all = 0.0;
         else if (!strcmp(force, "all")) r_po = r_lds = 0.0;
     }
+    if (!mf_on && h->mf_kk && h->ntaps >= 16) MI355_SWITCH_NOTE(h->ctx, "MI355_FIR_MFMA", "the vector-ALU kernels (k_fir_td and the decimating ones) instead of k_fir_mfma");
+    // (said at a decimation that the moved bound puts on the other side)
+    if (dl_min != 9 && h->decim >= (dl_min < 9 ? dl_min : 9) && h->decim < (dl_min < 9 ? 9 : dl_min))
+        MI355_SWITCH_NOTE(h->ctx, "MI355_FIR_DEC_LDS_MIN", "another smallest decimation for the LDS-staged kernels");
     const bool mf_ok = mf_on && h->mf_kk && h->ntaps >= 16, lds_ok = h->ntaps <= kDlSpan / 2 && !lds_off;
     // decimations 6 ... 8 belong to the kernels that compute every undecimated output (the matrix-core one from 96 taps, the register-tiled
     // one, ~ 14600 / K GS/s, below) unless one of the other two is predicted clearly ahead: at D = 8, 200 / 400 taps 107 / 60 -> 133 / 89 GS/s
@@ -1366,6 +1380,7 @@ int launch_filter(mi355_filter *h, size_t nout, const void *in, void *out, hipSt
         // samples staged per tile: 3072 (26 KiB: five or six workgroups per CU) up to 128 taps, 4096 above -- measured at 65 taps, D = 16: spans of
         // 2048 / 3072 / 4096 / 6144 / 8192 samples 489 / 603 / 550 / 464 / 377 GS/s of input; 400 taps 194 / 223 / 242 / 168 / 194 -- and whole rounds of
         // 256 outputs where a tile holds more than one (390 outputs per tile at D = 10 ran the second round of threads half empty)
+        if (span_env > 0) MI355_SWITCH_NOTE(h->ctx, "MI355_FIR_DEC2_SPAN", "k_fir_dec2 with a forced tile span");
         const int span_max = span_env > 0 ? span_env : (h->ntaps <= 128 ? 3072 : 4096);
         int tile_out = span_max > KP ? (span_max - KP) / h->decim + 1 : 1;
         if (tile_out > 2048) tile_out = 2048;
@@ -1491,7 +1506,7 @@ extern "C" int mi355_filter_work(mi355_filter *h, size_t noutput_items, const vo
     const size_t hist = (size_t)h->ntaps - 1;
     // sized from the larger side of a chunk, its INPUT (decim x the outputs): a slot's staging stays within the 1 ... 8 MiB pieces the
     // pipeline overlaps in, whatever the decimation
-    size_t chunk_out = mi355_chunk_bytes(noutput_items * (size_t)h->decim * 8) / (8 * (size_t)h->decim);
+    size_t chunk_out = mi355_chunk_bytes(noutput_items * (size_t)h->decim * 8, h->ctx) / (8 * (size_t)h->decim);
     if (chunk_out < 1) chunk_out = 1;
     size_t first = noutput_items < chunk_out ? noutput_items : chunk_out;
     size_t inb = (first * h->decim + hist) * 8;
@@ -1500,7 +1515,7 @@ extern "C" int mi355_filter_work(mi355_filter *h, size_t noutput_items, const vo
     HostPipe &p = h->pipe;
     const char *pin = (const char *)in;
     char *pout = (char *)out;
-    if (noutput_items <= chunk_out && mi355_direct_ok(inb)) {  // small call: the kernel works on the pinned staging itself
+    if (noutput_items <= chunk_out && mi355_direct_ok(inb, h->ctx)) {  // small call: the kernel works on the pinned staging itself
         hipStream_t st = h->ctx->stream[0];
         mi355_copy(p.h_in[0][0], pin, inb);
         rc = launch_filter(h, noutput_items, p.h_in[0][0], p.h_out[0], st);

@@ -300,7 +300,7 @@ extern "C" int mi355_mathop_work(mi355_mathop *h, size_t nitems, const void *a, 
     MI355_REQUIRE(a && b && c, "NULL buffer");
     std::lock_guard<std::mutex> g(h->ctx->lock);
     MI355_HIP(hipSetDevice(h->ctx->device));
-    const size_t chunk_items = mi355_chunk_bytes(nitems * h->isize) / h->isize;
+    const size_t chunk_items = mi355_chunk_bytes(nitems * h->isize, h->ctx) / h->isize;
     size_t first = nitems < chunk_items ? nitems : chunk_items;
     size_t inb[2] = {first * h->isize, first * h->isize};
     int rc = h->pipe.ensure(2, inb, first * h->isize);
@@ -308,7 +308,7 @@ extern "C" int mi355_mathop_work(mi355_mathop *h, size_t nitems, const void *a, 
     HostPipe &p = h->pipe;
     const char *pa = (const char *)a, *pb = (const char *)b;
     char *pc = (char *)c;
-    if (mi355_direct_ok(nitems * h->isize)) {
+    if (mi355_direct_ok(nitems * h->isize, h->ctx)) {
         // Small call (a scheduler-sized buffer): the kernel reads and writes the pinned staging buffers across PCIe
         // itself.  One launch + one synchronisation instead of three copy submissions + a launch + a synchronisation.
         const size_t bytes = nitems * h->isize;
@@ -418,7 +418,7 @@ extern "C" int mi355_mathconst_work(mi355_mathconst *h, size_t nitems, const voi
     MI355_HIP(hipSetDevice(h->ctx->device));
     float k;
     { std::lock_guard<std::mutex> gk(h->klock); k = h->k; }
-    const size_t chunk_items = mi355_chunk_bytes(nitems * h->isize) / h->isize;
+    const size_t chunk_items = mi355_chunk_bytes(nitems * h->isize, h->ctx) / h->isize;
     size_t first = nitems < chunk_items ? nitems : chunk_items;
     size_t inb = first * h->isize;
     int rc = h->pipe.ensure(1, &inb, inb);
@@ -426,7 +426,7 @@ extern "C" int mi355_mathconst_work(mi355_mathconst *h, size_t nitems, const voi
     HostPipe &p = h->pipe;
     const char *pa = (const char *)a;
     char *pc = (char *)c;
-    if (mi355_direct_ok(nitems * h->isize)) {  // small call: the kernel works on the pinned staging itself (see common.h)
+    if (mi355_direct_ok(nitems * h->isize, h->ctx)) {  // small call: the kernel works on the pinned staging itself (see common.h)
         const size_t bytes = nitems * h->isize;
         hipStream_t st = h->ctx->stream[0];
         mi355_copy(p.h_in[0][0], pa, bytes);

@@ -935,24 +935,33 @@ int launch_streams(mi355_pfb *h, const void *in, void *out, hipStream_t st, int 
     return MI355_OK;
 }
 
+// MI355_PFB_WAVE, once per process for create and launch alike: 0 = the staged kernel wherever there is one
+bool pfb_wave_on()
+{
+    static const bool wave = getenv("MI355_PFB_WAVE") ? atoi(getenv("MI355_PFB_WAVE")) != 0 : true;
+    return wave;
+}
+
 template <int M, int PMAX>
 int launch_fast(mi355_pfb *h, const void *in, void *out, hipStream_t st, int nsteps, long long buf_items)
 {
     // measured: 32 channels gain 6-11 % over the staged kernel; 8 and 16 channels (64-128 byte rows, gathered stores) lose 15 %
     if constexpr (M == 32 && PMAX <= 32) {
-        static const bool wave = getenv("MI355_PFB_WAVE") ? atoi(getenv("MI355_PFB_WAVE")) != 0 : true;
+        const bool wave = pfb_wave_on();
         const long long n_in = (long long)buf_items - h->R + h->K;
         if (wave && n_in * 8 < (4ll << 30) - (64 << 10)) return launch_streams<M, PMAX>(h, in, out, st, nsteps, buf_items);
+        if (!wave) MI355_SWITCH_NOTE(h->ctx, "MI355_PFB_WAVE", "k_pfb (staged) instead of k_pfbs");
     }
     if constexpr (M == 512 && PMAX > 32) return MI355_ERR_STATE;  // (create sends that shape down the two-kernel path)
     if constexpr ((M == 64 || M == 128 || M == 256 || M == 512) && PMAX <= 32) {
-        static const bool wave = getenv("MI355_PFB_WAVE") ? atoi(getenv("MI355_PFB_WAVE")) != 0 : true;
+        const bool wave = pfb_wave_on();
         const long long n_in = (long long)buf_items - h->R + h->K;
         // 32-bit byte offsets: the input as it is read (n_in * 8) and the OUTPUT including the rows the last group's unconditional, range-checked stores
         // overshoot by (up to 16 rows + the reversed row order inside a group: < 32 rows of M channels) -- an offset that wrapped past 2^32 would be
         // back in range and overwrite the first output rows
         if (wave && n_in * 8 < (4ll << 30) - (64 << 10) && ((long long)nsteps + 32) * M * 8 < (4ll << 30))
             return launch_wave<M, PMAX>(h, in, out, st, nsteps, buf_items);
+        if (!wave) MI355_SWITCH_NOTE(h->ctx, "MI355_PFB_WAVE", "k_pfb (staged) instead of k_pfbw / k_pfbq");
     }
     if constexpr (M == 512) return MI355_ERR_STATE;  // 512 channels exist on the ring kernel only (create and work_dev_n keep its calls inside the 32-bit offsets)
     else {
@@ -1071,6 +1080,7 @@ int launch_pfb(mi355_pfb *h, const void *in, void *out, hipStream_t st, int nste
         const long long g2 = tb < (long long)cus * 16 ? tb : (long long)cus * 16;
         const dim3 gd((unsigned)(g2 < 8 ? 8 : g2));
         static const int xr = getenv("MI355_PFB_NO_XCD_RUNS") ? 0 : 1;
+        if (!xr) MI355_SWITCH_NOTE(h->ctx, "MI355_PFB_NO_XCD_RUNS", "k_pfb_branches_t with its workgroups in plain order");
         if (over == 1)
             hipLaunchKernelGGL((k_pfb_branches_t<T, 16, 1>), gd, dim3(256), 0, st, (const c32 *)in, (c32 *)h->d_filt, h->d_taps, h->K, h->M, nsteps, tt, xr);
         else if (over == 2)
@@ -1138,7 +1148,8 @@ extern "C" int mi355_pfb_create(mi355_ctx *ctx, const float *taps, int ntaps, in
     h->fast = (M >= 2 && M <= 256 && (M & (M - 1)) == 0 && h->R == M && per_arm <= 64);
     // 512 channels, at most 32 taps per arm: the ring kernel with one 512-thread workgroup per CU (256 registers per thread); it has no staged
     // fallback, so a buffer must fit the ring kernel's 32-bit offsets (launch_fast)
-    if (M == 512 && h->R == M && per_arm <= 32 && !getenv("MI355_PFB_NO_RING_512") &&
+    const bool no_wave = !pfb_wave_on();  // (512 channels have no staged kernel to fall back to)
+    if (M == 512 && h->R == M && per_arm <= 32 && !getenv("MI355_PFB_NO_RING_512") && !no_wave &&
         ((long long)buf_items - h->R + ntaps) * 8 < (4ll << 30) - (64 << 10) && ((long long)h->nsteps + 32) * M * 8 < (4ll << 30))
         h->fast = true;
     h->pmax = per_arm <= 8 ? 8 : per_arm <= 16 ? 16 : per_arm <= 32 ? 32 : 64;
@@ -1272,7 +1283,7 @@ extern "C" int mi355_pfb_work(mi355_pfb *h, const void *in, void *out)
     HostPipe &p = h->pipe;
     hipStream_t st = h->ctx->stream[0];
     mi355_copy(p.h_in[0][0], in, inb);
-    if (mi355_direct_ok(inb > outb ? inb : outb)) {  // small call: the kernel works on the pinned staging itself (common.h)
+    if (mi355_direct_ok(inb > outb ? inb : outb, h->ctx)) {  // small call: the kernel works on the pinned staging itself (common.h)
         rc = launch_pfb(h, p.h_in[0][0], p.h_out[0], st, h->nsteps, h->buf_items);
         if (rc) return rc;
         MI355_HIP(mi355_direct_sync(st));

@@ -455,9 +455,14 @@ __attribute__((target("avx2"))) void copy_stream_avx2(char *d, const char *s, si
     _mm_sfence();
     if (n & 127) memcpy(d, s, n & 127);
 }
-void copy_piece(char *d, const char *s, size_t n)
+bool copy_streams()
 {
     static const bool stream = __builtin_cpu_supports("avx2") && !(getenv("MI355_COPY_STREAM") && atoi(getenv("MI355_COPY_STREAM")) == 0);
+    return stream;
+}
+void copy_piece(char *d, const char *s, size_t n)
+{
+    const bool stream = copy_streams();
     if (stream && n >= (1u << 20)) copy_stream_avx2(d, s, n);  // (scheduler-sized calls keep the cached memcpy: their data is re-read at once)
     else memcpy(d, s, n);
 }
@@ -479,6 +484,12 @@ void copy_part(void *a, int part, int parts)
     if (lo < hi) copy_piece(j->dst[1] + (lo - j->bytes[0]), j->src[1] + (lo - j->bytes[0]), hi - lo);
 }
 }  // namespace
+
+void mi355_copy_notes(const mi355_ctx *ctx)
+{
+    if (!job_pool()) MI355_SWITCH_NOTE(ctx, "MI355_COPY_THREADS", "staging copies on the calling thread alone");
+    if (!copy_streams() && __builtin_cpu_supports("avx2")) MI355_SWITCH_NOTE(ctx, "MI355_COPY_STREAM", "cached memcpy for the staging copies");
+}
 
 bool mi355_parallel(void (*fn)(void *, int, int), void *arg)
 {

@@ -252,7 +252,7 @@ int syn_choose(mi355_synth *h)
             if (rc) return rc;
         }
         h->route = kRoutePow2;
-        snprintf(name, sizeof name, "fused pow2 M=%d T=%d tile=%d", M, T, F);
+        snprintf(name, sizeof name, "fused pow2 M=%d T=%d tile=%d%s", M, T, F, !h->taps_lds && ring + tap_bytes <= kSynLds ? " taps=global" : "");
         h->route_name = name;
         return MI355_OK;
     }

@@ -554,7 +554,8 @@ int mi355_resampler_work_dev(mi355_resampler *h, long long noutput, const void *
  * A transformed frame does not depend on its place in a tile or a call and an output is one chain over exactly its T frames: any
  * split of a stream into calls and any 8-byte alignment give the same bits within a route; between routes the tolerance holds.
  * MI355_SYNTH_GENERIC=1, read at _create, gives the handle the generic route; MI355_SYNTH_TAPS_GLOBAL=1, read at _create / _set_taps,
- * makes the power-of-two kernel read its taps through the caches where they would fit the LDS (comparison variants, same bits).
+ * makes the power-of-two kernel read its taps through the caches where they would fit the LDS (comparison variants, same bits; _route()
+ * then ends in " taps=global").
  *   _plan      the arithmetic above, no device; any output pointer may be NULL
  *   _create    everything that can be told without a device is checked before ctx is touched
  *   _set_taps  may change T, and with it the history (T - 1) nmap

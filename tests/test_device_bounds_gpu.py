@@ -9,8 +9,9 @@ launcher does not look at the address the offset runs must equal the aligned run
 of the operation), at most 1 MiB, on each side (guarded.pad_items).  The refusals of the pointer contract are at the end, the host
 path's copy-back side (numpy outputs inside sentinel-filled arrays) before them.  DESIGN.md, 'Buffer contract', says the same in words.
 
-Routes are forced with the switches the code has and named in the test ids.  Not reachable from a test: the segment loop of k_ols
+Routes are forced with the switches the code has and named in the test ids.  Not reachable from this process: the segment loop of k_ols
 for a partitioned filter (MI355_OLS_PART_ONE_PASS is read once per process), the one-wave clFFT geometry (MI355_FFT_WAVE_GEO, same).
+Those run, without the guard bands, in child processes that start with the variable set: tests/test_switches_once_gpu.py.
 """
 import numpy as np
 import pytest

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from conftest import GPU_ARGS, crandn, golden, relerr
+from fft_ref import np_fft_block as _np_fft_block
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
@@ -251,7 +252,8 @@ def test_chirpz_real_input_device_path_and_chunks(gpu, oracle):
     blk.work_device(nvec, [dx], [dy])
     torch.cuda.synchronize()
     assert relerr(dy.cpu().numpy().view(np.complex64).reshape(-1), ref) <= TOL
-    # a call larger than one work-buffer chunk (128 MiB / (4096 * 8 B) = 4096 frames): first and last frames
+    # many frames through the host path: first and last frames.  (m = 4096 runs the fused chirp-z kernel, which has no work buffers; the
+    # piece loop of the five-launch path is run by chirpz_unfused_three_pieces and chirpz_16385_three_pieces in tests/switch_cases.py)
     nbig = 5000
     xb = crandn(rng, nbig * n)
     yb = np.empty_like(xb)
@@ -262,7 +264,9 @@ def test_chirpz_real_input_device_path_and_chunks(gpu, oracle):
 
 
 
-# 32768 / 65536: two kernels through a workspace (sub-transforms + radix-8/16 combine)
+# 32768: the 512-thread one-pass kernel; 65536: two tile passes through a workspace.  (The sub-transform + radix-8/16 combine scheme these
+# sizes ran on first is reached with MI355_FFT_32768_TWO_KERNELS / MI355_FFT_NO_TILE only: fft_32768_two_kernels and fft_no_tile in
+# tests/switch_cases.py)
 @pytest.mark.parametrize("n", [32768, 65536])
 @pytest.mark.parametrize("fwd,shift,win", [(True, False, False), (True, True, True), (False, True, True), (False, False, False)])
 def test_two_kernel_sizes(gpu, oracle, n, fwd, shift, win):
@@ -276,7 +280,8 @@ def test_two_kernel_sizes(gpu, oracle, n, fwd, shift, win):
     assert relerr(y, oracle.fft_block(n, fwd, w, shift, oracle.DTYPE_COMPLEX, x, f64=True)) <= TOL
 
 
-# 131072 .. 1048576: three passes (sub-transforms, radix-16 combine into 65536-point transforms, radix-2/4/8/16 combine)
+# 131072 .. 1048576: two tile passes.  (The three decimation-in-time passes -- sub-transforms, radix-16 combine into 65536-point
+# transforms, radix-2/4/8/16 combine -- run under MI355_FFT_NO_TILE: fft_no_tile and fft_ws_no_tile in tests/switch_cases.py)
 @pytest.mark.parametrize("n", [131072, 262144, 524288, 1048576])
 @pytest.mark.parametrize("fwd,shift,win", [(True, True, True), (False, True, True), (True, False, False)])
 def test_sizes_above_65536(gpu, oracle, n, fwd, shift, win):
@@ -331,22 +336,6 @@ def test_sizes_above_two_to_the_twenty(gpu, oracle, n, fwd, shift, win):
         z = np.empty_like(t)
         _fft(gpu, n, gpu.CLFFT_FORWARD).work(1, [t], [z])
         assert abs(z[1234567] - n) < 1e-5 * n * 8 and np.abs(np.delete(z, 1234567)).max() < 1e-5 * n * 8
-
-
-def _np_fft_block(n, fwd, w, shift, x):
-    """clFFT work() semantics (oracle/o_fft.c:140-188) on numpy's float64 pocketfft: the oracle's O(N^2) DFT for lengths that are not a
-    power of two cannot be run at 10^5 .. 10^7 points.  Tied to the oracle at a small length in the test below."""
-    x = x.astype(np.complex128).reshape(-1, n)
-    if w is not None:
-        x = x * np.asarray(w, np.float64)
-    if not fwd and shift:
-        half = n // 2
-        x = np.concatenate([x[:, half:], x[:, :half]], axis=1)  # original position i -> i + (n - half) for i < half
-    y = np.fft.fft(x, axis=1) if fwd else np.fft.ifft(x, axis=1) * n
-    if fwd and shift:
-        ln = (n + 1) // 2
-        y = np.concatenate([y[:, ln:], y[:, :ln]], axis=1)
-    return y.reshape(-1).astype(np.complex64)
 
 
 # lengths above 16384 that are not a power of two: chirp-z over the multi-pass power-of-two sizes (65536 .. 2^24 points)

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from conftest import GPU_ARGS, crandn, golden, relerr
+from fft_ref import np_xcorr as _np_xcorr
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
@@ -57,18 +58,6 @@ def test_many_inputs_and_device_path(gpu, oracle):
     ref = oracle.xcorr_fft(n, 2, ins, use_f64=True)
     for o, r in zip(d_out, ref):
         assert relerr(o.cpu().numpy(), r) <= TOL
-
-
-def _np_xcorr(n, itype, ins):
-    """The block's definition on numpy's float64 pocketfft (the oracle's O(N^2) DFT cannot run lengths that are not a power of two
-    at these sizes); tied to the oracle at a small length in the test below."""
-    x = [v.astype(np.complex128).reshape(-1, n) for v in ins]
-    spec = x if itype == 1 else [np.fft.fft(v, axis=1) for v in x]
-    outs = []
-    for sp in spec[1:]:
-        r = np.abs(np.fft.ifft(spec[0] * np.conj(sp), axis=1) * n)
-        outs.append(np.concatenate([r[:, n // 2:], r[:, :n // 2]], axis=1).reshape(-1).astype(np.float32))
-    return outs
 
 
 # sizes outside the fused kernel's (powers of two 16 ... 4096): the reference's steps over the clFFT transforms -- powers of two below 16
