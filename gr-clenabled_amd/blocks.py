@@ -439,7 +439,12 @@ class clXEngine(_Block):
 
     def pack3d_device(self, dst, src, width_bytes, rows, nblocks, src_pitch, src_block_stride, dst_pitch, dst_block_stride):
         """Strided device copy on this block's context (the send-side packing of the corner turn)."""
-        check(self._L.mi355_pack3d_dev(self._ctx, _dp(dst), _dp(src), int(width_bytes), int(rows), int(nblocks), int(src_pitch),
+        if min(int(width_bytes), int(rows), int(nblocks)) <= 0:
+            return  # (nothing to copy: the C call returns at once too)
+        # the last byte touched: the last row of the last block
+        src_bytes = (int(nblocks) - 1) * int(src_block_stride) + (int(rows) - 1) * int(src_pitch) + int(width_bytes)
+        dst_bytes = (int(nblocks) - 1) * int(dst_block_stride) + (int(rows) - 1) * int(dst_pitch) + int(width_bytes)
+        check(self._L.mi355_pack3d_dev(self._ctx, _dp(dst, dst_bytes, "destination"), _dp(src, src_bytes, "source"), int(width_bytes), int(rows), int(nblocks), int(src_pitch),
                                        int(src_block_stride), int(dst_pitch), int(dst_block_stride), _torch_stream(self.device)),
               "mi355_pack3d_dev")
 
@@ -675,8 +680,11 @@ class clxcorrelate_fft_vcf(_Block):
     work_test = work
 
     def work_device(self, noutput_items, input_items, output_items):
-        ip = (C.c_void_p * len(input_items))(*[_dp(x) for x in input_items])
-        op = (C.c_void_p * len(output_items))(*[_dp(y) for y in output_items])
+        if len(input_items) != self.num_inputs or len(output_items) != self.num_inputs - 1:
+            raise ValueError("work_device(): %d inputs and %d outputs expected" % (self.num_inputs, self.num_inputs - 1))
+        need = int(noutput_items) * self.fft_size
+        ip = (C.c_void_p * len(input_items))(*[_dp(x, need * 8, "input %d" % k).value for k, x in enumerate(input_items)])
+        op = (C.c_void_p * len(output_items))(*[_dp(y, need * 4, "output %d" % k).value for k, y in enumerate(output_items)])
         check(self._L.mi355_xcorr_fft_work_dev(self._h, noutput_items, ip, op, _torch_stream(self.device)), "mi355_xcorr_fft_work_dev")
         return noutput_items
 

@@ -9,8 +9,11 @@ allocation, so a test of values alone never sees it.  Here every buffer is a vie
   guarded_output(n_items, dtype, pad_items, offset_items)
                                                     interior pre-filled with NaN (an item the call never wrote shows), a finite
                                                     sentinel bit pattern on both sides (a store outside shows)
+  prefill_output(view, prior)                       the accumulate form of a call adds into its output: the interior then holds a prior
+                                                    result, not NaN (an item the call skipped shows in the values: it still holds the prior)
   check_guards(whole, view)                         pads bit for bit as they were made, interior of an output all written and
-                                                    finite; raises GuardError naming the first violated item
+                                                    finite; raises GuardError naming the first violated item.  interior=False: the pads
+                                                    only (an output the call writes in part, such as the rows of a pitched copy)
 
 The view's data pointer is `offset_items` items past a 16-byte boundary, so an offset of one complex64 item gives a buffer
 that is 8-byte but not 16-byte aligned.  Plain module (no fixtures); takes a torch device, so it runs on CPU tensors too
@@ -88,14 +91,24 @@ def guarded_output(n_items, dtype, pad_items, offset_items=0, device="cpu"):
     return whole, view
 
 
+def prefill_output(view, prior):
+    """Overwrite the NaN interior of a guarded_output with `prior` (numpy, same dtype and item count): what an accumulating call adds into.
+    The pads are untouched, so a store outside still shows; returns the view."""
+    prior = np.ascontiguousarray(prior).reshape(-1)
+    assert _TORCH_OF[prior.dtype] == view.dtype and prior.size == view.numel(), "the prior is not an output of this buffer"
+    view.copy_(torch.from_numpy(prior))
+    return view
+
+
 def _first_bad(mask):
     idx = torch.nonzero(mask)
     return None if idx.numel() == 0 else int(idx[0, 0])
 
 
-def check_guards(whole, view, name="buffer"):
-    """Raises GuardError unless both pads of `whole` still hold their bit pattern and, for an output, every interior item was written
-    and is finite.  The first violated item is named: stores before the buffer are reported nearest the payload first."""
+def check_guards(whole, view, name="buffer", interior=True):
+    """Raises GuardError unless both pads of `whole` still hold their bit pattern and, for an output (unless interior=False), every
+    interior item was written and is finite.  The first violated item is named: stores before the buffer are reported nearest the
+    payload first."""
     g = whole._guard
     start, nbytes, isz = g["start"], g["nbytes"], g["itemsize"]
     assert view.data_ptr() - whole.data_ptr() == start and view.numel() * view.element_size() == nbytes, "not the view of this allocation"
@@ -115,7 +128,7 @@ def check_guards(whole, view, name="buffer"):
     if after is not None:
         d = after // isz + 1
         raise GuardError(name, "after", n_items + d - 1, d, n_items, "byte %d of the allocation" % (start + nbytes + after))
-    if g["kind"] != "output":
+    if g["kind"] != "output" or not interior:
         return
     if g["dtype"] in _FLOAT:
         flat = view.view(torch.float32) if g["dtype"] == torch.float32 else torch.view_as_real(view).reshape(-1)

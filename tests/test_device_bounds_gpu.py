@@ -9,6 +9,10 @@ launcher does not look at the address the offset runs must equal the aligned run
 of the operation), at most 1 MiB, on each side (guarded.pad_items).  The refusals of the pointer contract are at the end, the host
 path's copy-back side (numpy outputs inside sentinel-filled arrays) before them.  DESIGN.md, 'Buffer contract', says the same in words.
 
+This file covers clFFT, the filters, the channelizer, the math and elementwise blocks and the FFT correlator.  The X-engine (every label
+of last_route(), several windows per call, the sharded engine, pack3d_device and the host calls) is in tests/test_xengine_bounds_gpu.py,
+which imports the helpers below; the resampler, the synthesizer, the loops and clXCorrelate carry their guard tests in their own files.
+
 Routes are forced with the switches the code has and named in the test ids.  Not reachable from this process: the segment loop of k_ols
 for a partitioned filter (MI355_OLS_PART_ONE_PASS is read once per process), the one-wave clFFT geometry (MI355_FFT_WAVE_GEO, same).
 Those run, without the guard bands, in child processes that start with the variable set: tests/test_switches_once_gpu.py.
@@ -603,3 +607,29 @@ def test_refusals_mathop_and_mathconst_want_sixteen_bytes(gpu):
         _refused(gpu, lambda: op.work_device(n, [a, b], [c]), [(cw, c)])
         if not ob:
             _refused(gpu, lambda: const.work_device(n, [a], [c]), [(cw, c)])
+
+
+def test_refusals_short_tensors_of_the_fft_correlator(gpu):
+    """work_device() of clxcorrelate_fft_vcf checks every tensor against nframes x fft_size items (complex64 in, float32 out): a short one
+    is a ValueError before anything is launched, not a device memory fault"""
+    n, nfr = 256, 5
+    ocl, sel, plat, dev = GPU_ARGS
+    blk = gpu.clxcorrelate_fft_vcf(n, 3, ocl, sel, plat, dev, 2)
+    ins = [guarded_input(np.ones(nfr * n, np.complex64), pad_items(8, n), 0, DEV)[1] for _ in range(3)]
+    outs = [guarded_output(nfr * n, np.float32, pad_items(4, n), 0, DEV) for _ in range(2)]
+    ov = [v for _, v in outs]
+    for bad_in, bad_out in ((2, None), (0, None), (None, 1), (None, 0)):
+        i = [x[:-1] if k == bad_in else x for k, x in enumerate(ins)]
+        o = [y[:-1] if k == bad_out else y for k, y in enumerate(ov)]
+        with pytest.raises(ValueError, match="holds %d bytes" % ((nfr * n - 1) * (8 if bad_out is None else 4))):
+            blk.work_device(nfr, i, o)
+    with pytest.raises(ValueError):
+        blk.work_device(nfr, ins[:2], ov)
+    torch.cuda.synchronize()
+    for whole, view in outs:
+        assert not torch.isfinite(view).any(), "a refused call wrote its output"
+        check_guards(whole, view, interior=False)
+    blk.work_device(nfr, ins, ov)  # exactly the items: accepted
+    torch.cuda.synchronize()
+    for whole, view in outs:
+        check_guards(whole, view)

@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 import torch
 
-from guarded import GuardError, NAN_BITS, SENTINEL, check_guards, guarded_input, guarded_output, pad_items, to_numpy
+from guarded import GuardError, NAN_BITS, SENTINEL, check_guards, guarded_input, guarded_output, pad_items, prefill_output, to_numpy
 
 DTYPES = [np.complex64, np.float32, np.int32]
 N = 1000
@@ -161,3 +161,83 @@ def test_nan_written_into_the_interior_is_reported():
     assert (e.value.where, e.value.index) == ("interior", 17)
     with pytest.raises(AssertionError):
         check_guards(yw, y[1:])  # not the view this allocation was made for
+
+
+# ------------------------------------------------------------- what tests/test_xengine_bounds_gpu.py adds: int8 payloads, pre-filled outputs
+
+def _sum_standin(x, n, stray):
+    """stand-in for a correlator's integer sum over an int8 payload: the int32 sum of n (+ stray) bytes from the start of the view"""
+    return int(_past(x, stray)[:n + stray].to(torch.int32).sum())
+
+
+@pytest.mark.parametrize("n,off", [(1000, 0), (1000, 4), (1000, 12), (1001, 0), (1003, 8), (1002, 1), (999, 3)])
+def test_int8_payload_a_read_one_byte_outside_changes_the_sum(n, off):
+    """every byte of the integer sentinel is non-zero (5B 5A 5A 5A), so ONE stray int8 sample on either side changes an exact integer sum,
+    whatever the phase of the pattern at the payload's edge; and check_guards compares pads that are not whole 32-bit words (odd payload
+    sizes, offsets that are no multiple of 4) byte by byte"""
+    assert all(b != 0 for b in SENTINEL.to_bytes(4, "little"))
+    a = np.random.default_rng(n + off).integers(-128, 128, n, dtype=np.int64).astype(np.int8)
+    xw, x = guarded_input(a, pad_items(1, 77), off)
+    assert x.dtype == torch.int8 and x.data_ptr() % 16 == off and np.array_equal(to_numpy(x), a)
+    check_guards(xw, x, "input")
+    want = int(a.astype(np.int64).sum())
+    assert _sum_standin(x, n, 0) == want
+    assert _sum_standin(x, n, 1) != want                                                   # one byte past the end
+    before = int(torch.as_strided(x, (n + 1,), (1,), x.storage_offset() - 1).to(torch.int32).sum())
+    assert before != want                                                                  # one byte before the start
+    # a store into either pad of the int8 input is seen too, at the byte next to the payload
+    for k, where, index in ((n, "after", n), (-1, "before", -1)):
+        xw, x = guarded_input(a, pad_items(1, 77), off)
+        torch.as_strided(x, (1,), (1,), x.storage_offset() + k)[0] = 0
+        with pytest.raises(GuardError) as e:
+            check_guards(xw, x, "input")
+        assert (e.value.where, e.value.index, e.value.distance) == (where, index, 1)
+
+
+@pytest.mark.parametrize("dtype", [np.complex64, np.int32], ids=lambda d: np.dtype(d).name)
+@pytest.mark.parametrize("off_out", [0, 1])
+def test_prefilled_output_still_reports_a_store_into_either_pad(dtype, off_out):
+    """the accumulate form: the interior holds a prior result instead of NaN; a correct accumulating stand-in passes, one that also stores one
+    item before or after the buffer is reported, and an item it skipped shows in the values (it still holds the prior)"""
+    a = _payload(dtype, N)
+    prior = (a[::-1] * 3).astype(dtype)
+    pad = pad_items(np.dtype(dtype).itemsize)
+
+    def accumulate(y, skip_last=False):
+        m = N - 1 if skip_last else N
+        y[:m] += torch.from_numpy(a)[:m]
+
+    yw, y = guarded_output(N, dtype, pad, off_out)
+    assert prefill_output(y, prior) is y
+    accumulate(y)
+    check_guards(yw, y, "output")
+    assert np.array_equal(to_numpy(y), prior + a)
+    for k, where, index in ((N, "after", N), (-1, "before", -1)):
+        yw, y = guarded_output(N, dtype, pad, off_out)
+        prefill_output(y, prior)
+        accumulate(y)
+        torch.as_strided(y, (1,), (1,), y.storage_offset() + k)[0] = 1
+        with pytest.raises(GuardError) as e:
+            check_guards(yw, y, "output")
+        assert (e.value.where, e.value.index, e.value.distance) == (where, index, 1)
+    yw, y = guarded_output(N, dtype, pad, off_out)
+    prefill_output(y, prior)
+    accumulate(y, skip_last=True)
+    check_guards(yw, y, "output")  # (finite everywhere: the guards cannot see it ...)
+    assert np.flatnonzero(to_numpy(y) != prior + a).tolist() == [N - 1]  # (... the comparison with the reference does)
+    with pytest.raises(AssertionError):
+        prefill_output(y, prior[:-1])
+
+
+def test_pads_only_check_of_a_partly_written_output():
+    """interior=False (the destination of a pitched copy: the gaps between its rows are never written): the pads are still compared"""
+    yw, y = guarded_output(N, np.int8, pad_items(1), 0)
+    y[:10] = 1
+    with pytest.raises(GuardError) as e:
+        check_guards(yw, y)
+    assert e.value.where == "interior"
+    check_guards(yw, y, interior=False)
+    _past(y, 1)[N] = 1
+    with pytest.raises(GuardError) as e:
+        check_guards(yw, y, interior=False)
+    assert (e.value.where, e.value.index) == ("after", N)
