@@ -192,6 +192,18 @@ def lib():
         "mi355_synth_route": (C.c_char_p, [vp]),
         "mi355_synth_work": (i, [vp, ll, vp, vp]),
         "mi355_synth_work_dev": (i, [vp, ll, vp, vp, vp]),
+        "mi355_pspec_plan": (i, [i, i, i, ll, llp, llp]),
+        "mi355_pspec_create": (i, [vp, i, vp, i, i, i, i, i, f, pp]),
+        "mi355_pspec_destroy": (i, [vp]),
+        "mi355_pspec_set_scale": (i, [vp, f]),
+        "mi355_pspec_set_window": (i, [vp, vp, i]),
+        "mi355_pspec_set_generic": (i, [vp, i]),
+        "mi355_pspec_fft_size": (i, [vp]),
+        "mi355_pspec_navg": (i, [vp]),
+        "mi355_pspec_hop": (i, [vp]),
+        "mi355_pspec_route": (C.c_char_p, [vp]),
+        "mi355_pspec_work": (i, [vp, ll, vp, vp]),
+        "mi355_pspec_work_dev": (i, [vp, ll, vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)  # AttributeError here = header/library mismatch: fail loudly

@@ -1100,3 +1100,92 @@ class clPolyphaseSynthesizer(_Block):
         check(self._L.mi355_synth_work_dev(self._h, int(nframes), _dp(input_items[0], nin * 8, "input"),
                                            _dp(output_items[0], nout * 8, "output"), _torch_stream(self.device)), "mi355_synth_work_dev")
         return nout
+
+
+class clPowerSpectrum(_Block):
+    """Averaged power spectrum: window, forward DFT, |X|^2, mean over navg frames, optionally 10 log10 (beyond the reference module;
+    the contract is in include/mi355_clenabled.h).  Frames start `hop` items apart (None: fft_size; smaller: Welch overlap; larger:
+    the items in between are skipped and never read).  A call for S spectra reads (S * navg - 1) * hop + fft_size complex items,
+    history() = max(fft_size - hop, 0) of them shared with the call before, and writes S * fft_size floats; the next call's input
+    starts S * navg * hop items later (with hop > fft_size that is past the last item read: general_work(), which reports what it
+    consumed, asks for all S * navg * hop items)."""
+    _destroy = "mi355_pspec_destroy"
+
+    def __init__(self, openCLPlatformType, devSelector, platformId, devId, fft_size, navg, window=None, hop=None, shift=False,
+                 log_output=False, scale=1.0, setDebug=0):
+        super().__init__(openCLPlatformType, devSelector, platformId, devId, setDebug)
+        self._N, self._K = int(fft_size), int(navg)
+        self._H = self._N if hop is None else int(hop)
+        w, wp, wn = self._window_arg(window)
+        check(self._L.mi355_pspec_create(self._ctx, self._N, wp, wn, self._K, self._H, 1 if shift else 0, 1 if log_output else 0,
+                                         float(scale), C.byref(self._h)), "mi355_pspec_create")
+
+    @staticmethod
+    def _window_arg(window):
+        if window is None or len(window) == 0:
+            return None, C.c_void_p(), 0
+        w = np.ascontiguousarray(window, dtype=np.float32).reshape(-1)
+        return w, _hp(w), int(w.size)
+
+    def fft_size(self):
+        return self._N
+
+    def navg(self):
+        return self._K
+
+    def hop(self):
+        return self._H
+
+    def history(self):
+        return max(self._N - self._H, 0)
+
+    def route(self):
+        return self._L.mi355_pspec_route(self._h).decode()
+
+    def set_scale(self, scale):
+        check(self._L.mi355_pspec_set_scale(self._h, float(scale)), "mi355_pspec_set_scale")
+
+    def set_window(self, window):
+        w, wp, wn = self._window_arg(window)
+        check(self._L.mi355_pspec_set_window(self._h, wp, wn), "mi355_pspec_set_window")
+
+    def set_generic(self, on):
+        check(self._L.mi355_pspec_set_generic(self._h, 1 if on else 0), "mi355_pspec_set_generic")
+
+    def plan(self, nspectra):
+        """(ninput_items, noutput_items) of a call of `nspectra` spectra"""
+        nin, nout = C.c_longlong(), C.c_longlong()
+        check(self._L.mi355_pspec_plan(self._N, self._K, self._H, int(nspectra), C.byref(nin), C.byref(nout)), "mi355_pspec_plan")
+        return nin.value, nout.value
+
+    def work(self, x):
+        """host buffer; as many whole spectra as x holds; returns them as a float32 array of shape (nspectra, fft_size)"""
+        x = _host(x, np.complex64)
+        ns = 0 if x.size < self._N else ((x.size - self._N) // self._H + 1) // self._K
+        y = np.empty((ns, self._N), np.float32)
+        check(self._L.mi355_pspec_work(self._h, ns, _hp(x), _hp(y)), "mi355_pspec_work")
+        return y
+
+    def general_work(self, noutput_items, ninput_items, input_items, output_items):
+        """host buffers; noutput_items counts spectra (vectors of fft_size floats); returns (produced, consumed).  The input must hold
+        what is consumed, navg * hop per spectrum: with hop > fft_size that is more than the (S * navg - 1) * hop + fft_size items read"""
+        ns = int(noutput_items)
+        if ns == 0:
+            return 0, 0
+        nin, nout = self.plan(ns)
+        nin = max(nin, ns * self._K * self._H)
+        x = _host(input_items[0], np.complex64)
+        if x.size < nin:
+            raise ValueError("clPowerSpectrum general_work(): need %d input items, got %d" % (nin, x.size))
+        y = _host(output_items[0], np.float32, writable=True)
+        _need("output", y, nout)
+        check(self._L.mi355_pspec_work(self._h, ns, _hp(x), _hp(y)), "mi355_pspec_work")
+        return ns, ns * self._K * self._H
+
+    def work_device(self, nspectra, input_items, output_items):
+        if int(nspectra) == 0:
+            return 0
+        nin, nout = self.plan(nspectra)
+        check(self._L.mi355_pspec_work_dev(self._h, int(nspectra), _dp(input_items[0], nin * 8, "input"),
+                                           _dp(output_items[0], nout * 4, "output"), _torch_stream(self.device)), "mi355_pspec_work_dev")
+        return nout

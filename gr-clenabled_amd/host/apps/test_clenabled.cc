@@ -669,11 +669,101 @@ static int synth_test(size_t n)
 #endif
 }
 
+// --pspec-only: 64 points (fused) with overlapping Hann frames and 100 points (generic) with skipped items, through general_work() in
+// two uneven pieces chained by what the block consumed, against a direct DFT in double; then the time per general_work() call at
+// 1024 points, 16 frames per spectrum.
+#ifndef MI355_WITH_GNURADIO
+static bool pspec_case(int N, int K, int H, bool hann, bool shift, int nspectra)
+{
+    std::vector<float> w;
+    if (hann)
+        for (int i = 0; i < N; i++) w.push_back((float)(0.5 - 0.5 * std::cos(2.0 * M_PI * i / N)));
+    auto ps = clPowerSpectrum::make(OCLTYPE_GPU, OCLDEVICESELECTOR_SPECIFIC, 0, g_dev, N, K, w, H, shift, false, 0.5f);
+    bool ok = ps->fft_size() == N && ps->navg() == K && ps->hop() == H && (int)ps->history() == std::max(N - H, 0) + 1 && !ps->route().empty();
+    // what the library reads, or with hop > fft_size what the block consumes: it waits for the skipped items of a spectrum
+    const long nin = std::max(((long)nspectra * K - 1) * H + N, (long)nspectra * K * H);
+    std::vector<gr_complex> x((size_t)nin);
+    std::vector<float> y((size_t)nspectra * N, -1.0f);
+    for (size_t i = 0; i < x.size(); i++) x[i] = gr_complex((float)std::cos(0.11 * i) + 0.25f, (float)std::sin(0.23 * i + 1.0));
+    long used = 0, made = 0;
+    for (int offered : {2, nspectra}) {  // spectra the buffer holds, from the start of the stream
+        gr_vector_int ni = {(int)(((long)offered * K - 1) * H + N + H / 2 - used)};  // (half a hop more than whole spectra need)
+        if (ni[0] > (int)(nin - used)) ni[0] = (int)(nin - used);
+        gr_vector_const_void_star in = {x.data() + used};
+        gr_vector_void_star out = {y.data() + made * N};
+        ps->reset_consumed();
+        ps->set_offered(ni);  // consuming more than was offered throws
+        const int got = ps->general_work(nspectra - (int)made, ni, in, out);
+        used += ps->nitems_consumed(0);
+        made += got;
+    }
+    ok = ok && made == nspectra && used == (long)nspectra * K * H;
+    double worst = 0, scale = 0;
+    for (int s = 0; s < nspectra && s < made; s++)
+        for (int b = 0; b < N; b++) {
+            double p = 0;
+            for (int k = 0; k < K; k++) {
+                std::complex<double> X(0, 0);
+                const gr_complex *f = x.data() + ((size_t)s * K + k) * H;
+                for (int n = 0; n < N; n++) {
+                    const double a = -2.0 * M_PI * (double)((long)b * n % N) / N;
+                    X += std::complex<double>(f[n]) * (hann ? (double)w[n] : 1.0) * std::complex<double>(std::cos(a), std::sin(a));
+                }
+                p += std::norm(X);
+            }
+            p *= 0.5 / K;
+            const int o = shift ? (b + N / 2) % N : b;  // out[(b + floor(N / 2)) mod N] = P[b]
+            worst = std::max(worst, std::abs(p - (double)y[(size_t)s * N + o]));
+            scale = std::max(scale, p);
+        }
+    return ok && scale > 0 && worst <= 1e-5 * scale;
+}
+#endif
+
+static int pspec_test(size_t n)
+{
+#ifdef MI355_WITH_GNURADIO
+    (void)n;
+    printf("--pspec-only acts as the scheduler of the stand-alone build (what general_work() consumed)\n");
+    return 2;
+#else
+    auto t0 = std::chrono::steady_clock::now();
+    bool ok = pspec_case(64, 5, 48, true, true, 6);
+    std::chrono::duration<double> dt = std::chrono::steady_clock::now() - t0;
+    report("clPowerSpectrum (64 points, 5 Hann frames, hop 48, shift)", 6 * 5 * 48, dt.count(), ok);
+    t0 = std::chrono::steady_clock::now();
+    ok = pspec_case(100, 3, 130, false, false, 5);
+    dt = std::chrono::steady_clock::now() - t0;
+    report("clPowerSpectrum (100 points, 3 frames, hop 130)", 5 * 3 * 130, dt.count(), ok);
+    const int N = 1024, K = 16;
+    const int S = (int)std::max<size_t>(n / ((size_t)N * K), 1);
+    auto ps = clPowerSpectrum::make(OCLTYPE_GPU, OCLDEVICESELECTOR_SPECIFIC, 0, g_dev, N, K);
+    gr_vector_int need(1, 0);
+    ps->forecast(S, need);
+    // a constant: all of its power in bin 0, N^2 |c|^2
+    std::vector<gr_complex> xi(need[0], gr_complex(1.0f, 0.5f));
+    std::vector<float> yo((size_t)S * N);
+    gr_vector_const_void_star in = {xi.data()};
+    gr_vector_void_star out = {yo.data()};
+    int got = 0;
+    const double t = time_calls([&] {
+        ps->reset_consumed();
+        ps->set_offered(need);  // (per call: the same buffer is offered again)
+        got = ps->general_work(S, need, in, out);
+    });
+    const float p0 = 1.25f * N * N;
+    report("clPowerSpectrum (1024 points, 16 frames, timing)", (size_t)S * N * K, t,
+           got == S && need[0] == S * K * N && std::abs(yo[0] - p0) <= 1e-5f * p0 && std::abs(yo[(size_t)(S - 1) * N] - p0) <= 1e-5f * p0 &&
+               std::abs(yo[1]) <= 1e-5f * p0);
+    return g_fail ? 1 : 0;
+#endif
+}
+
 int main(int argc, char **argv)
 {
     size_t n = 8192;  // the reference's default block size
     int fft_size = 4096, ntaps = 65;
-    bool only_fft = false, only_xcorrelate = false, xc_complex = false, only_loops = false, only_resampler = false, only_synth = false;
+    bool only_fft = false, only_xcorrelate = false, xc_complex = false, only_loops = false, only_resampler = false, only_synth = false, only_pspec = false;
     int xc_inputs = 2, xc_maxsearch = 512;
     for (int i = 1; i < argc; i++) {
         if (!strncmp(argv[i], "--device=", 9)) g_dev = atoi(argv[i] + 9);
@@ -686,6 +776,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--loops-only")) only_loops = true;
         else if (!strcmp(argv[i], "--resampler-only")) only_resampler = true;
         else if (!strcmp(argv[i], "--synth-only")) only_synth = true;
+        else if (!strcmp(argv[i], "--pspec-only")) only_pspec = true;
         else if (!strncmp(argv[i], "--num_inputs=", 13)) xc_inputs = atoi(argv[i] + 13);
         else if (!strncmp(argv[i], "--maxsearch=", 12)) xc_maxsearch = atoi(argv[i] + 12);
         else if (!strcmp(argv[i], "--input_complex")) xc_complex = true;
@@ -706,8 +797,9 @@ int main(int argc, char **argv)
                    "       %s --xcorrelate-only [--num_inputs=N] [--maxsearch=N] [--input_complex] [--iterations=N] [signal length]\n"
                    "       %s --loops-only [--iterations=N] [block size]\n"
                    "       %s --resampler-only [--iterations=N] [block size]\n"
-                   "       %s --synth-only [--iterations N] [block size]\n",
-                   argv[0], argv[0], argv[0], argv[0], argv[0]);
+                   "       %s --synth-only [--iterations N] [block size]\n"
+                   "       %s --pspec-only [--iterations N] [block size]\n",
+                   argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
             return 0;
         } else n = strtoull(argv[i], nullptr, 10);
     }
@@ -721,6 +813,10 @@ int main(int argc, char **argv)
     }
     if (only_synth) {
         try { return synth_test(n); }
+        catch (const std::exception &e) { std::cerr << "error: " << e.what() << std::endl; return 2; }
+    }
+    if (only_pspec) {
+        try { return pspec_test(n); }
         catch (const std::exception &e) { std::cerr << "error: " << e.what() << std::endl; return 2; }
     }
     if (only_xcorrelate) {

@@ -111,5 +111,26 @@ public:
     virtual std::string route() const = 0;
 };
 
+// gr::clenabled::clPowerSpectrum -- window, forward DFT, |X|^2, mean over navg frames that start hop items apart (0: fft_size), optionally
+// fftshift and 10 log10: the spectrum estimator (logpwrfft, Bartlett / Welch periodogram) in one block.  Beyond the reference module; the
+// contract is in mi355_clenabled.h.  A general block from complex items to vectors of fft_size floats: history max(fft_size - hop, 0) + 1,
+// one output vector per navg * hop items consumed (with hop > fft_size a spectrum is made once all navg * hop items are offered: the
+// block never consumes more than that).  An empty window is all ones.
+// (No per-block header of this name is installed by this build yet.)
+class CLENABLED_API clPowerSpectrum : virtual public gr::block {
+public:
+    typedef std::shared_ptr<clPowerSpectrum> sptr;
+    static sptr make(int openCLPlatformType, int devSelector, int platformId, int devId, int fft_size, int navg,
+                     const std::vector<float> &window = std::vector<float>(), int hop = 0, bool shift = false, bool log_output = false,
+                     float scale = 1.0f, int setDebug = 0);
+    virtual int fft_size() const = 0;
+    virtual int navg() const = 0;
+    virtual int hop() const = 0;
+    virtual void set_scale(float scale) = 0;
+    virtual void set_window(const std::vector<float> &window) = 0;  // empty: all ones
+    virtual void set_generic(bool on) = 0;                          // the generic route for every later call
+    virtual std::string route() const = 0;
+};
+
 }  // namespace clenabled
 }  // namespace gr

@@ -20,6 +20,7 @@
 #include <cstdint>
 #include <deque>
 #include <memory>
+#include <stdexcept>
 #include <string>
 #include <vector>
 typedef std::complex<float> gr_complex;
@@ -64,6 +65,7 @@ class basic_block_shim {
     int d_output_multiple = 1;
     uint64_t d_rate_interp = 1, d_rate_decim = 1;
     std::vector<long> d_consumed;  // per input, since the last reset_consumed()
+    std::vector<long> d_offered, d_offer_base;  // set_offered(): what the caller acting as scheduler offers the next general_work()
     std::vector<std::string> d_out_ports;
     std::deque<shim_message> d_messages;
     std::vector<uint64_t> d_first_tags;  // what get_tags_in_window(i, 0, 1) would return, set by the caller acting as scheduler
@@ -91,6 +93,9 @@ public:
     {
         if ((size_t)which_input >= d_consumed.size()) d_consumed.resize(which_input + 1, 0);
         d_consumed[which_input] += how_many;
+        // GNU Radio's read pointer must not pass its write pointer: a block never consumes more than it was offered
+        if ((size_t)which_input < d_offered.size() && d_consumed[which_input] - d_offer_base[which_input] > d_offered[which_input])
+            throw std::logic_error(d_name + ": consume() of more items than general_work() was offered");
     }
     void consume_each(int how_many)
     {
@@ -98,7 +103,19 @@ public:
         for (int i = 0; i < (n > 0 ? n : 1); i++) consume(i, how_many);
     }
     long nitems_consumed(int which_input) const { return (size_t)which_input < d_consumed.size() ? d_consumed[which_input] : 0; }
-    void reset_consumed() { d_consumed.assign(d_consumed.size(), 0); }
+    void reset_consumed()
+    {
+        d_consumed.assign(d_consumed.size(), 0);
+        d_offered.clear();
+        d_offer_base.clear();
+    }
+    // the items offered per input to the general_work() call that follows (ninput_items); consuming more than that throws
+    void set_offered(const std::vector<int> &ninput_items)
+    {
+        d_offered.assign(ninput_items.begin(), ninput_items.end());
+        d_offer_base.assign(ninput_items.size(), 0);
+        for (size_t i = 0; i < d_offer_base.size() && i < d_consumed.size(); i++) d_offer_base[i] = d_consumed[i];
+    }
     // message ports
     void message_port_register_out(const std::string &port) { d_out_ports.push_back(port); }
     const std::vector<std::string> &message_ports_out() const { return d_out_ports; }

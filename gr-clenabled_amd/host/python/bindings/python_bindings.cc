@@ -320,4 +320,44 @@ PYBIND11_MODULE(clenabled_python, m)
              py::arg("noutput_items"), py::arg("input_items"), py::arg("output_items"))
 #endif
         ;
+
+    // averaged power spectrum (lib/clPowerSpectrum_impl.cc).  general_work() is offered whatever the input array holds and returns
+    // (produced, consumed): whole spectra only (vectors of fft_size floats), as under the scheduler.
+    py::class_<clPowerSpectrum BLOCK_BASES, std::shared_ptr<clPowerSpectrum>>(m, "clPowerSpectrum")
+        .def(py::init(&clPowerSpectrum::make), py::arg("openCLPlatformType"), py::arg("devSelector"), py::arg("platformId"), py::arg("devId"),
+             py::arg("fft_size"), py::arg("navg"), py::arg("window") = std::vector<float>(), py::arg("hop") = 0, py::arg("shift") = false,
+             py::arg("log_output") = false, py::arg("scale") = 1.0f, py::arg("setDebug") = 0)
+        .def("fft_size", &clPowerSpectrum::fft_size)
+        .def("navg", &clPowerSpectrum::navg)
+        .def("hop", &clPowerSpectrum::hop)
+        .def("set_scale", &clPowerSpectrum::set_scale, py::arg("scale"))
+        .def("set_window", &clPowerSpectrum::set_window, py::arg("window"))
+        .def("set_generic", &clPowerSpectrum::set_generic, py::arg("on"))
+        .def("route", &clPowerSpectrum::route)
+        .def("history", [](clPowerSpectrum &b) { return b.history(); })
+        .def("forecast",
+             [](clPowerSpectrum &b, int noutput_items) {
+                 gr_vector_int req(1, 0);
+                 b.forecast(noutput_items, req);
+                 return req[0];
+             },
+             py::arg("noutput_items"))
+#ifndef MI355_WITH_GNURADIO
+        // stand-alone build only: consume_each() outside a flowgraph has nothing to report to
+        .def("general_work",
+             [](clPowerSpectrum &b, int noutput_items, const std::vector<py::array> &in, std::vector<py::array> out) {
+                 need(noutput_items >= 0, "noutput_items is negative");
+                 need(in.size() == 1 && out.size() == 1, "one input and one output");
+                 auto i = in_ptrs(in);
+                 auto o = out_ptrs(out);
+                 gr_vector_int n(1, (int)((size_t)in[0].nbytes() / sizeof(gr_complex)));
+                 need((size_t)out[0].nbytes() >= (size_t)noutput_items * sizeof(float) * (size_t)b.fft_size(), "output 0 holds fewer than noutput_items vectors");
+                 b.set_offered(n);  // consuming more than the array holds throws
+                 const long before = b.nitems_consumed(0);
+                 const int produced = b.general_work(noutput_items, n, i, o);
+                 return py::make_tuple(produced, b.nitems_consumed(0) - before);
+             },
+             py::arg("noutput_items"), py::arg("input_items"), py::arg("output_items"))
+#endif
+        ;
 }

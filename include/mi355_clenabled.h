@@ -578,6 +578,55 @@ const char *mi355_synth_route(const mi355_synth *h);
 int mi355_synth_work(mi355_synth *h, long long nframes, const void *in_with_history, void *out);
 int mi355_synth_work_dev(mi355_synth *h, long long nframes, const void *in_with_history, void *out, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Averaged power spectrum: clPowerSpectrum, window + forward DFT + |X|^2 + mean over K frames (+ dB) in one block.  Beyond the
+ * reference module, which has no spectrum estimator; the role is that of GNU Radio's logpwrfft and of the Bartlett / Welch
+ * periodogram (this comment is the contract).
+ *     N = fft_size;  w[0..N) = window (NULL / window_len 0: all ones; window_len must be N or 0);  K = navg >= 1 frames per spectrum;
+ *     H = hop >= 1 items from the start of one frame to the start of the next: H = N Bartlett, H < N Welch overlap, H > N skips
+ *     items (logpwrfft's frame-rate decimation; the skipped items are never read);  shift, log_output: 0 or 1;  scale: float.
+ * Input complex64 x, output float32; spectrum s = 0 .. S-1, bin b = 0 .. N-1:
+ *     P_s[b] = scale (1 / K) sum_{k < K} | DFT_N( w .* x[(s K + k) H + (0 .. N)) )[b] |^2        (forward DFT, unnormalised)
+ * shift: the output is in fftshift order, out[i] = P[(i + ceil(N / 2)) mod N] -- clFFT's permutation, odd N included, which is
+ * numpy's fftshift.  log_output: 10 log10(P) is written; P = 0 gives -inf, as in numpy.
+ * Buffers: a call for S spectra reads exactly (S K - 1) H + N input items (none when S = 0) and writes exactly S N floats; `in` may
+ * have any 8-byte and `out` any 4-byte alignment; a misaligned pointer, or in / out that overlap, is MI355_ERR_INVALID_ARG with nothing
+ * launched.  The next call's `in` is this call's in + S K H; history() of the block is max(N - H, 0).
+ * Routes, named by _route(): "fused pow2 N=1024 chunk=64" -- N = 16 .. 4096 a power of two: one kernel that keeps clFFT's transform in
+ * registers, adds re^2 + im^2 over a chunk of C frames per workgroup and stores N floats per chunk (K <= C: the finished spectrum;
+ * K > C: partial sums into a workspace of the handle, added in chunk order by a second, small kernel); "generic N=1000 batch=1048" --
+ * every other length mi355_fft_create takes, and every handle under _set_generic(h, 1): an internal clFFT handle transforms bounded
+ * batches of frames (gathered first when H != N) into a workspace and a second kernel adds |X|^2 over a spectrum's frames, k ascending.
+ * The partition of K and the order of every sum are functions of (N, K) alone and no float atomics are used: the bits of a spectrum
+ * depend neither on S nor on its place in the call, so any split of a stream into calls at spectrum boundaries, at any legal
+ * alignment, gives the same bits within a route; between routes the tolerance holds.
+ * Limits: N, K or H < 1, a window_len other than 0 or N: MI355_ERR_INVALID_ARG.  An N that mi355_fft_create would refuse (1, or above
+ * its range): MI355_ERR_UNSUPPORTED with clFFT's reason in mi355_last_error().  Item counts are long long; above 2^62 (_plan) or 2^44
+ * per call (_work, _work_dev): MI355_ERR_UNSUPPORTED.  Real input, exponential averaging across calls and one-sided output are not offered.
+ *   _plan        the arithmetic above, no device; either output pointer may be NULL
+ *   _create      everything that can be told without a device is checked before ctx is touched
+ *   _set_scale, _set_window   take effect at the next call; calls already enqueued keep what they were given
+ *   _set_generic on != 0: the generic route for every later call of the handle (there is no environment switch); 0: back
+ *   _route       valid until the next _set_generic / _destroy of the handle; "" for NULL
+ *   _work        host pointers, blocking (stages whole spectra through device buffers of the handle)
+ *   _work_dev    device pointers, enqueue only; nspectra == 0 is a no-op.  Calls that use the handle's workspace (K > C, generic)
+ *                from different streams are accepted and ordered on it; use one handle per stream for overlap.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct mi355_pspec mi355_pspec;
+int mi355_pspec_plan(int fft_size, int navg, int hop, long long nspectra, long long *ninput_items, long long *noutput_items);
+int mi355_pspec_create(mi355_ctx *ctx, int fft_size, const float *window, int window_len, int navg, int hop, int shift, int log_output,
+                       float scale, mi355_pspec **out);
+int mi355_pspec_destroy(mi355_pspec *h);
+int mi355_pspec_set_scale(mi355_pspec *h, float scale);
+int mi355_pspec_set_window(mi355_pspec *h, const float *window, int window_len);
+int mi355_pspec_set_generic(mi355_pspec *h, int on);
+int mi355_pspec_fft_size(const mi355_pspec *h);
+int mi355_pspec_navg(const mi355_pspec *h);
+int mi355_pspec_hop(const mi355_pspec *h);
+const char *mi355_pspec_route(const mi355_pspec *h);
+int mi355_pspec_work(mi355_pspec *h, long long nspectra, const void *in, void *out);
+int mi355_pspec_work_dev(mi355_pspec *h, long long nspectra, const void *in, void *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
