@@ -204,6 +204,24 @@ def lib():
         "mi355_pspec_route": (C.c_char_p, [vp]),
         "mi355_pspec_work": (i, [vp, ll, vp, vp]),
         "mi355_pspec_work_dev": (i, [vp, ll, vp, vp, vp]),
+        "mi355_xlate_plan": (i, [i, i, ll, llp, C.POINTER(i)]),
+        "mi355_xlate_create": (i, [vp, i, vp, i, i, d, dp, i, i, pp]),
+        "mi355_xlate_destroy": (i, [vp]),
+        "mi355_xlate_set_taps": (i, [vp, vp, i]),
+        "mi355_xlate_ntaps": (i, [vp]),
+        "mi355_xlate_get_taps": (i, [vp, vp, i]),
+        "mi355_xlate_num_channels": (i, [vp]),
+        "mi355_xlate_decimation": (i, [vp]),
+        "mi355_xlate_set_center_freq": (i, [vp, i, d]),
+        "mi355_xlate_get_center_freq": (i, [vp, i, dp]),
+        "mi355_xlate_get_bandpass_taps": (i, [vp, i, vp, i]),
+        "mi355_xlate_get_state": (i, [vp, i, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
+        "mi355_xlate_set_phase": (i, [vp, i, C.c_ulonglong]),
+        "mi355_xlate_skip": (i, [vp, ll]),
+        "mi355_xlate_set_generic": (i, [vp, i]),
+        "mi355_xlate_route": (C.c_char_p, [vp]),
+        "mi355_xlate_work": (i, [vp, ll, vp, pp]),
+        "mi355_xlate_work_dev": (i, [vp, ll, vp, pp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)  # AttributeError here = header/library mismatch: fail loudly

@@ -1189,3 +1189,121 @@ class clPowerSpectrum(_Block):
         check(self._L.mi355_pspec_work_dev(self._h, int(nspectra), _dp(input_items[0], nin * 8, "input"),
                                            _dp(output_items[0], nout * 4, "output"), _torch_stream(self.device)), "mi355_pspec_work_dev")
         return nout
+
+
+class clFreqXlatingFIRFilter(_Block):
+    """Frequency-translating FIR filter, the contract of GNU Radio's freq_xlating_fir_filter_ccf / ccc (beyond the reference module;
+    the contract is in include/mi355_clenabled.h): the band at `center_freq` is moved to baseband, filtered with `taps` and decimated.
+    `center_freq` is a scalar (one output stream) or a sequence (one output stream per frequency, all formed from one read of the
+    input).  Complex taps are detected from the array's dtype.  The input of a call is history-prefixed like clFilter's:
+    noutput * decimation + ntaps - 1 items, history() = ntaps.  The phase of every channel is a 64-bit integer kept across calls, so any
+    split of a stream into calls gives the same bits."""
+    _destroy = "mi355_xlate_destroy"
+
+    def __init__(self, openCLPlatformType, devSelector, platformId, devId, decimation, taps, center_freq, sampling_freq, use_time=False,
+                 setDebug=0):
+        super().__init__(openCLPlatformType, devSelector, platformId, devId, setDebug)
+        self._decim = int(decimation)
+        f = np.ascontiguousarray(np.atleast_1d(np.asarray(center_freq, dtype=np.float64))).reshape(-1)
+        self._nch = int(f.size)
+        a = np.asarray(taps)
+        self._complex = bool(np.iscomplexobj(a))
+        t = np.ascontiguousarray(a, dtype=np.complex64 if self._complex else np.float32).reshape(-1)
+        check(self._L.mi355_xlate_create(self._ctx, self._decim, _hp(t), int(t.size), 1 if self._complex else 0, float(sampling_freq),
+                                         f.ctypes.data_as(C.POINTER(C.c_double)), self._nch, 1 if use_time else 0, C.byref(self._h)),
+              "mi355_xlate_create")
+
+    def decimation(self):
+        return self._decim
+
+    def num_channels(self):
+        return self._nch
+
+    def ntaps(self):
+        return self._L.mi355_xlate_ntaps(self._h)
+
+    def history(self):
+        return self.ntaps()
+
+    def taps(self):
+        n = self.ntaps()
+        out = np.empty(n, np.complex64 if self._complex else np.float32)
+        check(min(self._L.mi355_xlate_get_taps(self._h, _hp(out), n), 0), "mi355_xlate_get_taps")
+        return out
+
+    def set_taps(self, taps):
+        a = np.asarray(taps)
+        if np.iscomplexobj(a) and not self._complex:
+            raise TypeError("complex taps for a filter created with real taps")
+        t = np.ascontiguousarray(a, dtype=np.complex64 if self._complex else np.float32).reshape(-1)
+        check(self._L.mi355_xlate_set_taps(self._h, _hp(t), int(t.size)), "mi355_xlate_set_taps")
+
+    def bandpass_taps(self, channel=0):
+        """the float32 band-pass taps b_c the kernels use"""
+        n = self.ntaps()
+        out = np.empty(n, np.complex64)
+        check(min(self._L.mi355_xlate_get_bandpass_taps(self._h, int(channel), _hp(out), n), 0), "mi355_xlate_get_bandpass_taps")
+        return out
+
+    def center_freq(self, channel=0):
+        f = C.c_double()
+        check(self._L.mi355_xlate_get_center_freq(self._h, int(channel), C.byref(f)), "mi355_xlate_get_center_freq")
+        return f.value
+
+    def set_center_freq(self, freq, channel=0):
+        """GNU Radio's set_center_freq(freq) for channel 0; the phase stays continuous"""
+        check(self._L.mi355_xlate_set_center_freq(self._h, int(channel), float(freq)), "mi355_xlate_set_center_freq")
+
+    def state(self, channel=0):
+        """(phase, increment) of the channel's 64-bit accumulator as Python integers: the phase of the next output"""
+        p, i = C.c_ulonglong(), C.c_ulonglong()
+        check(self._L.mi355_xlate_get_state(self._h, int(channel), C.byref(p), C.byref(i)), "mi355_xlate_get_state")
+        return p.value, i.value
+
+    def set_phase(self, phase, channel=0):
+        check(self._L.mi355_xlate_set_phase(self._h, int(channel), int(phase) % (1 << 64)), "mi355_xlate_set_phase")
+
+    def skip(self, noutputs):
+        """advance every channel's phase as if `noutputs` outputs had been made"""
+        check(self._L.mi355_xlate_skip(self._h, int(noutputs)), "mi355_xlate_skip")
+
+    def route(self):
+        return self._L.mi355_xlate_route(self._h).decode()
+
+    def set_generic(self, on):
+        check(self._L.mi355_xlate_set_generic(self._h, 1 if on else 0), "mi355_xlate_set_generic")
+
+    def plan(self, noutput_items):
+        """items of history-prefixed input a call of `noutput_items` outputs reads"""
+        nin = C.c_longlong()
+        check(self._L.mi355_xlate_plan(self._decim, self.ntaps(), int(noutput_items), C.byref(nin), None), "mi355_xlate_plan")
+        return nin.value
+
+    def work(self, noutput_items, input_items, output_items):
+        """host buffers; input_items[0] is the history-prefixed buffer, output_items one complex64 array per channel"""
+        n = int(noutput_items)
+        if n == 0:
+            return 0
+        x = _host(input_items[0], np.complex64)
+        need = self.plan(n)
+        if x.size < need:
+            raise ValueError("clFreqXlatingFIRFilter work(): need %d input items (history included), got %d" % (need, x.size))
+        if len(output_items) != self._nch:
+            raise ValueError("clFreqXlatingFIRFilter work(): %d channels, %d output buffers" % (self._nch, len(output_items)))
+        ys = [_host(y, np.complex64, writable=True) for y in output_items]
+        for y in ys:
+            _need("output", y, n)
+        ptrs = (C.c_void_p * self._nch)(*[y.ctypes.data for y in ys])
+        check(self._L.mi355_xlate_work(self._h, n, _hp(x), ptrs), "mi355_xlate_work")
+        return n
+
+    def work_device(self, noutput_items, input_items, output_items):
+        n = int(noutput_items)
+        if n == 0:
+            return 0
+        if len(output_items) != self._nch:
+            raise ValueError("clFreqXlatingFIRFilter work_device(): %d channels, %d output buffers" % (self._nch, len(output_items)))
+        xin = _dp(input_items[0], self.plan(n) * 8, "input")
+        ptrs = (C.c_void_p * self._nch)(*[_dp(y, n * 8, "output").value for y in output_items])
+        check(self._L.mi355_xlate_work_dev(self._h, n, xin, ptrs, _torch_stream(self.device)), "mi355_xlate_work_dev")
+        return n

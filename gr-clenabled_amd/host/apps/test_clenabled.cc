@@ -759,11 +759,71 @@ static int pspec_test(size_t n)
 #endif
 }
 
+// --xlate-only: two tones in one capture, one clFreqXlatingFIRFilter with two centre frequencies and a 32-tap boxcar whose nulls hold
+// the other tone: each tone must land at DC of its own output with its own amplitude and zero phase (the phase reference is item 0 of
+// the stream); then channel 0 is retuned to the second tone through the "freq" message port; then the time per work() call at
+// decimation 16, 65 taps, four channels.
+static int xlate_test(size_t n)
+{
+    const int K = 32, D = 8;
+    const double fs = 1.0e6, f0 = fs / 8, f1 = -fs / 4;
+    auto tone = [&](std::vector<gr_complex> &x, int hist) {
+        for (size_t i = 0; i < x.size(); i++) {
+            const double t = (double)i - hist;
+            x[i] = gr_complex((float)(std::cos(2.0 * M_PI * f0 / fs * t) + 0.5 * std::cos(2.0 * M_PI * f1 / fs * t)),
+                              (float)(std::sin(2.0 * M_PI * f0 / fs * t) + 0.5 * std::sin(2.0 * M_PI * f1 / fs * t)));
+        }
+    };
+    const int no = 1000;
+    auto fx = clFreqXlatingFIRFilter::make(OCLTYPE_GPU, OCLDEVICESELECTOR_SPECIFIC, 0, g_dev, D, std::vector<float>(K, 1.0f / K), {f0, f1}, fs);
+    bool ok = fx->num_channels() == 2 && (int)fx->history() == K && (int)fx->decimation() == D && fx->route().compare(0, 5, "fused") == 0;
+    std::vector<gr_complex> x((size_t)no * D + K - 1), y0(no, gr_complex(-9.f, -9.f)), y1(no, gr_complex(-9.f, -9.f));
+    tone(x, K - 1);
+    gr_vector_const_void_star in = {x.data()};
+    gr_vector_void_star out = {y0.data(), y1.data()};
+    auto t0 = std::chrono::steady_clock::now();
+    ok = ok && fx->work(no, in, out) == no;
+    std::chrono::duration<double> dt = std::chrono::steady_clock::now() - t0;
+    for (int m : {0, 1, no / 2, no - 1})
+        ok = ok && close_to(y0[m], gr_complex(1.0f, 0.0f), 1e-4f) && close_to(y1[m], gr_complex(0.5f, 0.0f), 1e-4f);
+    report("clFreqXlatingFIRFilter (two tones, two channels, decimation 8)", (size_t)no * D, dt.count(), ok);
+    // retune channel 0 to the second tone: the phase accumulator is kept, the magnitude is the second tone's
+#ifdef MI355_WITH_GNURADIO
+    fx->set_center_freq(f1, 0);
+#else
+    ok = fx->post_double("freq", f1) && !fx->post_double("nosuchport", 0.0);
+#endif
+    ok = ok && fx->center_freq(0) == f1 && fx->center_freq(1) == f1;
+    t0 = std::chrono::steady_clock::now();
+    ok = ok && fx->work(no, in, out) == no;
+    dt = std::chrono::steady_clock::now() - t0;
+    for (int m : {0, no - 1}) ok = ok && std::abs(std::abs(y0[m]) - 0.5f) <= 1e-4f && std::abs(std::abs(y1[m]) - 0.5f) <= 1e-4f;
+    report("clFreqXlatingFIRFilter (channel 0 retuned through the freq port)", (size_t)no * D, dt.count(), ok);
+    const int Dt = 16, Kt = 65, Ct = 4;
+    const int nt = (int)std::max<size_t>(n / Dt, 1);
+    std::vector<double> fc;
+    for (int c = 0; c < Ct; c++) fc.push_back((c - 1.5) * fs / 8);
+    std::vector<float> taps(Kt, 0.0f);
+    taps[0] = 1.0f;  // y_c[m] = r_c(m) x[m D]
+    auto ft = clFreqXlatingFIRFilter::make(OCLTYPE_GPU, OCLDEVICESELECTOR_SPECIFIC, 0, g_dev, Dt, taps, fc, fs);
+    std::vector<gr_complex> xi((size_t)nt * Dt + Kt - 1, gr_complex(1.0f, 0.5f));
+    std::vector<std::vector<gr_complex>> yo(Ct, std::vector<gr_complex>((size_t)nt));
+    gr_vector_const_void_star tin = {xi.data()};
+    gr_vector_void_star tout;
+    for (auto &v : yo) tout.push_back(v.data());
+    int got = 0;
+    const double t = time_calls([&] { got = ft->work(nt, tin, tout); });
+    bool tok = got == nt;
+    for (int c = 0; c < Ct; c++) tok = tok && std::abs(std::abs(yo[c][nt - 1]) - std::abs(gr_complex(1.0f, 0.5f))) <= 1e-5f;
+    report("clFreqXlatingFIRFilter (decimation 16, 65 taps, 4 channels, timing)", (size_t)nt * Dt, t, tok);
+    return g_fail ? 1 : 0;
+}
+
 int main(int argc, char **argv)
 {
     size_t n = 8192;  // the reference's default block size
     int fft_size = 4096, ntaps = 65;
-    bool only_fft = false, only_xcorrelate = false, xc_complex = false, only_loops = false, only_resampler = false, only_synth = false, only_pspec = false;
+    bool only_fft = false, only_xcorrelate = false, xc_complex = false, only_loops = false, only_resampler = false, only_synth = false, only_pspec = false, only_xlate = false;
     int xc_inputs = 2, xc_maxsearch = 512;
     for (int i = 1; i < argc; i++) {
         if (!strncmp(argv[i], "--device=", 9)) g_dev = atoi(argv[i] + 9);
@@ -777,6 +837,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--resampler-only")) only_resampler = true;
         else if (!strcmp(argv[i], "--synth-only")) only_synth = true;
         else if (!strcmp(argv[i], "--pspec-only")) only_pspec = true;
+        else if (!strcmp(argv[i], "--xlate-only")) only_xlate = true;
         else if (!strncmp(argv[i], "--num_inputs=", 13)) xc_inputs = atoi(argv[i] + 13);
         else if (!strncmp(argv[i], "--maxsearch=", 12)) xc_maxsearch = atoi(argv[i] + 12);
         else if (!strcmp(argv[i], "--input_complex")) xc_complex = true;
@@ -798,8 +859,9 @@ int main(int argc, char **argv)
                    "       %s --loops-only [--iterations=N] [block size]\n"
                    "       %s --resampler-only [--iterations=N] [block size]\n"
                    "       %s --synth-only [--iterations N] [block size]\n"
-                   "       %s --pspec-only [--iterations N] [block size]\n",
-                   argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
+                   "       %s --pspec-only [--iterations N] [block size]\n"
+                   "       %s --xlate-only [--iterations N] [block size]\n",
+                   argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
             return 0;
         } else n = strtoull(argv[i], nullptr, 10);
     }
@@ -817,6 +879,10 @@ int main(int argc, char **argv)
     }
     if (only_pspec) {
         try { return pspec_test(n); }
+        catch (const std::exception &e) { std::cerr << "error: " << e.what() << std::endl; return 2; }
+    }
+    if (only_xlate) {
+        try { return xlate_test(n); }
         catch (const std::exception &e) { std::cerr << "error: " << e.what() << std::endl; return 2; }
     }
     if (only_xcorrelate) {

@@ -132,5 +132,29 @@ public:
     virtual std::string route() const = 0;
 };
 
+// gr::clenabled::clFreqXlatingFIRFilter -- tune + FIR + decimate, the contract of GNU Radio's freq_xlating_fir_filter_ccf (make) / _ccc
+// (make_ccc), for one or several centre frequencies at once: one complex input, one complex output stream per centre frequency, all
+// formed from one read of the input.  Beyond the reference module; the contract is in mi355_clenabled.h.  A sync_decimator with
+// history ntaps; the message port "freq" retunes channel 0 (a pair whose cdr is a real number, as GNU Radio's block takes it).  The phase
+// of every channel is a 64-bit integer and stays continuous across set_center_freq(); taps() reports real taps with a zero imaginary
+// part.  set_taps() takes effect at once; the work() call after it only installs the new history and produces nothing (clFilter's rule).
+// (No per-block header of this name is installed by this build yet.)
+class CLENABLED_API clFreqXlatingFIRFilter : virtual public gr::sync_decimator {
+public:
+    typedef std::shared_ptr<clFreqXlatingFIRFilter> sptr;
+    static sptr make(int openCLPlatformType, int devSelector, int platformId, int devId, int decimation, const std::vector<float> &taps,
+                     const std::vector<double> &center_freqs, double sampling_freq, bool use_time = false, int setDebug = 0);
+    static sptr make_ccc(int openCLPlatformType, int devSelector, int platformId, int devId, int decimation, const std::vector<gr_complex> &taps,
+                         const std::vector<double> &center_freqs, double sampling_freq, bool use_time = false, int setDebug = 0);
+    virtual void set_center_freq(double center_freq, int channel = 0) = 0;
+    virtual double center_freq(int channel = 0) const = 0;
+    virtual std::vector<gr_complex> taps() const = 0;
+    virtual void set_taps(const std::vector<gr_complex> &taps) = 0;  // a block made with real taps refuses a non-zero imaginary part
+    virtual int num_channels() const = 0;
+    virtual void skip(long long noutputs) = 0;  // advance every phase as if that many outputs had been made (dropped upstream samples)
+    virtual void set_generic(bool on) = 0;      // the generic route for every later call
+    virtual std::string route() const = 0;
+};
+
 }  // namespace clenabled
 }  // namespace gr

@@ -19,6 +19,8 @@
 #include <complex>
 #include <cstdint>
 #include <deque>
+#include <functional>
+#include <map>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -66,7 +68,8 @@ class basic_block_shim {
     uint64_t d_rate_interp = 1, d_rate_decim = 1;
     std::vector<long> d_consumed;  // per input, since the last reset_consumed()
     std::vector<long> d_offered, d_offer_base;  // set_offered(): what the caller acting as scheduler offers the next general_work()
-    std::vector<std::string> d_out_ports;
+    std::vector<std::string> d_out_ports, d_in_ports;
+    std::map<std::string, std::function<void(double)>> d_in_handlers;
     std::deque<shim_message> d_messages;
     std::vector<uint64_t> d_first_tags;  // what get_tags_in_window(i, 0, 1) would return, set by the caller acting as scheduler
 
@@ -125,6 +128,18 @@ public:
         if (d_messages.empty()) return false;
         m = std::move(d_messages.front());
         d_messages.pop_front();
+        return true;
+    }
+    // input message ports that carry one real number (cons(key, double) under GNU Radio): the block registers a handler, the caller
+    // acting as scheduler delivers a value; false: no such port
+    void message_port_register_in(const std::string &port) { d_in_ports.push_back(port); }
+    const std::vector<std::string> &message_ports_in() const { return d_in_ports; }
+    void set_double_handler(const std::string &port, std::function<void(double)> fn) { d_in_handlers[port] = std::move(fn); }
+    bool post_double(const std::string &port, double value)
+    {
+        auto it = d_in_handlers.find(port);
+        if (it == d_in_handlers.end()) return false;
+        it->second(value);
         return true;
     }
     // stream tags: the first tag value of every input in the current window (set by the caller acting as scheduler)

@@ -360,4 +360,28 @@ PYBIND11_MODULE(clenabled_python, m)
              py::arg("noutput_items"), py::arg("input_items"), py::arg("output_items"))
 #endif
         ;
+
+    // frequency-translating FIR filter (lib/clFreqXlatingFIRFilter_impl.cc): one output array per centre frequency.  post_freq() is what
+    // a message on the "freq" port does (stand-alone build: there is no message passing to deliver one).
+    py::class_<clFreqXlatingFIRFilter DECIM_BASES, std::shared_ptr<clFreqXlatingFIRFilter>>(m, "clFreqXlatingFIRFilter")
+        .def(py::init(&clFreqXlatingFIRFilter::make), py::arg("openCLPlatformType"), py::arg("devSelector"), py::arg("platformId"), py::arg("devId"),
+             py::arg("decimation"), py::arg("taps"), py::arg("center_freqs"), py::arg("sampling_freq"), py::arg("use_time") = false,
+             py::arg("setDebug") = 0)
+        .def_static("make_ccc", &clFreqXlatingFIRFilter::make_ccc, py::arg("openCLPlatformType"), py::arg("devSelector"), py::arg("platformId"),
+                    py::arg("devId"), py::arg("decimation"), py::arg("taps"), py::arg("center_freqs"), py::arg("sampling_freq"),
+                    py::arg("use_time") = false, py::arg("setDebug") = 0)
+        .def("set_center_freq", &clFreqXlatingFIRFilter::set_center_freq, py::arg("center_freq"), py::arg("channel") = 0)
+        .def("center_freq", &clFreqXlatingFIRFilter::center_freq, py::arg("channel") = 0)
+        .def("taps", &clFreqXlatingFIRFilter::taps)
+        .def("set_taps", &clFreqXlatingFIRFilter::set_taps, py::arg("taps"))
+        .def("num_channels", &clFreqXlatingFIRFilter::num_channels)
+        .def("skip", &clFreqXlatingFIRFilter::skip, py::arg("noutputs"))
+        .def("set_generic", &clFreqXlatingFIRFilter::set_generic, py::arg("on"))
+        .def("route", &clFreqXlatingFIRFilter::route)
+        .def("history", [](clFreqXlatingFIRFilter &b) { return b.history(); })
+        .def("decimation", [](clFreqXlatingFIRFilter &b) { return b.decimation(); })
+#ifndef MI355_WITH_GNURADIO
+        .def("post_freq", [](clFreqXlatingFIRFilter &b, double f) { return b.post_double("freq", f); }, py::arg("freq"))
+#endif
+        .def("work", &call_work<clFreqXlatingFIRFilter>, py::arg("noutput_items"), py::arg("input_items"), py::arg("output_items"));
 }

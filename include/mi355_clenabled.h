@@ -627,6 +627,64 @@ const char *mi355_pspec_route(const mi355_pspec *h);
 int mi355_pspec_work(mi355_pspec *h, long long nspectra, const void *in, void *out);
 int mi355_pspec_work_dev(mi355_pspec *h, long long nspectra, const void *in, void *out, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Frequency-translating FIR filter: clFreqXlatingFIRFilter, tune + low-pass + decimate for C channels of one wideband stream.  Beyond
+ * the reference module; the contract is GNU Radio's freq_xlating_fir_filter_ccf / ccc (this comment is the contract).
+ *     h[0..K) = prototype taps (float, or complex64 with complex_taps != 0);  D = decimation >= 1;  fs = samp_rate > 0;
+ *     f_c = center_freqs[c], c = 0 .. C-1, C = nfreq >= 1.  All channels share h and D.
+ * Input: GNU Radio's history-prefixed buffer of complex64, in[K-1] is x[0]; a call for n outputs reads exactly n D + K - 1 items (none
+ * when n = 0) and writes exactly n complex64 items to each of the C buffers outs[0..C).  Output m (counted since create) of channel c:
+ *     y_c[m] = r_c(m) sum_k b_c[k] x[m D - k]
+ *     b_c[k] = h[k] exp(+j 2 pi frac(k f_c / fs))        float64 on the host, rounded to float32 (_get_bandpass_taps)
+ *     r_c(m) = exp(-j 2 pi P_c(m) / 2^64),   P_c(m) = (P_c(0) + inc_c m) mod 2^64,    inc_c = round(frac(f_c D / fs) 2^64) mod 2^64
+ * (inc_c is evaluated on the signed fraction nearest zero, so -f gives exactly 2^64 - inc.)
+ * -- band-pass taps, decimate, rotate by -omega D per output, which is mixing x down by f_c, filtering with h and decimating.  The
+ * phase is a 64-bit fixed-point accumulator kept on the host per channel (P_c = 0 at create, advanced by inc_c n after a call of n
+ * outputs) and evaluated on the device in integer arithmetic per output, then one double sincospi, rounded to float: nothing drifts at
+ * any stream length, and _set_center_freq keeps P_c (the phase is continuous across a retune; inc_c and b_c are rebuilt).
+ * Routes, named by _route() and decided at _create / _set_taps from (D, K, C) alone: "fused D=16 K=65 C=8 tile_out=128" -- D = 2 .. 64,
+ * K <= 512, C <= 16 and taps + tile within 160 KiB of LDS: one kernel that stages a tile's input span once and forms the outputs of all
+ * C channels from it; "generic D=1 K=3000 C=20" -- everything else, and every handle under _set_generic(h, 1): per channel an internal
+ * clComplexFilter handle (taps b_c, decimation D, the use_time given here) and an in-place rotate kernel with the same integer phase.
+ * Fused route: any split of a stream into calls and any 8-byte alignment of `in` / outs[c] give the same bits.  Generic route: the bits
+ * are clComplexFilter's, rotated -- the same for any split as long as clComplexFilter picks the same kernel (direct form: it looks at
+ * the 16-byte alignment of `in`; overlap-save blocks start at a call's first output).  Between routes the tolerance holds.
+ * Errors (nothing launched): NULL pointers, `in` or an outs[c] not 8-byte aligned, `in` overlapping an output, nfreq < 1, samp_rate
+ * <= 0 or not finite, a frequency that is not finite, c out of range: MI355_ERR_INVALID_ARG.  More than 4096 channels, more than 2^62
+ * items (_plan) or 2^44 input items per call: MI355_ERR_UNSUPPORTED.
+ *   _plan         ninput_items = noutput D + K - 1 (0 for no output), history = K (GNU Radio's set_history(K)); no device; either
+ *                 output pointer may be NULL
+ *   _create       everything that can be told without a device is checked before ctx is touched
+ *   _set_taps     new prototype (same kind as at create), any length; phases are kept; the route is decided again
+ *   _get_taps / _get_bandpass_taps   return K; cap counts taps; the band-pass taps are complex64 whatever the prototype
+ *   _get_state    P_c of the next output and inc_c (either pointer may be NULL);  _set_phase sets P_c
+ *   _skip         advances every P_c as if noutputs outputs had been made, no device work (dropped upstream samples, resuming a stream)
+ *   _set_generic  on != 0: the generic route for every later call of the handle (there is no environment switch); 0: back
+ *   _route        valid until the next _set_generic / _set_taps / _destroy of the handle; "" for NULL
+ *   _work         host pointers, blocking (pieces staged through pinned buffers of the handle)
+ *   _work_dev     device pointers (outs: a host array of C device pointers), enqueue only; noutput == 0 is a no-op
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct mi355_xlate mi355_xlate;
+int mi355_xlate_plan(int decimation, int ntaps, long long noutput, long long *ninput_items, int *history);
+int mi355_xlate_create(mi355_ctx *ctx, int decimation, const void *taps, int ntaps, int complex_taps, double samp_rate,
+                       const double *center_freqs, int nfreq, int use_time, mi355_xlate **out);
+int mi355_xlate_destroy(mi355_xlate *h);
+int mi355_xlate_set_taps(mi355_xlate *h, const void *taps, int ntaps);
+int mi355_xlate_ntaps(const mi355_xlate *h);
+int mi355_xlate_get_taps(const mi355_xlate *h, void *taps_out, int cap);
+int mi355_xlate_num_channels(const mi355_xlate *h);
+int mi355_xlate_decimation(const mi355_xlate *h);
+int mi355_xlate_set_center_freq(mi355_xlate *h, int c, double freq);
+int mi355_xlate_get_center_freq(const mi355_xlate *h, int c, double *freq);
+int mi355_xlate_get_bandpass_taps(const mi355_xlate *h, int c, void *out, int cap);
+int mi355_xlate_get_state(const mi355_xlate *h, int c, unsigned long long *phase, unsigned long long *inc);
+int mi355_xlate_set_phase(mi355_xlate *h, int c, unsigned long long phase);
+int mi355_xlate_skip(mi355_xlate *h, long long noutputs);
+int mi355_xlate_set_generic(mi355_xlate *h, int on);
+const char *mi355_xlate_route(const mi355_xlate *h);
+int mi355_xlate_work(mi355_xlate *h, long long noutput, const void *in_with_history, void *const *outs);
+int mi355_xlate_work_dev(mi355_xlate *h, long long noutput, const void *in_with_history, void *const *outs, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
