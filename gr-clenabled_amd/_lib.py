@@ -222,6 +222,19 @@ def lib():
         "mi355_xlate_route": (C.c_char_p, [vp]),
         "mi355_xlate_work": (i, [vp, ll, vp, pp]),
         "mi355_xlate_work_dev": (i, [vp, ll, vp, pp, vp]),
+        "mi355_beamform_plan": (i, [i, i, i, i, i, i, i, llp, C.POINTER(i), llp]),
+        "mi355_beamform_create": (i, [vp, i, i, i, i, i, i, i, vp, pp]),
+        "mi355_beamform_destroy": (i, [vp]),
+        "mi355_beamform_set_weights": (i, [vp, vp]),
+        "mi355_beamform_set_beam_weights": (i, [vp, i, vp]),
+        "mi355_beamform_get_weights": (i, [vp, vp, ll]),
+        "mi355_beamform_num_beams": (i, [vp]),
+        "mi355_beamform_frame_bytes": (ll, [vp]),
+        "mi355_beamform_out_bytes_per_unit": (ll, [vp]),
+        "mi355_beamform_set_generic": (i, [vp, i]),
+        "mi355_beamform_route": (C.c_char_p, [vp]),
+        "mi355_beamform_work": (i, [vp, ll, vp, vp]),
+        "mi355_beamform_work_dev": (i, [vp, ll, vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)  # AttributeError here = header/library mismatch: fail loudly

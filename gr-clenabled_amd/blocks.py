@@ -1307,3 +1307,100 @@ class clFreqXlatingFIRFilter(_Block):
         ptrs = (C.c_void_p * self._nch)(*[_dp(y, n * 8, "output").value for y in output_items])
         check(self._L.mi355_xlate_work_dev(self._h, n, xin, ptrs, _torch_stream(self.device)), "mi355_xlate_work_dev")
         return n
+
+
+BEAMFORM_VOLTAGE, BEAMFORM_POWER = 0, 1
+
+
+class clBeamformer(_Block):
+    """Tied-array beamformer on the X-engine's int8 frames (beyond the reference module; the contract is in include/mi355_clenabled.h):
+    per channel and polarisation, `num_beams` weighted sums of the `num_inputs` stations with complex int8 weights, as voltage beams
+    (complex64 holding exact integers, one unit = one frame) or as power integrated over `integration` frames (float32 of an exact
+    int64 sum, one unit = one window; `stokes_i` adds the two polarisations).  `weights`: int8 in the layout [f][p][b][s]{re, im},
+    components -127 .. 127, or None for all zero.  Every output is bit-exact on either route and for any split into calls."""
+    _destroy = "mi355_beamform_destroy"
+
+    def __init__(self, openCLPlatformType, devSelector, platformId, devId, mode, polarization, num_inputs, num_channels, num_beams,
+                 integration=1, stokes_i=False, weights=None, setDebug=0):
+        self.mode, self.npol = int(mode), int(polarization)
+        self.num_inputs, self.num_channels, self.num_beams = int(num_inputs), int(num_channels), int(num_beams)
+        self.integration, self.stokes_i = int(integration), 1 if stokes_i else 0
+        L = lib()
+        fb, fpu, ob = C.c_longlong(), C.c_int(), C.c_longlong()
+        # argument errors before a context exists
+        check(L.mi355_beamform_plan(self.mode, self.npol, self.num_inputs, self.num_channels, self.num_beams, self.integration, self.stokes_i,
+                                    C.byref(fb), C.byref(fpu), C.byref(ob)), "mi355_beamform_plan")
+        self._frame_bytes, self._fpu, self._out_bytes = fb.value, fpu.value, ob.value
+        w = None if weights is None else self._weights(weights, self.weight_bytes())
+        super().__init__(openCLPlatformType, devSelector, platformId, devId, setDebug)
+        check(self._L.mi355_beamform_create(self._ctx, self.mode, self.npol, self.num_inputs, self.num_channels, self.num_beams,
+                                            self.integration, self.stokes_i, None if w is None else _hp(w), C.byref(self._h)),
+              "mi355_beamform_create")
+
+    @staticmethod
+    def _weights(w, nbytes):
+        a = np.ascontiguousarray(w)
+        if a.dtype != np.int8:
+            raise TypeError("weights are int8 {re, im} pairs")
+        if a.size != nbytes:
+            raise ValueError("weights hold %d bytes, the geometry needs %d" % (a.size, nbytes))
+        return a
+
+    def weight_bytes(self):
+        return 2 * self.num_channels * self.npol * self.num_beams * self.num_inputs
+
+    def frame_bytes(self):
+        return self._frame_bytes
+
+    def frames_per_unit(self):
+        return self._fpu
+
+    def out_bytes_per_unit(self):
+        return self._out_bytes
+
+    def out_items_per_unit(self):
+        return self._out_bytes // (8 if self.mode == BEAMFORM_VOLTAGE else 4)
+
+    def route(self):
+        return self._L.mi355_beamform_route(self._h).decode()
+
+    def set_generic(self, on):
+        check(self._L.mi355_beamform_set_generic(self._h, 1 if on else 0), "mi355_beamform_set_generic")
+
+    def set_weights(self, weights):
+        check(self._L.mi355_beamform_set_weights(self._h, _hp(self._weights(weights, self.weight_bytes()))), "mi355_beamform_set_weights")
+
+    def set_beam_weights(self, beam, w_beam):
+        """the weights of one beam, [f][p][s]{re, im}"""
+        w = self._weights(w_beam, 2 * self.num_channels * self.npol * self.num_inputs)
+        check(self._L.mi355_beamform_set_beam_weights(self._h, int(beam), _hp(w)), "mi355_beamform_set_beam_weights")
+
+    def weights(self):
+        out = np.empty((self.num_channels, self.npol, self.num_beams, self.num_inputs, 2), np.int8)
+        check(self._L.mi355_beamform_get_weights(self._h, _hp(out), out.nbytes), "mi355_beamform_get_weights")
+        return out
+
+    def _out_dtype(self):
+        return np.complex64 if self.mode == BEAMFORM_VOLTAGE else np.float32
+
+    def work(self, nunits, input_items, output_items):
+        """host buffers: input_items[0] int8 frames (nunits * frames_per_unit of them), output_items[0] complex64 / float32"""
+        n = int(nunits)
+        if n == 0:
+            return 0
+        x = _host(input_items[0])
+        if x.nbytes < n * self._fpu * self._frame_bytes:
+            raise ValueError("clBeamformer work(): need %d input bytes, got %d" % (n * self._fpu * self._frame_bytes, x.nbytes))
+        y = _host(output_items[0], self._out_dtype(), writable=True)
+        _need("output", y, n * self.out_items_per_unit())
+        check(self._L.mi355_beamform_work(self._h, n, _hp(x), _hp(y)), "mi355_beamform_work")
+        return n
+
+    def work_device(self, nunits, input_items, output_items):
+        n = int(nunits)
+        if n == 0:
+            return 0
+        check(self._L.mi355_beamform_work_dev(self._h, n, _dp(input_items[0], n * self._fpu * self._frame_bytes, "input"),
+                                              _dp(output_items[0], n * self._out_bytes, "output"), _torch_stream(self.device)),
+              "mi355_beamform_work_dev")
+        return n

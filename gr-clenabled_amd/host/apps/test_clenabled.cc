@@ -819,11 +819,69 @@ static int xlate_test(size_t n)
     return g_fail ? 1 : 0;
 }
 
+// --beamform-only: clBeamformer at (S, B, F, npol) = (20, 5, 8, 2) on frames and weights from a 32-bit linear congruential generator
+// (state = 1664525 state + 1013904223, the top byte of each state; a weight of -128 becomes -127): 17 frames of voltage beams and 4
+// windows of 4 frames of Stokes-I power.  Prints "checksum" lines that tests/test_beamform_gpu.py compares with the integer reference:
+// voltage sum_i (i % 7 + 1) re_i + (i % 5 + 1) im_i, power sum_i (i % 7 + 1) P_i over the outputs in memory order; then one timing row.
+static int beamform_test(size_t n)
+{
+    const int S = 20, B = 5, F = 8, npol = 2, T = 17, Ti = 4, W = 4;
+    uint32_t state = 12345u;
+    auto next = [&]() { state = state * 1664525u + 1013904223u; return (int8_t)(state >> 24); };
+    std::vector<int8_t> x((size_t)T * S * F * npol * 2), w((size_t)F * npol * B * S * 2);
+    for (auto &v : x) v = next();
+    for (auto &v : w) { v = next(); if (v == -128) v = -127; }
+    bool ok = true;
+    {
+        auto bf = clBeamformer::make(OCLTYPE_GPU, OCLDEVICESELECTOR_SPECIFIC, 0, g_dev, 0, npol, S, F, B, 1, false, w);
+        ok = bf->num_beams() == B && bf->frame_bytes() == 2ll * S * F * npol && bf->decimation() == 1 && bf->route().compare(0, 4, "mfma") == 0 &&
+             bf->weights() == w;
+        std::vector<gr_complex> y((size_t)T * B * F * npol, gr_complex(-9.f, -9.f));
+        gr_vector_const_void_star in = {x.data()};
+        gr_vector_void_star out = {y.data()};
+        auto t0 = std::chrono::steady_clock::now();
+        ok = ok && bf->work(T, in, out) == T;
+        std::chrono::duration<double> dt = std::chrono::steady_clock::now() - t0;
+        long long sum = 0;
+        for (size_t i = 0; i < y.size(); i++) sum += (long long)(i % 7 + 1) * (long long)y[i].real() + (long long)(i % 5 + 1) * (long long)y[i].imag();
+        printf("clBeamformer voltage checksum %lld\n", sum);
+        report("clBeamformer (voltage, 20 inputs, 5 beams, 8 channels, 2 pol)", (size_t)T, dt.count(), ok);
+    }
+    {
+        auto bf = clBeamformer::make(OCLTYPE_GPU, OCLDEVICESELECTOR_SPECIFIC, 0, g_dev, 1, npol, S, F, B, Ti, true);
+        bf->set_weights(w);
+        bool pok = (int)bf->decimation() == Ti && bf->out_bytes_per_unit() == 4ll * B * F;
+        std::vector<float> p((size_t)W * B * F, -9.f);
+        gr_vector_const_void_star in = {x.data()};
+        gr_vector_void_star out = {p.data()};
+        auto t0 = std::chrono::steady_clock::now();
+        pok = pok && bf->work(W, in, out) == W;
+        std::chrono::duration<double> dt = std::chrono::steady_clock::now() - t0;
+        double sum = 0.0;
+        for (size_t i = 0; i < p.size(); i++) sum += (double)(i % 7 + 1) * (double)p[i];
+        printf("clBeamformer power checksum %.0f\n", sum);
+        report("clBeamformer (Stokes I power, 4 windows of 4 frames)", (size_t)W * Ti, dt.count(), pok);
+    }
+    {
+        const int St = 64, Bt = 64, Ft = 64, nt = (int)std::max<size_t>(n / 1024, 16);
+        std::vector<int8_t> xt((size_t)nt * St * Ft * 2 * 2, 3), wt((size_t)Ft * 2 * Bt * St * 2, 0);
+        for (size_t i = 0; i < wt.size(); i += 2) wt[i] = 1;  // every beam the plain sum of the stations
+        auto bf = clBeamformer::make(OCLTYPE_GPU, OCLDEVICESELECTOR_SPECIFIC, 0, g_dev, 0, 2, St, Ft, Bt, 1, false, wt);
+        std::vector<gr_complex> y((size_t)nt * Bt * Ft * 2);
+        gr_vector_const_void_star in = {xt.data()};
+        gr_vector_void_star out = {y.data()};
+        int got = 0;
+        const double t = time_calls([&] { got = bf->work(nt, in, out); });
+        report("clBeamformer (voltage, 64 x 64 x 64 x 2, timing)", (size_t)nt, t, got == nt && y.back() == gr_complex(3.f * St, 3.f * St));
+    }
+    return g_fail ? 1 : 0;
+}
+
 int main(int argc, char **argv)
 {
     size_t n = 8192;  // the reference's default block size
     int fft_size = 4096, ntaps = 65;
-    bool only_fft = false, only_xcorrelate = false, xc_complex = false, only_loops = false, only_resampler = false, only_synth = false, only_pspec = false, only_xlate = false;
+    bool only_fft = false, only_xcorrelate = false, xc_complex = false, only_loops = false, only_resampler = false, only_synth = false, only_pspec = false, only_xlate = false, only_beamform = false;
     int xc_inputs = 2, xc_maxsearch = 512;
     for (int i = 1; i < argc; i++) {
         if (!strncmp(argv[i], "--device=", 9)) g_dev = atoi(argv[i] + 9);
@@ -838,6 +896,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--synth-only")) only_synth = true;
         else if (!strcmp(argv[i], "--pspec-only")) only_pspec = true;
         else if (!strcmp(argv[i], "--xlate-only")) only_xlate = true;
+        else if (!strcmp(argv[i], "--beamform-only")) only_beamform = true;
         else if (!strncmp(argv[i], "--num_inputs=", 13)) xc_inputs = atoi(argv[i] + 13);
         else if (!strncmp(argv[i], "--maxsearch=", 12)) xc_maxsearch = atoi(argv[i] + 12);
         else if (!strcmp(argv[i], "--input_complex")) xc_complex = true;
@@ -860,8 +919,9 @@ int main(int argc, char **argv)
                    "       %s --resampler-only [--iterations=N] [block size]\n"
                    "       %s --synth-only [--iterations N] [block size]\n"
                    "       %s --pspec-only [--iterations N] [block size]\n"
-                   "       %s --xlate-only [--iterations N] [block size]\n",
-                   argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
+                   "       %s --xlate-only [--iterations N] [block size]\n"
+                   "       %s --beamform-only [--iterations N] [block size]\n",
+                   argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
             return 0;
         } else n = strtoull(argv[i], nullptr, 10);
     }
@@ -883,6 +943,10 @@ int main(int argc, char **argv)
     }
     if (only_xlate) {
         try { return xlate_test(n); }
+        catch (const std::exception &e) { std::cerr << "error: " << e.what() << std::endl; return 2; }
+    }
+    if (only_beamform) {
+        try { return beamform_test(n); }
         catch (const std::exception &e) { std::cerr << "error: " << e.what() << std::endl; return 2; }
     }
     if (only_xcorrelate) {

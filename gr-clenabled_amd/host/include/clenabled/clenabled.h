@@ -156,5 +156,29 @@ public:
     virtual std::string route() const = 0;
 };
 
+// gr::clenabled::clBeamformer -- tied-array beamformer on the X-engine's int8 frames: num_beams weighted sums of the num_inputs stations
+// per channel and polarisation, complex int8 weights, integer-exact.  Beyond the reference module; the contract is in mi355_clenabled.h.
+// One input stream whose item is a frame (frame_bytes() = 2 num_inputs num_channels npol bytes), one output stream whose item is a unit's
+// output: mode 0 (VOLTAGE) num_beams num_channels npol gr_complex per frame -- decimation 1, a sync_block in all but name -- and mode 1
+// (POWER) num_beams num_channels (stokes_i ? 1 : npol) floats per `integration` frames, a sync_decimator by `integration`.  Weights are
+// int8 {re, im} in the layout [f][p][b][s], -127 .. 127; an empty vector at make() is all zero.  There is no message port: weights are
+// set through set_weights() / set_beam_weights(), and a work() call uses one weight set entirely.
+// (No per-block header of this name is installed by this build yet.)
+class CLENABLED_API clBeamformer : virtual public gr::sync_decimator {
+public:
+    typedef std::shared_ptr<clBeamformer> sptr;
+    static sptr make(int openCLPlatformType, int devSelector, int platformId, int devId, int mode, int polarization, int num_inputs,
+                     int num_channels, int num_beams, int integration = 1, bool stokes_i = false,
+                     const std::vector<int8_t> &weights = std::vector<int8_t>(), int setDebug = 0);
+    virtual void set_weights(const std::vector<int8_t> &weights) = 0;                     // 2 F npol B S bytes, anything else throws
+    virtual void set_beam_weights(int beam, const std::vector<int8_t> &w_beam) = 0;      // 2 F npol S bytes, [f][p][s]
+    virtual std::vector<int8_t> weights() const = 0;
+    virtual int num_beams() const = 0;
+    virtual long long frame_bytes() const = 0;
+    virtual long long out_bytes_per_unit() const = 0;
+    virtual void set_generic(bool on) = 0;  // the generic route for every later call
+    virtual std::string route() const = 0;
+};
+
 }  // namespace clenabled
 }  // namespace gr

@@ -384,4 +384,35 @@ PYBIND11_MODULE(clenabled_python, m)
         .def("post_freq", [](clFreqXlatingFIRFilter &b, double f) { return b.post_double("freq", f); }, py::arg("freq"))
 #endif
         .def("work", &call_work<clFreqXlatingFIRFilter>, py::arg("noutput_items"), py::arg("input_items"), py::arg("output_items"));
+
+    // tied-array beamformer (lib/clBeamformer_impl.cc): input items are int8 frames, output items one unit's complex64 / float32 values;
+    // weights go in and out as int8 arrays in the layout [f][p][b][s]{re, im}
+    using i8array = py::array_t<int8_t, py::array::c_style | py::array::forcecast>;
+    py::class_<clBeamformer DECIM_BASES, std::shared_ptr<clBeamformer>>(m, "clBeamformer")
+        .def(py::init([](int openCLPlatformType, int devSelector, int platformId, int devId, int mode, int polarization, int num_inputs,
+                         int num_channels, int num_beams, int integration, bool stokes_i, const i8array &weights, int setDebug) {
+                 return clBeamformer::make(openCLPlatformType, devSelector, platformId, devId, mode, polarization, num_inputs, num_channels,
+                                           num_beams, integration, stokes_i, std::vector<int8_t>(weights.data(), weights.data() + weights.size()),
+                                           setDebug);
+             }),
+             py::arg("openCLPlatformType"), py::arg("devSelector"), py::arg("platformId"), py::arg("devId"), py::arg("mode"),
+             py::arg("polarization"), py::arg("num_inputs"), py::arg("num_channels"), py::arg("num_beams"), py::arg("integration") = 1,
+             py::arg("stokes_i") = false, py::arg("weights") = i8array(0), py::arg("setDebug") = 0)
+        .def("set_weights", [](clBeamformer &b, const i8array &w) { b.set_weights(std::vector<int8_t>(w.data(), w.data() + w.size())); },
+             py::arg("weights"))
+        .def("set_beam_weights",
+             [](clBeamformer &b, int beam, const i8array &w) { b.set_beam_weights(beam, std::vector<int8_t>(w.data(), w.data() + w.size())); },
+             py::arg("beam"), py::arg("w_beam"))
+        .def("weights",
+             [](clBeamformer &b) {
+                 const std::vector<int8_t> w = b.weights();
+                 return i8array(w.size(), w.data());
+             })
+        .def("num_beams", &clBeamformer::num_beams)
+        .def("frame_bytes", &clBeamformer::frame_bytes)
+        .def("out_bytes_per_unit", &clBeamformer::out_bytes_per_unit)
+        .def("set_generic", &clBeamformer::set_generic, py::arg("on"))
+        .def("route", &clBeamformer::route)
+        .def("decimation", [](clBeamformer &b) { return b.decimation(); })
+        .def("work", &call_work<clBeamformer>, py::arg("noutput_items"), py::arg("input_items"), py::arg("output_items"));
 }

@@ -685,6 +685,67 @@ const char *mi355_xlate_route(const mi355_xlate *h);
 int mi355_xlate_work(mi355_xlate *h, long long noutput, const void *in_with_history, void *const *outs);
 int mi355_xlate_work_dev(mi355_xlate *h, long long noutput, const void *in_with_history, void *const *outs, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Tied-array beamformer: clBeamformer, B beams from the S inputs of the X-engine's int8 frames, per channel a complex int8 weight
+ * matrix, delivered as voltage beams or as detected, time-integrated power.  Beyond the reference module, which has no beamformer
+ * (this comment is the contract).  Both modes are integer-exact: there is no tolerance anywhere.
+ *     mode = MI355_BEAMFORM_VOLTAGE (0) or MI355_BEAMFORM_POWER (1);  npol = 1 or 2;  S = num_inputs 1 .. 512;  F = num_channels >= 1;
+ *     B = num_beams 1 .. 1024;  Ti = integration 1 .. 4096 (POWER only, it must be 1 for VOLTAGE);  stokes_i = 0 or 1 (POWER only, and
+ *     it needs npol = 2).
+ * Input: the X-engine's BYTE frame layout.  One frame is x[s][f][p] = int8 {I, Q}, frame_bytes = 2 S F npol, frames consecutive in
+ * time; every int8 value is legal, -128 included.
+ * Weights: w[f][p][b][s] = int8 {re, im}, 2 F npol B S bytes.  Every component must lie in -127 .. 127: a -128 is
+ * MI355_ERR_INVALID_ARG (which lets a kernel negate a weight byte without overflow).  weights == NULL at _create means all zero.
+ * VOLTAGE, for each frame t:
+ *     y[t][b][f][p] = sum_s w[f][p][b][s] x[t][s][f][p]
+ * a complex product in integer arithmetic, exact in int32: each component satisfies |component| <= S 2 127 128 <= 16 646 144 < 2^24
+ * (the reason for S <= 512), so the complex64 output, layout [t][b][f][p], holds the exact integers.  The unit of work is one frame; a
+ * unit writes B F npol complex64.
+ * POWER, for each window W of Ti consecutive frames:
+ *     P[W][b][f][p] = (float) sum_{t in W} (re^2 + im^2)
+ * the sum taken exactly in int64 (bounded by 2 (1.67e7)^2 4096 2 = 4.6e18 < 2^63, the reason for Ti <= 4096) and converted to float32
+ * once, round to nearest even.  With stokes_i the sum also runs over p and the output is [W][b][f].  The unit of work is one window; a
+ * unit writes B F (stokes_i ? 1 : npol) floats.
+ * Any split of a stream into calls at unit boundaries, any legal alignment and either route give identical bits.
+ * Routes, decided at _create from the geometry alone and named by _route(): "mfma S=64 B=64 F=1024 npol=2 kblocks=2 beam_tiles=4" --
+ * F npol 2 a multiple of 16 and S <= 256 (any B): per (f, p) the product (B x S) . (S x time) on v_mfma_i32_16x16x64_i8 with K = the
+ * interleaved (station, {I, Q}) bytes, zero padded in registers (nothing past a frame is read); "generic S=3 B=2 F=5 npol=1" --
+ * everything else, every handle under _set_generic(h, 1), and any single call whose `in` is not 16-byte aligned: one thread per output,
+ * the same integer arithmetic.  The route is forced by _set_generic only; there is no environment switch.
+ * Weight updates: a call enqueued before _set_weights / _set_beam_weights returns uses the old weights entirely, a later call the new
+ * ones entirely (versioned device buffers; an old version is released behind the event of its last launch, when the next update or
+ * _destroy finds it complete; nothing on the work path waits for the device).
+ * Errors (nothing launched): NULL pointers, `in` not 2-byte aligned, `out` not 8-byte (VOLTAGE) / 4-byte (POWER) aligned, `in`
+ * overlapping `out`, a parameter outside the ranges above, a weight of -128, `beam` out of range: MI355_ERR_INVALID_ARG.  More than 2^40
+ * input bytes per call, or a weight set above 2 GiB: MI355_ERR_UNSUPPORTED.
+ *   _plan         frame_bytes, frames_per_unit (Ti; 1 for VOLTAGE), out_bytes_per_unit; no device; any output pointer may be NULL
+ *   _create       everything that can be told without a device is checked before ctx is touched
+ *   _set_weights  replaces all weights;  _set_beam_weights: those of one beam, w_beam = [f][p][s] {re, im}
+ *   _get_weights  copies the 2 F npol B S weight bytes; cap_bytes is the size of `out`
+ *   _set_generic  on != 0: the generic route for every later call of the handle; 0: back
+ *   _route        valid until the next _set_generic / _destroy of the handle; "" for NULL
+ *   _work         host pointers, blocking (pieces of whole units staged through pinned buffers of the handle)
+ *   _work_dev     device pointers, enqueue only; nunits == 0 is a no-op
+ * ------------------------------------------------------------------------------------------------ */
+#define MI355_BEAMFORM_VOLTAGE 0
+#define MI355_BEAMFORM_POWER 1
+typedef struct mi355_beamform mi355_beamform;
+int mi355_beamform_plan(int mode, int npol, int num_inputs, int num_channels, int num_beams, int integration, int stokes_i,
+                        long long *frame_bytes, int *frames_per_unit, long long *out_bytes_per_unit);
+int mi355_beamform_create(mi355_ctx *ctx, int mode, int npol, int num_inputs, int num_channels, int num_beams, int integration,
+                          int stokes_i, const void *weights, mi355_beamform **out);
+int mi355_beamform_destroy(mi355_beamform *h);
+int mi355_beamform_set_weights(mi355_beamform *h, const void *weights);
+int mi355_beamform_set_beam_weights(mi355_beamform *h, int beam, const void *w_beam);
+int mi355_beamform_get_weights(const mi355_beamform *h, void *out, long long cap_bytes);
+int mi355_beamform_num_beams(const mi355_beamform *h);
+long long mi355_beamform_frame_bytes(const mi355_beamform *h);
+long long mi355_beamform_out_bytes_per_unit(const mi355_beamform *h);
+int mi355_beamform_set_generic(mi355_beamform *h, int on);
+const char *mi355_beamform_route(const mi355_beamform *h);
+int mi355_beamform_work(mi355_beamform *h, long long nunits, const void *in, void *out);
+int mi355_beamform_work_dev(mi355_beamform *h, long long nunits, const void *in, void *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
