@@ -235,6 +235,19 @@ def lib():
         "mi355_beamform_route": (C.c_char_p, [vp]),
         "mi355_beamform_work": (i, [vp, ll, vp, vp]),
         "mi355_beamform_work_dev": (i, [vp, ll, vp, vp, vp]),
+        "mi355_fengine_plan": (i, [i, i, i, i, i, ll, llp, llp, llp]),
+        "mi355_fengine_create": (i, [vp, i, i, i, i, vp, i, vp, pp]),
+        "mi355_fengine_destroy": (i, [vp]),
+        "mi355_fengine_set_gains": (i, [vp, vp]),
+        "mi355_fengine_set_input_gain": (i, [vp, i, vp]),
+        "mi355_fengine_get_gains": (i, [vp, vp, ll]),
+        "mi355_fengine_get_clips": (i, [vp, vp, i]),
+        "mi355_fengine_set_generic": (i, [vp, i]),
+        "mi355_fengine_route": (C.c_char_p, [vp]),
+        "mi355_fengine_frame_bytes": (ll, [vp]),
+        "mi355_fengine_history_items": (ll, [vp]),
+        "mi355_fengine_work": (i, [vp, ll, pp, vp]),
+        "mi355_fengine_work_dev": (i, [vp, ll, pp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)  # AttributeError here = header/library mismatch: fail loudly

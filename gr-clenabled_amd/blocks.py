@@ -1404,3 +1404,104 @@ class clBeamformer(_Block):
                                               _dp(output_items[0], n * self._out_bytes, "output"), _torch_stream(self.device)),
               "mi355_beamform_work_dev")
         return n
+
+
+class clFEngine(_Block):
+    """F-engine in front of clXEngine / clBeamformer (beyond the reference module; the contract is in include/mi355_clenabled.h):
+    `num_inputs` stations of `polarization` complex64 streams each (input r = s * npol + p) go through a critically sampled polyphase
+    filter bank (`taps`: P * num_channels real prototype taps, None = all ones; P = 1 is a windowed FFT), a forward DFT, a real gain
+    per (input, channel) and symmetric int8 quantisation (round half to even, -127 .. 127, NaN -> 0) into the frames
+    [t][station][chan][pol]{I, Q}.  Every saturated or NaN component is counted per input (`clips()`).  Every input buffer is
+    history-prefixed: it starts at the first item of the first frame's window and holds (n + P - 1) * num_channels items."""
+    _destroy = "mi355_fengine_destroy"
+
+    def __init__(self, openCLPlatformType, devSelector, platformId, devId, polarization, num_inputs, num_channels, taps=None,
+                 taps_per_channel=1, shift=False, gains=None, setDebug=0):
+        self.npol, self.num_inputs, self.num_channels = int(polarization), int(num_inputs), int(num_channels)
+        self.taps_per_channel, self.shift = int(taps_per_channel), 1 if shift else 0
+        L = lib()
+        fb, hi = C.c_longlong(), C.c_longlong()
+        # argument errors before a context exists
+        check(L.mi355_fengine_plan(self.num_inputs, self.npol, self.num_channels, self.taps_per_channel, self.shift, 0, C.byref(fb),
+                                   C.byref(hi), None), "mi355_fengine_plan")
+        self._frame_bytes, self._history = fb.value, hi.value
+        self._nin = self.num_inputs * self.npol
+        t = None
+        if taps is not None:
+            t = np.ascontiguousarray(taps, np.float32)
+            if t.size != self.taps_per_channel * self.num_channels:
+                raise ValueError("taps hold %d values, the geometry needs %d" % (t.size, self.taps_per_channel * self.num_channels))
+        g = None if gains is None else self._gains(gains, self._nin * self.num_channels)
+        super().__init__(openCLPlatformType, devSelector, platformId, devId, setDebug)
+        check(self._L.mi355_fengine_create(self._ctx, self.num_inputs, self.npol, self.num_channels, self.taps_per_channel,
+                                           None if t is None else _hp(t), self.shift, None if g is None else _hp(g), C.byref(self._h)),
+              "mi355_fengine_create")
+
+    @staticmethod
+    def _gains(g, n):
+        a = np.ascontiguousarray(g, np.float32)
+        if a.size != n:
+            raise ValueError("gains hold %d values, the geometry needs %d" % (a.size, n))
+        return a
+
+    def frame_bytes(self):
+        return self._frame_bytes
+
+    def history_items(self):
+        """items in front of a call's first new frame: (P - 1) * num_channels (the GR block's history() is this plus one)"""
+        return self._history
+
+    def items_per_input(self, nframes):
+        return 0 if nframes == 0 else int(nframes) * self.num_channels + self._history
+
+    def route(self):
+        return self._L.mi355_fengine_route(self._h).decode()
+
+    def set_generic(self, on):
+        check(self._L.mi355_fengine_set_generic(self._h, 1 if on else 0), "mi355_fengine_set_generic")
+
+    def set_gains(self, gains):
+        check(self._L.mi355_fengine_set_gains(self._h, _hp(self._gains(gains, self._nin * self.num_channels))), "mi355_fengine_set_gains")
+
+    def set_input_gain(self, r, gain):
+        check(self._L.mi355_fengine_set_input_gain(self._h, int(r), _hp(self._gains(gain, self.num_channels))), "mi355_fengine_set_input_gain")
+
+    def gains(self):
+        out = np.empty((self._nin, self.num_channels), np.float32)
+        check(self._L.mi355_fengine_get_gains(self._h, _hp(out), out.size), "mi355_fengine_get_gains")
+        return out
+
+    def clips(self, reset=False):
+        """saturated or NaN components per input so far (waits for the device)"""
+        out = np.zeros(self._nin, np.uint64)
+        check(self._L.mi355_fengine_get_clips(self._h, _hp(out), 1 if reset else 0), "mi355_fengine_get_clips")
+        return out
+
+    def work(self, nframes, input_items, output_items):
+        """host buffers: one history-prefixed complex64 array per input, output_items[0] int8 / uint8 frames"""
+        n = int(nframes)
+        if n == 0:
+            return 0
+        if len(input_items) != self._nin:
+            raise ValueError("clFEngine work(): %d inputs, %d buffers" % (self._nin, len(input_items)))
+        xs = [_host(x, np.complex64) for x in input_items]
+        for x in xs:
+            if x.size < self.items_per_input(n):
+                raise ValueError("clFEngine work(): need %d input items (history included), got %d" % (self.items_per_input(n), x.size))
+        y = _host(output_items[0], writable=True)
+        if y.nbytes < n * self._frame_bytes:
+            raise ValueError("clFEngine work(): output holds %d bytes, the call needs %d" % (y.nbytes, n * self._frame_bytes))
+        ptrs = (C.c_void_p * self._nin)(*[x.ctypes.data for x in xs])
+        check(self._L.mi355_fengine_work(self._h, n, ptrs, _hp(y)), "mi355_fengine_work")
+        return n
+
+    def work_device(self, nframes, input_items, output_items):
+        n = int(nframes)
+        if n == 0:
+            return 0
+        if len(input_items) != self._nin:
+            raise ValueError("clFEngine work_device(): %d inputs, %d buffers" % (self._nin, len(input_items)))
+        ptrs = (C.c_void_p * self._nin)(*[_dp(x, self.items_per_input(n) * 8, "input").value for x in input_items])
+        check(self._L.mi355_fengine_work_dev(self._h, n, ptrs, _dp(output_items[0], n * self._frame_bytes, "output"),
+                                             _torch_stream(self.device)), "mi355_fengine_work_dev")
+        return n

@@ -877,11 +877,61 @@ static int beamform_test(size_t n)
     return g_fail ? 1 : 0;
 }
 
+// --fengine-only: clFEngine at (S, npol, F, P) = (3, 2, 64, 2) with shift, 70 frames, on streams from the 32-bit linear congruential
+// generator of --beamform-only (the top byte of each state as int8: re then im of every item, input after input), taps
+// h[i] = (1 + i % 5) / 4 and all gains 1 / 512.  Prints a "checksum" line that tests/test_fengine_gpu.py compares with the float64
+// reference: sum_i (i % 7 + 1) out_i over the output bytes in memory order; then one timing row.
+static int fengine_test(size_t n)
+{
+    const int S = 3, npol = 2, F = 64, P = 2, T = 70, R = S * npol;
+    const size_t items = (size_t)(T + P - 1) * F;
+    uint32_t state = 12345u;
+    auto next = [&]() { state = state * 1664525u + 1013904223u; return (float)(int8_t)(state >> 24); };
+    std::vector<std::vector<gr_complex>> x(R, std::vector<gr_complex>(items));
+    for (auto &v : x)
+        for (auto &c : v) { const float re = next(); const float im = next(); c = gr_complex(re, im); }
+    std::vector<float> h((size_t)P * F), g((size_t)R * F, 1.0f / 512.0f);
+    for (size_t i = 0; i < h.size(); i++) h[i] = (float)(1 + i % 5) * 0.25f;
+    {
+        auto fe = clFEngine::make(OCLTYPE_GPU, OCLDEVICESELECTOR_SPECIFIC, 0, g_dev, npol, S, F, h, P, true, g);
+        bool ok = fe->frame_bytes() == 2ll * S * F * npol && (int)fe->decimation() == F && (int)fe->history() == (P - 1) * F + 1 &&
+                  fe->route().compare(0, 5, "fused") == 0 && fe->gains() == g;
+        std::vector<int8_t> y((size_t)T * fe->frame_bytes(), -128);
+        gr_vector_const_void_star in;
+        for (auto &v : x) in.push_back(v.data());
+        gr_vector_void_star out = {y.data()};
+        auto t0 = std::chrono::steady_clock::now();
+        ok = ok && fe->work(T, in, out) == T;
+        std::chrono::duration<double> dt = std::chrono::steady_clock::now() - t0;
+        long long sum = 0;
+        for (size_t i = 0; i < y.size(); i++) {
+            ok = ok && y[i] != -128;
+            sum += (long long)(i % 7 + 1) * (long long)y[i];
+        }
+        printf("clFEngine checksum %lld\n", sum);
+        report("clFEngine (3 stations, 2 pol, 64 channels, 2 taps per channel)", (size_t)T, dt.count(), ok);
+    }
+    {
+        const int St = 16, Ft = 1024, Pt = 4, nt = (int)std::max<size_t>(n / 1024, 16), Rt = St * 2;
+        std::vector<gr_complex> xt((size_t)(nt + Pt - 1) * Ft, gr_complex(1.f, -1.f));
+        std::vector<float> ht((size_t)Pt * Ft, 0.25f), gt((size_t)Rt * Ft, 2.0f / Ft);
+        auto fe = clFEngine::make(OCLTYPE_GPU, OCLDEVICESELECTOR_SPECIFIC, 0, g_dev, 2, St, Ft, ht, Pt, false, gt);
+        std::vector<int8_t> y((size_t)nt * fe->frame_bytes(), -128);
+        gr_vector_const_void_star in(Rt, xt.data());
+        gr_vector_void_star out = {y.data()};
+        int got = 0;
+        const double t = time_calls([&] { got = fe->work(nt, in, out); });
+        // a constant 1 - j through four arms of 1/4 and a gain of 2 / F: channel 0 holds (2, -2), every other channel 0
+        report("clFEngine (16 x 2 x 1024, 4 taps per channel, timing)", (size_t)nt, t, got == nt && y[0] == 2 && y[1] == -2 && y[4] == 0 && y.back() == 0);
+    }
+    return g_fail ? 1 : 0;
+}
+
 int main(int argc, char **argv)
 {
     size_t n = 8192;  // the reference's default block size
     int fft_size = 4096, ntaps = 65;
-    bool only_fft = false, only_xcorrelate = false, xc_complex = false, only_loops = false, only_resampler = false, only_synth = false, only_pspec = false, only_xlate = false, only_beamform = false;
+    bool only_fft = false, only_xcorrelate = false, xc_complex = false, only_loops = false, only_resampler = false, only_synth = false, only_pspec = false, only_xlate = false, only_beamform = false, only_fengine = false;
     int xc_inputs = 2, xc_maxsearch = 512;
     for (int i = 1; i < argc; i++) {
         if (!strncmp(argv[i], "--device=", 9)) g_dev = atoi(argv[i] + 9);
@@ -897,6 +947,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--pspec-only")) only_pspec = true;
         else if (!strcmp(argv[i], "--xlate-only")) only_xlate = true;
         else if (!strcmp(argv[i], "--beamform-only")) only_beamform = true;
+        else if (!strcmp(argv[i], "--fengine-only")) only_fengine = true;
         else if (!strncmp(argv[i], "--num_inputs=", 13)) xc_inputs = atoi(argv[i] + 13);
         else if (!strncmp(argv[i], "--maxsearch=", 12)) xc_maxsearch = atoi(argv[i] + 12);
         else if (!strcmp(argv[i], "--input_complex")) xc_complex = true;
@@ -920,8 +971,9 @@ int main(int argc, char **argv)
                    "       %s --synth-only [--iterations N] [block size]\n"
                    "       %s --pspec-only [--iterations N] [block size]\n"
                    "       %s --xlate-only [--iterations N] [block size]\n"
-                   "       %s --beamform-only [--iterations N] [block size]\n",
-                   argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
+                   "       %s --beamform-only [--iterations N] [block size]\n"
+                   "       %s --fengine-only [--iterations N] [block size]\n",
+                   argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
             return 0;
         } else n = strtoull(argv[i], nullptr, 10);
     }
@@ -947,6 +999,10 @@ int main(int argc, char **argv)
     }
     if (only_beamform) {
         try { return beamform_test(n); }
+        catch (const std::exception &e) { std::cerr << "error: " << e.what() << std::endl; return 2; }
+    }
+    if (only_fengine) {
+        try { return fengine_test(n); }
         catch (const std::exception &e) { std::cerr << "error: " << e.what() << std::endl; return 2; }
     }
     if (only_xcorrelate) {

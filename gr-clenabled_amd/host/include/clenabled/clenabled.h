@@ -180,5 +180,27 @@ public:
     virtual std::string route() const = 0;
 };
 
+// gr::clenabled::clFEngine -- the F-engine in front of clXEngine and clBeamformer: num_inputs stations of `polarization` complex streams
+// (input r = s npol + p) through a critically sampled polyphase filter bank (taps: taps_per_channel * num_channels real prototype taps,
+// empty = all ones), a forward DFT, a real gain per (input, channel) and symmetric int8 quantisation into the frames
+// [t][station][chan][pol]{I, Q}.  Beyond the reference module; the contract is in mi355_clenabled.h.  A sync_decimator over R = S npol
+// gr_complex inputs with decimation num_channels and history (taps_per_channel - 1) num_channels + 1; its one output item is a frame of
+// frame_bytes() = 2 S num_channels npol bytes, the item clBeamformer takes in.  gains: R num_channels floats, [r][f]; empty = all 1.
+// (No per-block header of this name is installed by this build yet.)
+class CLENABLED_API clFEngine : virtual public gr::sync_decimator {
+public:
+    typedef std::shared_ptr<clFEngine> sptr;
+    static sptr make(int openCLPlatformType, int devSelector, int platformId, int devId, int polarization, int num_inputs, int num_channels,
+                     const std::vector<float> &taps = std::vector<float>(), int taps_per_channel = 1, bool shift = false,
+                     const std::vector<float> &gains = std::vector<float>(), int setDebug = 0);
+    virtual void set_gains(const std::vector<float> &gains) = 0;                  // R num_channels floats, anything else throws
+    virtual void set_input_gain(int input, const std::vector<float> &gain) = 0;   // num_channels floats
+    virtual std::vector<float> gains() const = 0;
+    virtual std::vector<uint64_t> clips(bool reset = false) = 0;                  // saturated or NaN components per input (waits for the device)
+    virtual long long frame_bytes() const = 0;
+    virtual void set_generic(bool on) = 0;  // the generic route for every later call
+    virtual std::string route() const = 0;
+};
+
 }  // namespace clenabled
 }  // namespace gr

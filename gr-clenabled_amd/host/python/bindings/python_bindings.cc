@@ -415,4 +415,39 @@ PYBIND11_MODULE(clenabled_python, m)
         .def("route", &clBeamformer::route)
         .def("decimation", [](clBeamformer &b) { return b.decimation(); })
         .def("work", &call_work<clBeamformer>, py::arg("noutput_items"), py::arg("input_items"), py::arg("output_items"));
+
+    // F-engine (lib/clFEngine_impl.cc): R complex64 input streams with (P - 1) F items of history in front, output items are int8 frames;
+    // taps and gains go in and out as float32 arrays
+    using f32array = py::array_t<float, py::array::c_style | py::array::forcecast>;
+    py::class_<clFEngine DECIM_BASES, std::shared_ptr<clFEngine>>(m, "clFEngine")
+        .def(py::init([](int openCLPlatformType, int devSelector, int platformId, int devId, int polarization, int num_inputs, int num_channels,
+                         const f32array &taps, int taps_per_channel, bool shift, const f32array &gains, int setDebug) {
+                 return clFEngine::make(openCLPlatformType, devSelector, platformId, devId, polarization, num_inputs, num_channels,
+                                        std::vector<float>(taps.data(), taps.data() + taps.size()), taps_per_channel, shift,
+                                        std::vector<float>(gains.data(), gains.data() + gains.size()), setDebug);
+             }),
+             py::arg("openCLPlatformType"), py::arg("devSelector"), py::arg("platformId"), py::arg("devId"), py::arg("polarization"),
+             py::arg("num_inputs"), py::arg("num_channels"), py::arg("taps") = f32array(0), py::arg("taps_per_channel") = 1,
+             py::arg("shift") = false, py::arg("gains") = f32array(0), py::arg("setDebug") = 0)
+        .def("set_gains", [](clFEngine &b, const f32array &g) { b.set_gains(std::vector<float>(g.data(), g.data() + g.size())); }, py::arg("gains"))
+        .def("set_input_gain",
+             [](clFEngine &b, int input, const f32array &g) { b.set_input_gain(input, std::vector<float>(g.data(), g.data() + g.size())); },
+             py::arg("input"), py::arg("gain"))
+        .def("gains",
+             [](clFEngine &b) {
+                 const std::vector<float> g = b.gains();
+                 return f32array(g.size(), g.data());
+             })
+        .def("clips",
+             [](clFEngine &b, bool reset) {
+                 const std::vector<uint64_t> c = b.clips(reset);
+                 return py::array_t<uint64_t>(c.size(), c.data());
+             },
+             py::arg("reset") = false)
+        .def("frame_bytes", &clFEngine::frame_bytes)
+        .def("set_generic", &clFEngine::set_generic, py::arg("on"))
+        .def("route", &clFEngine::route)
+        .def("decimation", [](clFEngine &b) { return b.decimation(); })
+        .def("history", [](clFEngine &b) { return b.history(); })
+        .def("work", &call_work<clFEngine>, py::arg("noutput_items"), py::arg("input_items"), py::arg("output_items"));
 }

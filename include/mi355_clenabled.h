@@ -746,6 +746,67 @@ const char *mi355_beamform_route(const mi355_beamform *h);
 int mi355_beamform_work(mi355_beamform *h, long long nunits, const void *in, void *out);
 int mi355_beamform_work_dev(mi355_beamform *h, long long nunits, const void *in, void *out, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * F-engine: clFEngine, polyphase filter bank + forward DFT + gain + int8 quantisation of R = S npol complex64 streams into the int8
+ * frames that clXEngine (BYTE) and clBeamformer consume.  Beyond the reference module, which has no F-engine (this comment is the
+ * contract).
+ *     S = num_inputs (stations) 1 .. 4096;  npol = 1 or 2;  F = num_channels, any length mi355_fft_create takes (>= 2);
+ *     P = taps_per_channel 1 .. 1024;  shift = 0 or 1 (1 needs an even F).
+ * Input r = s npol + p is a complex64 stream.  taps: P F real float32 prototype taps h (NULL at _create: all ones); P = 1 is a
+ * windowed FFT.  For frame t of input r:
+ *     z[n] = sum_{p < P} h[p F + n] x_r[(t + p) F + n]                    n = 0 .. F-1
+ *     X[f] = sum_n z[n] exp(-j 2 pi f n / F)
+ *     v    = gain[r][f] X[f]                                              real float32 gain, [r][f]; NULL at _create: all 1
+ *     q    = clamp(rint(v.re), -127, 127), clamp(rint(v.im), -127, 127)   rint = round half to even
+ *     out[t][s][f'][p] = int8 {q.re, q.im},   f' = shift ? (f + F / 2) mod F : f       (f ^ (F / 2) when F is a power of two)
+ * This is the critically sampled analysis bank of radio astronomy -- hop F, window P F, the taps applied in the order of the stream --
+ * NOT the GNU Radio arm convention of clPolyphaseChannelizer (whose arms run against the stream and whose outputs are per-channel
+ * streams).  Saturation is symmetric: -128 is never produced.  A NaN component becomes 0.  Every component that saturated or was NaN
+ * adds one to the clip counter of its input r (uint64, integer atomics): the totals are exact and do not depend on how a stream is
+ * split into calls.
+ * Calling convention: in_with_history[r] points at the first item of the first frame's window; a call for n frames reads
+ * (n + P - 1) F items per input and nothing beyond, and writes n frames of frame_bytes = 2 S F npol bytes.  The caller advances every
+ * pointer by n F items between calls.  Any split of a stream into calls at frame boundaries and any legal alignment (inputs 8-byte,
+ * out 2-byte) give the same bits within a route.
+ * Routes, decided at _create and named by _route(): "fused pow2 F=1024 P=4 npol=2 group=4" -- F = 16 .. 4096 a power of two and
+ * P <= 16: one kernel, the arms, the register transform of clFFT, gain, round, clamp and pack, whole rows out[t][s][.][.] stored 16
+ * bytes at a time; "generic F=1000 P=4 npol=2 batch=32x65" -- every other F, P > 16 and every handle under _set_generic(h, 1): a
+ * weighted-overlap-add kernel, an internal clFFT handle on a bounded workspace, a quantise-and-pack kernel.  The route is forced by
+ * _set_generic only; there is no environment switch.  The two routes order their float32 sums differently: an output whose exact value
+ * lies within the rounding error of a half-integer (or of +-127.5) may differ by one between them.
+ * Gain updates: a call enqueued before _set_gains / _set_input_gain returns uses the old gains entirely, a later call the new ones
+ * entirely (versioned device buffers; an old version is released behind the event of its last launch, when the next update or
+ * _destroy finds it complete; nothing on the work path waits for the device).
+ * Errors (nothing launched): NULL pointers, an input not 8-byte aligned, `out` not 2-byte aligned, an input overlapping `out`, a
+ * parameter outside the ranges above, shift with an odd F, `input` out of range: MI355_ERR_INVALID_ARG.  An F that mi355_fft_create
+ * would refuse, a gain or tap table above 1 GiB, more than 2^40 bytes per buffer and call: MI355_ERR_UNSUPPORTED.
+ *   _plan            frame_bytes, history_items = (P - 1) F, items_per_input = nframes F + history (0 for no frames); no device; any
+ *                    output pointer may be NULL
+ *   _create          everything that can be told without a device is checked before ctx is touched
+ *   _set_gains       replaces all gains, [r][f];  _set_input_gain: the F gains of one input;  _get_gains copies the R F floats
+ *   _get_clips       waits for the device, copies the R counters to out; reset != 0 zeroes them afterwards
+ *   _set_generic     on != 0: the generic route for every later call of the handle; 0: back
+ *   _route           valid until the next _set_generic / _destroy of the handle; "" for NULL
+ *   _work            host pointers, blocking (pieces of whole frames staged through buffers of the handle)
+ *   _work_dev        device pointers (the pointer array itself lives on the host), enqueue only; nframes == 0 is a no-op
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct mi355_fengine mi355_fengine;
+int mi355_fengine_plan(int num_inputs, int npol, int num_channels, int taps_per_channel, int shift, long long nframes,
+                       long long *frame_bytes, long long *history_items, long long *items_per_input);
+int mi355_fengine_create(mi355_ctx *ctx, int num_inputs, int npol, int num_channels, int taps_per_channel, const float *taps, int shift,
+                         const float *gains, mi355_fengine **out);
+int mi355_fengine_destroy(mi355_fengine *h);
+int mi355_fengine_set_gains(mi355_fengine *h, const float *gains);
+int mi355_fengine_set_input_gain(mi355_fengine *h, int input, const float *gain);
+int mi355_fengine_get_gains(const mi355_fengine *h, float *out, long long cap_floats);
+int mi355_fengine_get_clips(mi355_fengine *h, unsigned long long *out, int reset);
+int mi355_fengine_set_generic(mi355_fengine *h, int on);
+const char *mi355_fengine_route(const mi355_fengine *h);
+long long mi355_fengine_frame_bytes(const mi355_fengine *h);
+long long mi355_fengine_history_items(const mi355_fengine *h);
+int mi355_fengine_work(mi355_fengine *h, long long nframes, const void *const *in_with_history, void *out);
+int mi355_fengine_work_dev(mi355_fengine *h, long long nframes, const void *const *in_with_history, void *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
