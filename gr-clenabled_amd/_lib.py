@@ -94,6 +94,7 @@ def lib():
         "mi355_filter_fftsize": (i, [vp]),
         "mi355_filter_work": (i, [vp, sz, vp, vp]),
         "mi355_filter_work_dev": (i, [vp, sz, vp, vp, vp]),
+        "mi355_filter_last_route": (C.c_char_p, [vp]),
         "mi355_pfb_create": (i, [vp, vp, i, i, i, i, vp, i, pp]),
         "mi355_pfb_destroy": (i, [vp]),
         "mi355_pfb_noutput": (i, [vp]),
@@ -101,6 +102,7 @@ def lib():
         "mi355_pfb_work": (i, [vp, vp, vp]),
         "mi355_pfb_work_dev": (i, [vp, vp, vp, vp]),
         "mi355_pfb_work_dev_n": (i, [vp, i, vp, vp, vp]),
+        "mi355_pfb_last_route": (C.c_char_p, [vp]),
         "mi355_xengine_create": (i, [vp, i, i, i, i, i, pp]),
         "mi355_xengine_destroy": (i, [vp]),
         "mi355_xengine_input_bytes": (sz, [vp]),

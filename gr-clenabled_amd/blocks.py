@@ -265,6 +265,10 @@ class _FilterBase(_Block):
                                             _torch_stream(self.device)), "mi355_filter_work_dev")
         return noutput_items
 
+    def last_route(self):
+        """The kernel the last work() / work_device() launched and its parameters (mi355_filter_last_route); "" before the first call."""
+        return self._L.mi355_filter_last_route(self._h).decode()
+
 
 class clFilter(_FilterBase):
     """clFilter::make(openclPlatform, devSelector, platformId, devId, decimation, taps,
@@ -338,6 +342,10 @@ class clPolyphaseChannelizer(_Block):
         check(self._L.mi355_pfb_work_dev_n(self._h, nbuf, _dp(x, nin, "input"), _dp(y, nout, "output"), _torch_stream(self.device)),
               "mi355_pfb_work_dev_n")
         return nbuf * self.noutput()
+
+    def last_route(self):
+        """The kernels the last call launched (mi355_pfb_last_route); "" before the first call."""
+        return self._L.mi355_pfb_last_route(self._h).decode()
 
 
 class clXEngine(_Block):

@@ -412,7 +412,8 @@ __global__ __launch_bounds__(512) void k_pfb_mr(const MrArgs a, const PfbMr f)
         if (arm && o + (f.K - 1 - j) >= 0 && r < f.nsteps && !(a.dbg & 4)) x = __builtin_nontemporal_load(xp + o);
         return x;
     };
-    for (int i = tid0; i < a.ntw; i += blockDim.x) mr_lds[a.tw_lds + i] = a.tw[i];  // (the first barrier of the loop is in front of their first use)
+    for (int i = tid0; i < a.ntw; i += blockDim.x) mr_lds[a.tw_lds + i] = a.tw[i];
+    __syncthreads();  // taps and twiddles are staged by thread id and read by arm: in place before the first iteration's filters
     f2v x[PMAX - 1 + FS], nx[FS];
 #pragma unroll
     for (int u = 0; u < PMAX - 1 + FS; u++) x[u] = ld(s0 - (PMAX - 1) + u);  // the warm-up rows and the first FS rows

@@ -797,7 +797,7 @@ __global__ __launch_bounds__(kDlThreads) void k_fir_dec_lds(const c32 *__restric
 }
 
 
-// Round 6: the same staging for EVEN decimations with everything 16 bytes wide.  k_fir_dec_lds spends its time in the staging loop (8-byte loads, one
+// Round 6: the same staging with everything 16 bytes wide (written for EVEN decimations; ODD ones below).  k_fir_dec_lds spends its time in the staging loop (8-byte loads, one
 // LDS slot computed and written per sample: ~ 3.7 ps per input sample, "reads every sample once" at a third of the read bandwidth) and in a tap loop that
 // mixes scalar tap loads with the LDS reads on one counter.  Here a thread stages sample PAIRS (global_load_dwordx4, all of a thread's loads in
 // flight before the first LDS write), pair p sits at 16-byte unit p (+ p / 32 where D is a multiple of 8: dec2_pad_shift; an output's window starts on a
@@ -830,7 +830,7 @@ __global__ __launch_bounds__(kD2Threads) void k_fir_dec2(const c32 *__restrict__
     for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const long long o0 = tile * tile_out, left = n_out - o0;
         const int no = left < tile_out ? (int)left : tile_out;
-        const long long s0 = o0 * decim;  // even
+        const long long s0 = o0 * decim;  // even: an even decimation, or an even tile_out (the launcher sends an odd decimation with one output per tile elsewhere)
         const v4f_ *__restrict__ src = (const v4f_ *)(in + s0);
         const int pairs = ((no - 1) * decim + KP + 1) / 2 + (ODD ? 1 : 0);
         const long long avail = n_in - s0;  // valid samples from s0 on
@@ -954,11 +954,17 @@ struct mi355_filter {
     int ups = 0;           // number of those segments (0: not applicable)
     std::vector<void *> retired;   // tables of earlier taps, kept alive for kernels still in flight (see retire_dev)
     size_t retired_bytes = 0, table_bytes = 0;
+    // what the last work / work_dev launched (mi355_filter_last_route): a kind and two ints, formatted when asked for
+    int rt_kind = 0, rt_a = 0, rt_b = 0;
+    char rt_text[64] = "";
     HostPipe pipe;
     std::mutex lock;
 };
 
 namespace {
+
+enum { kRtNone = 0, kRtOls, kRtOlsUps, kRtOlsPart, kRtTd, kRtMfma, kRtDec2, kRtDecLds, kRtTdDec };
+inline void set_route(mi355_filter *h, int kind, int a = 0, int b = 0) { h->rt_kind = kind; h->rt_a = a; h->rt_b = b; }
 
 constexpr int kOlsMaxTaps = 2048;  // longest filter one NF = 4096 block can overlap with at least half of it new samples
 constexpr int kUpsMaxSeg = 5;      // k_ols_ups keeps the spectra of the previous segments' input blocks in registers: up to 10240 taps
@@ -1170,6 +1176,7 @@ int launch_ols_g(mi355_filter *h, size_t nout, const void *in, void *out, hipStr
     if constexpr (NF == 4096) {
         const bool ups_on = !getenv("MI355_OLS_UPS") || atoi(getenv("MI355_OLS_UPS")) != 0;
         if (h->ups > 1 && ups_on) {
+            set_route(h, kRtOlsUps, h->ups);
             const long long nblocks = (n_y + 2047) / 2048;
             if (nblocks > 0x7fffffffLL) { mi355_set_error("work() call too large"); return MI355_ERR_INVALID_ARG; }
             // a run of consecutive blocks per workgroup (the P - 1 warm-up transforms of a run are the overhead): two
@@ -1193,6 +1200,7 @@ int launch_ols_g(mi355_filter *h, size_t nout, const void *in, void *out, hipStr
         }
         if (h->nseg > 1 && !one_pass) MI355_SWITCH_NOTE(h->ctx, "MI355_OLS_PART_ONE_PASS", "k_ols, one accumulating pass per segment, instead of k_ols_part");
         if (h->nseg > 1 && one_pass) {
+            set_route(h, kRtOlsPart, NF, h->nseg);
             const int s0 = (h->seg_len - 1 + 15) & ~15;
             const int L = (NF - s0) & ~15;
             const long long nblocks = (n_y + L - 1) / L, ngroups = (nblocks + F - 1) / F;
@@ -1208,6 +1216,7 @@ int launch_ols_g(mi355_filter *h, size_t nout, const void *in, void *out, hipStr
         }
     }
     if (!align_stores) MI355_SWITCH_NOTE(h->ctx, "MI355_OLS_ALIGN", "k_ols blocks that start storing at ntaps - 1");
+    set_route(h, kRtOls, NF, h->nseg);
     for (int sgm = 0; sgm < h->nseg; sgm++) {
         // segment sgm of a partitioned filter (nseg == 1: the whole filter): its taps, and where its input starts --
         // in_p[i] = in[i + (segments after this one) * seg_len], see upload_taps
@@ -1283,7 +1292,7 @@ int launch_filter(mi355_filter *h, size_t nout, const void *in, void *out, hipSt
     double r_lds = h->decim / ((h->complex_taps ? 0.00022 : 0.00017) * h->ntaps + 0.0037 * h->decim);
     if (r_all > (h->complex_taps ? 210.0 : 300.0)) r_all = h->complex_taps ? 210.0 : 300.0;
     if (r_lds > 250.0) r_lds = 250.0;
-    // even decimations of a 16-byte aligned input: the 16-byte-wide form k_fir_dec2 (round 6), time per output ~ 0.10 K + 1.5 D ps (65 taps 304 / 603 /
+    // a 16-byte aligned input (even decimations, and odd ones whose tiles hold an even number of outputs): the 16-byte-wide form k_fir_dec2 (round 6), time per output ~ 0.10 K + 1.5 D ps (65 taps 304 / 603 /
     // 637 / 653 GS/s of input at D = 10 / 16 / 32 / 64, 200 taps 404 / 467 / 505 at D = 16 / 32 / 64, 400 taps 242 / 331 / 363)
     const bool dec2_ok = (reinterpret_cast<uintptr_t>(in) & 15u) == 0 && h->ntaps <= 1024 && !getenv("MI355_FIR_DEC2_OFF") &&
                          (h->decim % 2 == 0 || !getenv("MI355_FIR_DEC2_EVEN_ONLY"));
@@ -1328,6 +1337,7 @@ int launch_filter(mi355_filter *h, size_t nout, const void *in, void *out, hipSt
     const bool per_output = above && r_po >= (mf_ok ? r_all : 0.0) && r_po >= (lds_ok ? r_lds : 0.0) && !(h->ntaps < 16 && h->decim <= 64);
     const bool all_outputs_above_8 = h->decim > dmax && h->decim >= dl_min && r_all >= r_lds && !per_output;
     if (mf_on && h->mf_kk && ((h->decim == 1 && h->ntaps >= 16) || (h->decim >= 2 && h->decim <= dmax && h->ntaps >= 96 && !early) || (all_outputs_above_8 && h->ntaps >= 16))) {  // fewer taps: the vector kernel's short loop wins (9 taps: 350 vs 330 GS/s)
+        set_route(h, kRtMfma, h->decim == 1 ? 0 : 1);
         const int span = kMfTile + 4 * h->mf_kk;
         const int nq = (span + kMfThreads - 1) / kMfThreads;
         const size_t smem = ((size_t)2 * (mf_pad(nq * kMfThreads + 16) + 1) + (size_t)(h->complex_taps ? 2 : 1) * (4 * h->mf_kk + 24)) * sizeof(float);
@@ -1350,9 +1360,23 @@ int launch_filter(mi355_filter *h, size_t nout, const void *in, void *out, hipSt
         return MI355_OK;
     }
     const int kpad0 = (h->ntaps + kTdU - 1) / kTdU * kTdU;
+    // k_fir_dec2's tile: samples staged per tile 3072 (26 KiB: five or six workgroups per CU) up to 128 taps, 4096 above -- measured at 65 taps, D = 16: spans of
+    // 2048 / 3072 / 4096 / 6144 / 8192 samples 489 / 603 / 550 / 464 / 377 GS/s of input; 400 taps 194 / 223 / 242 / 168 / 194 -- and whole rounds of
+    // 256 outputs where a tile holds more than one (390 outputs per tile at D = 10 ran the second round of threads half empty)
+    const int KP = (h->ntaps + 7) / 8 * 8;
+    static const int span_env = getenv("MI355_FIR_DEC2_SPAN") ? atoi(getenv("MI355_FIR_DEC2_SPAN")) : 0;
+    const int span_max = span_env > 0 ? span_env : (h->ntaps <= 128 ? 3072 : 4096);
+    int d2_tile_out = span_max > KP ? (span_max - KP) / h->decim + 1 : 1;
+    if (d2_tile_out > 2048) d2_tile_out = 2048;
+    if (d2_tile_out > kD2Threads) d2_tile_out = d2_tile_out / kD2Threads * kD2Threads;
+    if (h->decim % 2 && d2_tile_out > 1) d2_tile_out &= ~1;  // (odd decimations: tiles start on a sample pair)
+    // an odd decimation whose tile holds a single output would start every other tile on the second sample of a pair, 8 bytes off the 16-byte
+    // loads of the staging loop: such a shape goes to k_fir_dec_lds below
+    const bool dec2_pairs = h->decim % 2 == 0 || d2_tile_out >= 2;
     // the register-tiled kernel computes every undecimated output: worth it up to a decimation of 8
     if (h->decim == 1 || (((h->decim <= dmax && !early) || (h->ntaps < 16 && h->decim <= 64 && h->decim >= dl_min)) && (size_t)td_rows(kpad0) * kTdU * sizeof(c32) <= 160 * 1024)) {  // (fewer than 16 taps: this kernel runs at 400 GS/s of input whatever the decimation)
         const int kpad = kpad0;
+        set_route(h, kRtTd);
         const size_t smem = (size_t)td_rows(kpad) * kTdU * sizeof(c32);
         if (smem > 160 * 1024) { mi355_set_error("time-domain mode supports up to ~18000 taps"); return MI355_ERR_UNSUPPORTED; }
         const long long n_y = (long long)nout * h->decim;  // undecimated outputs
@@ -1372,20 +1396,13 @@ int launch_filter(mi355_filter *h, size_t nout, const void *in, void *out, hipSt
         if (h->complex_taps) LAUNCH_TD(true);
         else LAUNCH_TD(false);
 #undef LAUNCH_TD
-    } else if (lds_ok && !per_output && dec2_ok) {
-        // even decimations, 16-byte aligned input: the 16-byte-wide form of the LDS-staged kernel
-        const int KP = (h->ntaps + 7) / 8 * 8;
+    } else if (lds_ok && !per_output && dec2_ok && dec2_pairs) {
+        // 16-byte aligned input, tiles that start on a sample pair (any even decimation; an odd one with an even number of outputs per tile): the
+        // 16-byte-wide form of the LDS-staged kernel
         const int tap_units = (h->complex_taps ? 2 : 1) * KP / 4;
-        static const int span_env = getenv("MI355_FIR_DEC2_SPAN") ? atoi(getenv("MI355_FIR_DEC2_SPAN")) : 0;
-        // samples staged per tile: 3072 (26 KiB: five or six workgroups per CU) up to 128 taps, 4096 above -- measured at 65 taps, D = 16: spans of
-        // 2048 / 3072 / 4096 / 6144 / 8192 samples 489 / 603 / 550 / 464 / 377 GS/s of input; 400 taps 194 / 223 / 242 / 168 / 194 -- and whole rounds of
-        // 256 outputs where a tile holds more than one (390 outputs per tile at D = 10 ran the second round of threads half empty)
         if (span_env > 0) MI355_SWITCH_NOTE(h->ctx, "MI355_FIR_DEC2_SPAN", "k_fir_dec2 with a forced tile span");
-        const int span_max = span_env > 0 ? span_env : (h->ntaps <= 128 ? 3072 : 4096);
-        int tile_out = span_max > KP ? (span_max - KP) / h->decim + 1 : 1;
-        if (tile_out > 2048) tile_out = 2048;
-        if (tile_out > kD2Threads) tile_out = tile_out / kD2Threads * kD2Threads;
-        if (h->decim % 2 && tile_out > 1) tile_out &= ~1;  // (odd decimations: tiles start on a sample pair)
+        const int tile_out = d2_tile_out;
+        set_route(h, kRtDec2, h->decim % 2, tile_out);
         const int pairs = ((tile_out - 1) * h->decim + KP + 1) / 2 + 1;
         const int sh = getenv("MI355_FIR_DEC2_PAD") ? atoi(getenv("MI355_FIR_DEC2_PAD")) : dec2_pad_shift(h->decim);
         const size_t smem = (size_t)(tap_units + d2_unit(pairs, sh) + 2) * 16;
@@ -1406,6 +1423,7 @@ int launch_filter(mi355_filter *h, size_t nout, const void *in, void *out, hipSt
         // (a decimation far above the filter length skips most of the input: the per-output kernel reads only what it needs)
         int tile_out = (kDlSpan - h->ntaps) / h->decim + 1;
         if (tile_out > 2048) tile_out = 2048;
+        set_route(h, kRtDecLds, 0, tile_out);
         const size_t smem = (size_t)(dl_slot(kDlSpan) + 1) * sizeof(c32);
         const long long ntiles = ((long long)nout + tile_out - 1) / tile_out;
         const long long grid = ntiles < (long long)cus * 8 ? ntiles : (long long)cus * 8;
@@ -1419,6 +1437,7 @@ int launch_filter(mi355_filter *h, size_t nout, const void *in, void *out, hipSt
         else LAUNCH_DL(false);
 #undef LAUNCH_DL
     } else {
+        set_route(h, kRtTdDec);
         long long blocks = ((long long)nout + 255) / 256;
         long long grid = blocks < (long long)cus * 8 ? blocks : (long long)cus * 8;
         if (h->complex_taps)
@@ -1473,6 +1492,27 @@ extern "C" int mi355_filter_set_taps(mi355_filter *h, const void *taps, int ntap
 extern "C" int mi355_filter_ntaps(const mi355_filter *h) { return h ? h->ntaps : MI355_ERR_INVALID_ARG; }
 
 extern "C" int mi355_filter_fftsize(const mi355_filter *h) { return h ? h->nf : MI355_ERR_INVALID_ARG; }
+
+extern "C" const char *mi355_filter_last_route(mi355_filter *h)
+{
+    if (!h) return "";
+    std::lock_guard<std::mutex> g(h->lock);
+    const char *ct = h->complex_taps ? "complex" : "real";
+    char *t = h->rt_text;
+    const size_t n = sizeof(h->rt_text);
+    switch (h->rt_kind) {
+    case kRtOls: snprintf(t, n, h->rt_b > 1 ? "k_ols<%d> x %d segments" : "k_ols<%d>", h->rt_a, h->rt_b); break;
+    case kRtOlsUps: snprintf(t, n, "k_ols_ups<%d>", h->rt_a); break;
+    case kRtOlsPart: snprintf(t, n, "k_ols_part<%d> %d segments", h->rt_a, h->rt_b); break;
+    case kRtTd: snprintf(t, n, "k_fir_td<%s>", ct); break;
+    case kRtMfma: snprintf(t, n, "k_fir_mfma<%s,%s>", ct, h->rt_a ? "dec" : "all"); break;
+    case kRtDec2: snprintf(t, n, "k_fir_dec2<%s,%s> tile_out=%d", ct, h->rt_a ? "odd" : "even", h->rt_b); break;
+    case kRtDecLds: snprintf(t, n, "k_fir_dec_lds<%s> tile_out=%d", ct, h->rt_b); break;
+    case kRtTdDec: snprintf(t, n, "k_fir_td_dec<%s>", ct); break;
+    default: t[0] = 0; break;
+    }
+    return t;
+}
 
 extern "C" int mi355_filter_get_taps(const mi355_filter *h, void *taps_out, int cap)
 {

@@ -837,10 +837,17 @@ struct mi355_pfb {
     mi355_fft *dft = nullptr;
     void *d_filt2 = nullptr;      // the transforms' output when a channel map follows
     bool whole_map = false;       // ch_map = 0 .. M-1: the transform writes the output itself
+    // what the last call launched (mi355_pfb_last_route): a kind and three ints, formatted when asked for
+    int rt_kind = 0, rt_a = 0, rt_b = 0, rt_second = 0;
+    char rt_text[80] = "";
     HostPipe pipe;
 };
 
 namespace {
+
+enum { kRtNone = 0, kRtQ, kRtW, kRtWOver, kRtS, kRtStaged, kRtMr, kRtFir, kRtBranchesT, kRtBranches };
+enum { kRt2None = 0, kRt2Fft, kRt2FftMap, kRt2DftMap, kRt2Map };
+inline void set_route(mi355_pfb *h, int kind, int a = 0, int b = 0, int second = kRt2None) { h->rt_kind = kind; h->rt_a = a; h->rt_b = b; h->rt_second = second; }
 
 template <int M, int PMAX>
 int launch_wave(mi355_pfb *h, const void *in, void *out, hipStream_t st, int nsteps, long long buf_items)
@@ -851,6 +858,7 @@ int launch_wave(mi355_pfb *h, const void *in, void *out, hipStream_t st, int nst
     const int small_on = getenv("MI355_PFB_SMALL") ? atoi(getenv("MI355_PFB_SMALL")) : 1;  // (read per call: a tuning / test switch)
     if constexpr (!(M == 256 && PMAX > 16) && M <= 256) {  // (1024 threads x 32 taps per arm would spill: that shape keeps the ring kernel; 512 channels too)
         if (small_on && ngroups <= 2 * cus) {
+            set_route(h, kRtQ, M, PMAX);
             const long long n_in = (long long)buf_items - h->R + h->K;
             if (h->ident)
                 hipLaunchKernelGGL((k_pfbq<M, PMAX, true>), dim3(ngroups), dim3(4 * M), 0, st, (const c32 *)in, (c32 *)out, h->d_taps,
@@ -870,6 +878,7 @@ int launch_wave(mi355_pfb *h, const void *in, void *out, hipStream_t st, int nst
     const int per = (int)((ngroups + wgs - 1) / wgs);
     const int grid = (ngroups + per - 1) / per;
     const long long n_in = (long long)buf_items - h->R + h->K;
+    set_route(h, kRtW, M, PMAX);
     if (h->ident)
         hipLaunchKernelGGL((k_pfbw<M, PMAX, true>), dim3(grid), dim3(M), 0, st, (const c32 *)in, (c32 *)out, h->d_taps, (const c32 *)h->d_tw,
                            h->d_map, h->nmap, h->K, n_in, nsteps, per, 0);
@@ -888,6 +897,7 @@ int launch_wave_over(mi355_pfb *h, const void *in, void *out, hipStream_t st, in
     const long long n_in = (long long)nsteps * h->R - h->R + h->K;
     // (512 channels: one 8-wave workgroup per CU and a single round: 8 -> 133 us, 16 -> 142, 32 -> 157 per 2^25 items)
     const int wpc = getenv("MI355_PFB_WAVES_PER_CU") ? atoi(getenv("MI355_PFB_WAVES_PER_CU")) : (M >= 512 ? 8 : 16);
+    set_route(h, kRtWOver, M, PMAX, S);
     for (int par = 0; par < S; par++) {
         const int nsub = (nsteps - par + S - 1) / S;
         if (nsub <= 0) continue;
@@ -925,6 +935,7 @@ int launch_streams(mi355_pfb *h, const void *in, void *out, hipStream_t st, int 
     const int nstreams = (ngroups + gps - 1) / gps;
     const int grid = (nstreams + SEG - 1) / SEG;
     const long long n_in = (long long)buf_items - h->R + h->K;
+    set_route(h, kRtS, M, PMAX);
     if (h->ident)
         hipLaunchKernelGGL((k_pfbs<M, PMAX, true>), dim3(grid), dim3(64), 0, st, (const c32 *)in, (c32 *)out, h->d_taps, (const c32 *)h->d_tw,
                            h->d_map, h->nmap, h->K, n_in, nsteps, gps);
@@ -970,6 +981,7 @@ int launch_fast(mi355_pfb *h, const void *in, void *out, hipStream_t st, int nst
     // many short grid-stride workgroups (measured at 8 and 16 channels: 2 per CU 250 GS/s, 8 per CU 280, 32 per CU 302)
     int grid = mi355_balanced_grid(h->ctx, ngroups, 16, 32);
     long long n_in = (long long)buf_items - h->R + h->K;
+    set_route(h, kRtStaged, M, PMAX);
     if (h->ident)
         hipLaunchKernelGGL((k_pfb<M, PMAX, true>), dim3(grid), dim3(256), 0, st, (const c32 *)in, (c32 *)out, h->d_taps,
                            (const c32 *)h->d_tw, h->d_map, h->nmap, h->K, n_in, nsteps, ngroups);
@@ -1030,6 +1042,8 @@ int launch_pfb(mi355_pfb *h, const void *in, void *out, hipStream_t st, int nste
         if (mp && mi355_fft_mr_pfb_ok(*mp, sign, h->K, h->M, nsteps)) {
             const int rc = mi355_fft_mr_pfb_launch(*mp, h->ctx, in, h->whole_map ? out : h->d_filt2, h->d_taps, h->K, h->M, nsteps, st);
             if (rc) return rc;
+            const int P_mr = (h->K + h->M - 1) / h->M;
+            set_route(h, kRtMr, P_mr <= 8 ? 8 : P_mr <= 16 ? 16 : 32, 0, h->whole_map ? kRt2None : kRt2Map);
             if (!h->whole_map) {
                 const long long tot = (long long)nsteps * h->nmap, blocks = (tot + 255) / 256;
                 const long long cu8 = (long long)(h->ctx->num_cus > 0 ? h->ctx->num_cus : 256) * 8;
@@ -1046,6 +1060,7 @@ int launch_pfb(mi355_pfb *h, const void *in, void *out, hipStream_t st, int nste
     long long grid = blocks < (long long)cus * 8 ? blocks : (long long)cus * 8;
     const int over = h->R > 0 && h->M % h->R == 0 ? h->M / h->R : 0;  // 1: critically sampled; 2, 4: oversampled by that factor
     const int P_arm = (h->K + h->M - 1) / h->M;
+    const int second = h->dft ? (h->whole_map ? kRt2Fft : kRt2FftMap) : kRt2DftMap;
     if (over == 1 && (P_arm <= 8 || (P_arm > 16 && P_arm <= 32)) && !getenv("MI355_PFB_BRANCHES_PER_OUTPUT") && !getenv("MI355_PFB_NO_FIR_RING")) {  // (64 taps per arm: 309 + 53 registers, slower than k_pfb_branches_t; 9 ... 16: no faster)
         FirRing f;
         f.in = (const c32 *)in;
@@ -1071,8 +1086,10 @@ int launch_pfb(mi355_pfb *h, const void *in, void *out, hipStream_t st, int nste
         const long long nrb = (nsteps + len * f.Q - 1) / (len * f.Q);  // range blocks
         const dim3 gd((unsigned)(nrb * f.arm_blocks));
         const size_t lds = (size_t)pm * f.A * 4;
+        set_route(h, kRtFir, pm, 0, second);
         if (pm == 8) hipLaunchKernelGGL((k_pfb_fir<8>), gd, dim3(256), lds, st, f);
         else hipLaunchKernelGGL((k_pfb_fir<32>), gd, dim3(256), lds, st, f);
+        MI355_HIP(hipGetLastError());
     } else
     if ((over == 1 || over == 2 || over == 4) && !getenv("MI355_PFB_BRANCHES_PER_OUTPUT")) {
         constexpr int T = 8;
@@ -1081,15 +1098,18 @@ int launch_pfb(mi355_pfb *h, const void *in, void *out, hipStream_t st, int nste
         const dim3 gd((unsigned)(g2 < 8 ? 8 : g2));
         static const int xr = getenv("MI355_PFB_NO_XCD_RUNS") ? 0 : 1;
         if (!xr) MI355_SWITCH_NOTE(h->ctx, "MI355_PFB_NO_XCD_RUNS", "k_pfb_branches_t with its workgroups in plain order");
+        set_route(h, kRtBranchesT, over == 1 ? 16 : over == 2 ? 8 : 4, over, second);
         if (over == 1)
             hipLaunchKernelGGL((k_pfb_branches_t<T, 16, 1>), gd, dim3(256), 0, st, (const c32 *)in, (c32 *)h->d_filt, h->d_taps, h->K, h->M, nsteps, tt, xr);
         else if (over == 2)
             hipLaunchKernelGGL((k_pfb_branches_t<T, 8, 2>), gd, dim3(256), 0, st, (const c32 *)in, (c32 *)h->d_filt, h->d_taps, h->K, h->M, nsteps, tt, xr);
         else
             hipLaunchKernelGGL((k_pfb_branches_t<T, 4, 4>), gd, dim3(256), 0, st, (const c32 *)in, (c32 *)h->d_filt, h->d_taps, h->K, h->M, nsteps, tt, xr);
-    } else
-    hipLaunchKernelGGL(k_pfb_branches, dim3((unsigned)grid), dim3(256), 0, st, (const c32 *)in, (c32 *)h->d_filt, h->d_taps, h->K,
-                       h->M, h->R, total);
+    } else {
+        set_route(h, kRtBranches, 0, 0, second);
+        hipLaunchKernelGGL(k_pfb_branches, dim3((unsigned)grid), dim3(256), 0, st, (const c32 *)in, (c32 *)h->d_filt, h->d_taps, h->K,
+                           h->M, h->R, total);
+    }
     total = (long long)nsteps * h->nmap;
     blocks = (total + 255) / 256;
     grid = blocks < (long long)cus * 8 ? blocks : (long long)cus * 8;
@@ -1209,6 +1229,31 @@ extern "C" int mi355_pfb_create(mi355_ctx *ctx, const float *taps, int ntaps, in
               num_channels, ntaps, ninputs_per_iter, nmap, num_channels, buf_items, h->fast ? "fused filter + transform" : "two-pass");
     *out = h;
     return MI355_OK;
+}
+
+extern "C" const char *mi355_pfb_last_route(mi355_pfb *h)
+{
+    if (!h) return "";
+    char *t = h->rt_text;
+    const size_t n = sizeof(h->rt_text);
+    int len = 0;
+    switch (h->rt_kind) {
+    case kRtQ: len = snprintf(t, n, "k_pfbq<%d,%d>", h->rt_a, h->rt_b); break;
+    case kRtW: len = snprintf(t, n, "k_pfbw<%d,%d>", h->rt_a, h->rt_b); break;
+    case kRtWOver: len = snprintf(t, n, "k_pfbw<%d,%d,over=%d>", h->rt_a, h->rt_b, h->rt_second); break;
+    case kRtS: len = snprintf(t, n, "k_pfbs<%d,%d>", h->rt_a, h->rt_b); break;
+    case kRtStaged: len = snprintf(t, n, "k_pfb<%d,%d>", h->rt_a, h->rt_b); break;
+    case kRtMr: len = snprintf(t, n, "k_pfb_mr<%d>", h->rt_a); break;
+    case kRtFir: len = snprintf(t, n, "k_pfb_fir<%d>", h->rt_a); break;
+    case kRtBranchesT: len = snprintf(t, n, "k_pfb_branches_t<8,%d,%d>", h->rt_a, h->rt_b); break;
+    case kRtBranches: len = snprintf(t, n, "k_pfb_branches"); break;
+    default: t[0] = 0; return t;
+    }
+    if (h->rt_kind != kRtWOver && len > 0 && (size_t)len < n) {
+        static const char *const second[] = {"", " + clFFT", " + clFFT + k_pfb_map", " + k_pfb_dft_map", " + k_pfb_map"};
+        snprintf(t + len, n - len, "%s", second[h->rt_second]);
+    }
+    return t;
 }
 
 extern "C" int mi355_pfb_noutput(const mi355_pfb *h) { return h ? h->nmap * h->nsteps : MI355_ERR_INVALID_ARG; }

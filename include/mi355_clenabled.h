@@ -203,6 +203,17 @@ int mi355_filter_get_taps(const mi355_filter *h, void *taps_out, int cap);
 int mi355_filter_fftsize(const mi355_filter *h);
 int mi355_filter_work(mi355_filter *h, size_t noutput_items, const void *in_with_history, void *out);
 int mi355_filter_work_dev(mi355_filter *h, size_t noutput_items, const void *in_with_history, void *out, void *stream);
+/* The kernel the last work / work_dev of this handle launched and the parameters that matter, e.g. "k_fir_td<real>", "k_fir_mfma<complex,dec>",
+ * "k_fir_dec2<real,odd> tile_out=166", "k_fir_dec_lds<real> tile_out=32", "k_fir_td_dec<real>", "k_ols<256>"; "" before the first call.  Valid
+ * until the handle's next call. */
+const char *mi355_filter_last_route(mi355_filter *h);
+/* Which input items an output depends on (direct form, use_time = 1).  Output m reads items [m D, m D + K) of the history-prefixed input
+ * (D = decimation, K = ntaps).  A non-finite item s makes every output whose window holds s non-finite.  The kernels pad the taps with
+ * zeros that multiply neighbouring samples (0 x NaN = NaN), so s may also make non-finite outputs with m D - PAD <= s < m D + K + PAD and
+ * no others: every other output has the bits of the same call without it.  PAD = 18 items, the largest over the kernels: k_fir_mfma
+ * multiplies blocks of 16 undecimated outputs by K + 15 samples rounded up to a multiple of four (15 items before a window, 18 behind);
+ * k_fir_td and k_fir_dec2 round K up to a multiple of 8 (7 items behind); k_fir_dec_lds and k_fir_td_dec read the window alone.
+ * The fast-convolution mode (use_time = 0) spreads a non-finite item over every output of the transform blocks that hold it. */
 
 /* ---------------------------------------------------------------------------
  * clPolyphaseChannelizer: M-branch polyphase filterbank + M-point backward DFT
@@ -223,6 +234,20 @@ int mi355_pfb_work_dev(mi355_pfb *h, const void *in_with_history, void *out, voi
 /* nbuf consecutive buffers in one launch (general_work() offered nbuf output multiples): in holds
  * nbuf * buf_items - ninputs_per_iter + ntaps samples, out nbuf * noutput().  Same samples as nbuf single calls. */
 int mi355_pfb_work_dev_n(mi355_pfb *h, int nbuf, const void *in_dev, void *out_dev, void *stream);
+/* The kernels the last call of this handle launched, e.g. "k_pfbw<64,32>", "k_pfbq<256,8>", "k_pfbs<32,8>", "k_pfb<8,16>" (staged),
+ * "k_pfbw<64,8,over=2>", "k_pfb_mr<16>", "k_pfb_fir<32> + clFFT", "k_pfb_branches_t<8,16,1> + clFFT + k_pfb_map",
+ * "k_pfb_branches + k_pfb_dft_map"; "" before the first call.  Valid until the handle's next call. */
+const char *mi355_pfb_last_route(mi355_pfb *h);
+/* Which input items a step depends on.  Step i (R = ninputs_per_iter, M = num_channels, K = ntaps) reads items [i R, i R + K) of the
+ * history-prefixed input, item s with tap k = i R + K - 1 - s; every mapped channel of a step depends on all of them (the M-point DFT).
+ * A non-finite item s makes every mapped channel of the steps ceil((s - K + 1) / R) ... floor(s / R) non-finite.  For R = M, with s in
+ * input row r = ceil((s - K + 1) / M) and P the taps of its arm, these are the steps r ... r + P - 1.  The kernels round the taps per arm
+ * up with zeros (0 x NaN = NaN), so s may also reach the steps up to floor((s - K + PMAXR M) / R) -- for R = M the steps up to
+ * r + PMAXR - 1, for R < M as many more steps as fit PMAXR rows of M items -- never a step before the first one named and never a later
+ * one; every other step has the bits of the same call without it.  PMAXR = 32 steps for up to 32 taps per arm, the largest over the
+ * kernels: the fused kernels (k_pfbs, k_pfbq, k_pfbw, k_pfb, k_pfb_mr) round the taps per arm up to 8, 16 or 32, k_pfb_fir to 8 or 32,
+ * k_pfb_branches_t to a multiple of 16 (8 and 4 when 2- and 4-fold oversampled), k_pfb_branches reads the window alone.  Longer arms: the
+ * fused power-of-two kernels round 33 ... 64 taps per arm up to 64, k_pfb_branches_t rounds up to its multiple (at most 15 more). */
 
 /* ---------------------------------------------------------------------------
  * clXEngine: V[f][k][pol2] = sum_t x_s1(t,f) conj(x_s2(t,f)), k = s1(s1+1)/2+s2.

@@ -348,6 +348,32 @@ fir_case("fir_dec2_off_pad", [(65, 16, False, 40013)], {"MI355_FIR_DEC_KERNEL": 
 fir_case("fir_dec2_off", [(65, 16, False, 40013)], {"MI355_FIR_DEC_KERNEL": "lds", "MI355_FIR_DEC2_OFF": "1"}, taken=None, switches=["MI355_FIR_DEC2_OFF"])
 
 
+def fir_window_case(name, shapes, route, group, switches):
+    """every component of every output within the per-output bound of tests/fir_ref.py (error / bound against 1.0), on the kernel `route`
+    names: evidence is last_route() of every shape.  shapes: (ntaps, decim, complex taps); two tiles of the kernel and a ragged third."""
+    def fn(pkg, oracle):
+        import fir_ref
+        import torch
+        checks, routes = [], []
+        for K, D, ct in shapes:
+            n = fir_ref.nout(route.split("<")[0], K, D)
+            h, x = fir_ref.make_taps(K, ct), fir_ref.make_input(K, D, n)
+            blk = (pkg.clComplexFilter if ct else pkg.clFilter)(*GPU_ARGS, D, h, 1, 1, True)
+            y = torch.full((n,), float("nan"), dtype=torch.complex64, device="cuda")
+            blk.work_device(n, [torch.from_numpy(x).cuda()], [y])
+            torch.cuda.synchronize()
+            routes.append(blk.last_route())
+            checks.append(("%s %d taps decim %d x %d, error / bound per output" % (routes[-1], K, D, n),
+                           fir_ref.worst(y.cpu().numpy(), fir_ref.fir(h, x, D, n), fir_ref.bound(h, x, D, n)), 1.0))
+            blk.stop()
+        return result(all(r == route for r in routes), " | ".join(routes), checks)
+    return add(name, fn, None, group, switches)
+
+
+# k_fir_td with 16 taps and more runs only with the matrix-core kernel switched off (read once per process)
+fir_window_case("fir_td_window_mfma_off", [(K, D, False) for K in (16, 65, 129) for D in (1, 2)], "k_fir_td<real>", "filter_mfma", ["MI355_FIR_MFMA"])
+
+
 # ------------------------------------------------------------------------------------------------------------------ channelizer
 
 def run_pfb(pkg, oracle, M, R, per_arm, steps, nmap=None):
@@ -407,6 +433,36 @@ pfb_case("pfb_branches_per_output", [(1024, 1024, 32, 45), (128, 32, 32, 134)], 
 pfb_case("pfb_no_fast_oversampled", [(64, 32, 8, 203), (128, 32, 32, 134)], {"MI355_PFB_NO_FAST_OVERSAMPLED": "1"}, kernel="two-pass kernel")
 pfb_case("pfb_no_mr_fused", [(100, 100, 32, 70)], {"MI355_PFB_NO_MR_FUSED": "1"}, taken=None)
 pfb_case("pfb_direct_dft", [(100, 30, 5, 83), (1000, 1000, 7, 83)], {"MI355_PFB_DIRECT_DFT": "1"}, taken=None)
+
+
+def pfb_window_case(name, shapes, group, switches):
+    """the same for the channelizer and the per-step bound of tests/pfb_ref.py; shapes: (channels, inputs per step, taps per arm, steps,
+    the first kernel last_route() must name); identity map and one that repeats and omits channels"""
+    def fn(pkg, oracle):
+        import pfb_ref
+        import torch
+        checks, routes, tk = [], [], True
+        for M, R, P, steps, first in shapes:
+            h = pfb_ref.make_taps(M, P)
+            x = pfb_ref.make_input(h.size, R, steps)
+            for cm in pfb_ref.maps(M):
+                blk = pkg.clPolyphaseChannelizer(*GPU_ARGS, h, steps * R, M, R, cm, 1)
+                y = torch.full((blk.noutput(),), float("nan"), dtype=torch.complex64, device="cuda")
+                blk.work_device([torch.from_numpy(x).cuda()], [y])
+                torch.cuda.synchronize()
+                routes.append(blk.last_route())
+                tk = tk and routes[-1].split(" + ")[0] == first
+                want, bnd = pfb_ref.channelize(h, M, R, cm, x, steps)
+                checks.append(("%s %d / %d, %d taps per arm, %d mapped x %d steps, error / bound per step" % (routes[-1], M, R, P, len(cm), steps),
+                               pfb_ref.worst(y.cpu().numpy(), want, bnd, len(cm)), 1.0))
+                blk.stop()
+        return result(tk, " | ".join(routes), checks)
+    return add(name, fn, None, group, switches)
+
+
+# the staged kernel k_pfb<M, PMAX> at the channel counts the wave kernels take otherwise: 4096 / M steps per workgroup iteration, two and a ragged third
+pfb_window_case("pfb_staged_window", [(32, 32, 8, 2 * 128 + 37, "k_pfb<32,8>"), (64, 64, 32, 2 * 64 + 37, "k_pfb<64,32>"), (256, 256, 5, 2 * 16 + 37, "k_pfb<256,8>")],
+                "pfb", ["MI355_PFB_WAVE"])
 
 
 # ------------------------------------------------------------------------------------------------------- resampler, synthesizer
