@@ -250,6 +250,17 @@ def lib():
         "mi355_fengine_history_items": (ll, [vp]),
         "mi355_fengine_work": (i, [vp, ll, pp, vp]),
         "mi355_fengine_work_dev": (i, [vp, ll, pp, vp, vp]),
+        "mi355_dedisp_plan": (i, [i, i, i, i, i, llp, llp, llp]),
+        "mi355_dedisp_create": (i, [vp, i, i, i, i, i, vp, pp]),
+        "mi355_dedisp_destroy": (i, [vp]),
+        "mi355_dedisp_set_delays": (i, [vp, vp]),
+        "mi355_dedisp_get_delays": (i, [vp, vp, ll]),
+        "mi355_dedisp_history": (ll, [vp]),
+        "mi355_dedisp_set_generic": (i, [vp, i]),
+        "mi355_dedisp_route": (C.c_char_p, [vp]),
+        "mi355_dedisp_work": (i, [vp, ll, vp, vp, ll]),
+        "mi355_dedisp_work_dev": (i, [vp, ll, vp, vp, ll, vp]),
+        "mi355_dedisp_delays": (i, [d, d, i, d, vp, i, vp, C.POINTER(i)]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)  # AttributeError here = header/library mismatch: fail loudly

@@ -1513,3 +1513,117 @@ class clFEngine(_Block):
         check(self._L.mi355_fengine_work_dev(self._h, n, ptrs, _dp(output_items[0], n * self._frame_bytes, "output"),
                                              _torch_stream(self.device)), "mi355_fengine_work_dev")
         return n
+
+
+DEDISP_TRIAL_MAJOR, DEDISP_TIME_MAJOR = 0, 1
+
+
+def dedisp_delays(f0_mhz, df_mhz, num_channels, tsamp_s, dm):
+    """(delay[d][f] int32, max_delay): the cold-plasma delay table of mi355_dedisp_delays for a band of `num_channels` channels
+    nu_f = f0 + f df MHz against its highest frequency, dispersion measures `dm` in pc cm^-3 and a sampling time in seconds"""
+    dms = np.ascontiguousarray(dm, np.float64).reshape(-1)
+    out = np.empty((dms.size, int(num_channels)), np.int32)
+    top = C.c_int()
+    check(lib().mi355_dedisp_delays(float(f0_mhz), float(df_mhz), int(num_channels), float(tsamp_s), _hp(dms), dms.size, _hp(out), C.byref(top)),
+          "mi355_dedisp_delays")
+    return out, top.value
+
+
+class clDedisperser(_Block):
+    """Exact incoherent dedispersion behind clBeamformer's POWER output (beyond the reference module; the contract is in
+    include/mi355_clenabled.h): x[t][row][chan] float32 summed over the channels at per-(trial, channel) sample delays,
+    y(r, d, t) = sum_f x[t + delay[d][f]][r][f] in ascending channel order, one binary32 rounding per addition, -1 entries skipped.
+    `delays`: int32 [num_trials][num_channels], each 0 .. max_delay or -1, None for all zero.  A call for n outputs reads n + max_delay
+    samples.  Output TIME_MAJOR y[t][r][d], or TRIAL_MAJOR y[(r D + d) out_pitch + t].  Bit-exact on either route and for any split."""
+    _destroy = "mi355_dedisp_destroy"
+
+    def __init__(self, openCLPlatformType, devSelector, platformId, devId, num_rows, num_channels, num_trials, max_delay,
+                 order=DEDISP_TIME_MAJOR, delays=None, setDebug=0):
+        self.num_rows, self.num_channels, self.num_trials = int(num_rows), int(num_channels), int(num_trials)
+        self.max_delay, self.order = int(max_delay), int(order)
+        L = lib()
+        fi, hi, fo = C.c_longlong(), C.c_longlong(), C.c_longlong()
+        # argument errors before a context exists
+        check(L.mi355_dedisp_plan(self.num_rows, self.num_channels, self.num_trials, self.max_delay, self.order, C.byref(fi), C.byref(hi),
+                                  C.byref(fo)), "mi355_dedisp_plan")
+        self._in_floats, self._history, self._out_floats = fi.value, hi.value, fo.value
+        t = None if delays is None else self._table(delays)
+        super().__init__(openCLPlatformType, devSelector, platformId, devId, setDebug)
+        check(self._L.mi355_dedisp_create(self._ctx, self.num_rows, self.num_channels, self.num_trials, self.max_delay, self.order,
+                                          None if t is None else _hp(t), C.byref(self._h)), "mi355_dedisp_create")
+
+    def _table(self, delays):
+        a = np.ascontiguousarray(delays)
+        if a.dtype != np.int32:
+            raise TypeError("delays are int32")
+        if a.size != self.num_trials * self.num_channels:
+            raise ValueError("delays hold %d entries, the geometry needs %d" % (a.size, self.num_trials * self.num_channels))
+        return a
+
+    def in_floats_per_sample(self):
+        return self._in_floats
+
+    def out_floats_per_sample(self):
+        return self._out_floats
+
+    def history(self):
+        """samples of look-ahead behind a call's last output: max_delay (the GR block's history() is this plus one)"""
+        return self._history
+
+    def in_floats(self, n):
+        return 0 if n == 0 else (int(n) + self._history) * self._in_floats
+
+    def out_floats(self, n, out_pitch=None):
+        """floats from the first to one past the last a call for n outputs writes"""
+        if n == 0:
+            return 0
+        if self.order == DEDISP_TIME_MAJOR:
+            return int(n) * self._out_floats
+        return (self._out_floats - 1) * (int(n) if out_pitch is None else int(out_pitch)) + int(n)
+
+    def route(self):
+        return self._L.mi355_dedisp_route(self._h).decode()
+
+    def set_generic(self, on):
+        check(self._L.mi355_dedisp_set_generic(self._h, 1 if on else 0), "mi355_dedisp_set_generic")
+
+    def set_delays(self, delays):
+        check(self._L.mi355_dedisp_set_delays(self._h, _hp(self._table(delays))), "mi355_dedisp_set_delays")
+
+    def delays(self):
+        out = np.empty((self.num_trials, self.num_channels), np.int32)
+        check(self._L.mi355_dedisp_get_delays(self._h, _hp(out), out.size), "mi355_dedisp_get_delays")
+        return out
+
+    def _pitch(self, n, out_pitch):
+        if self.order == DEDISP_TIME_MAJOR:
+            return 0 if out_pitch is None else int(out_pitch)
+        return n if out_pitch is None else int(out_pitch)
+
+    def work(self, noutput_items, input_items, output_items, out_pitch=None):
+        """host buffers: input_items[0] float32 [n + max_delay][R][F], output_items[0] float32; out_pitch (TRIAL_MAJOR): floats between
+        the time series, default n"""
+        n = int(noutput_items)
+        if n == 0:
+            return 0
+        x = _host(input_items[0], np.float32)
+        _need("input", x, self.in_floats(n))
+        y = _host(output_items[0], np.float32, writable=True)
+        pitch = self._pitch(n, out_pitch)
+        if self.order == DEDISP_TRIAL_MAJOR and pitch >= n:
+            _need("output", y, self.out_floats(n, pitch))
+        elif self.order == DEDISP_TIME_MAJOR:
+            _need("output", y, self.out_floats(n))
+        check(self._L.mi355_dedisp_work(self._h, n, _hp(x), _hp(y), pitch), "mi355_dedisp_work")
+        return n
+
+    def work_device(self, noutput_items, input_items, output_items, out_pitch=None):
+        n = int(noutput_items)
+        if n == 0:
+            return 0
+        pitch = self._pitch(n, out_pitch)
+        need = self.out_floats(n, pitch) if (self.order == DEDISP_TRIAL_MAJOR and pitch >= n) else self.out_floats(n)
+        check(self._L.mi355_dedisp_work_dev(self._h, n, _dp(input_items[0], self.in_floats(n) * 4, "input"),
+                                            _dp(output_items[0], need * 4, "output"), pitch, _torch_stream(self.device)),
+              "mi355_dedisp_work_dev")
+        return n

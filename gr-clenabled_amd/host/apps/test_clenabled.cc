@@ -927,11 +927,61 @@ static int fengine_test(size_t n)
     return g_fail ? 1 : 0;
 }
 
+// --dedisp-only: clDedisperser at (R, F, D) = (2, 20, 5) with delay[d][f] = d (F - 1 - f) / 4 (max_delay 19) and channel 3 of trial 2
+// killed, 70 outputs, on samples from the 32-bit linear congruential generator of --beamform-only (the top byte of each state as int8,
+// as float: every sum is an exact integer).  Prints a "checksum" line that tests/test_dedisp_gpu.py compares with the numpy
+// reference: sum_i (i % 7 + 1) y_i over the output floats in memory order; then one timing row.
+static int dedisp_test(size_t n)
+{
+    const int R = 2, F = 20, D = 5, T = 70, H = (D - 1) * (F - 1) / 4;
+    uint32_t state = 12345u;
+    auto next = [&]() { state = state * 1664525u + 1013904223u; return (float)(int8_t)(state >> 24); };
+    std::vector<float> x((size_t)(T + H) * R * F);
+    for (auto &v : x) v = next();
+    std::vector<int32_t> tab((size_t)D * F);
+    for (int d = 0; d < D; d++)
+        for (int f = 0; f < F; f++) tab[(size_t)d * F + f] = d * (F - 1 - f) / 4;
+    tab[2 * F + 3] = -1;
+    {
+        auto dd = clDedisperser::make(OCLTYPE_GPU, OCLDEVICESELECTOR_SPECIFIC, 0, g_dev, R, F, D, H, tab);
+        bool ok = (int)dd->history() == H + 1 && dd->max_delay() == H && dd->route().compare(0, 5, "tiled") == 0 && dd->delays() == tab;
+        std::vector<float> y((size_t)T * R * D, -1e30f);
+        gr_vector_const_void_star in = {x.data()};
+        gr_vector_void_star out = {y.data()};
+        auto t0 = std::chrono::steady_clock::now();
+        ok = ok && dd->work(T, in, out) == T;
+        std::chrono::duration<double> dt = std::chrono::steady_clock::now() - t0;
+        long long sum = 0;
+        for (size_t i = 0; i < y.size(); i++) {
+            ok = ok && y[i] != -1e30f;
+            sum += (long long)(i % 7 + 1) * (long long)y[i];
+        }
+        printf("clDedisperser checksum %lld\n", sum);
+        report("clDedisperser (2 rows, 20 channels, 5 trials)", (size_t)T, dt.count(), ok);
+    }
+    {
+        const int Rt = 4, Ft = 256, Dt = 64, Ht = 63, nt = (int)std::max<size_t>(n / 8, 16);
+        std::vector<float> xt((size_t)(nt + Ht) * Rt * Ft, 0.5f);
+        std::vector<int32_t> tt((size_t)Dt * Ft);
+        for (int d = 0; d < Dt; d++)
+            for (int f = 0; f < Ft; f++) tt[(size_t)d * Ft + f] = d * (Ft - 1 - f) / (Ft - 1);
+        auto dd = clDedisperser::make(OCLTYPE_GPU, OCLDEVICESELECTOR_SPECIFIC, 0, g_dev, Rt, Ft, Dt, Ht, tt);
+        std::vector<float> y((size_t)nt * Rt * Dt, -1.0f);
+        gr_vector_const_void_star in = {xt.data()};
+        gr_vector_void_star out = {y.data()};
+        int got = 0;
+        const double t = time_calls([&] { got = dd->work(nt, in, out); });
+        // 256 channels of a constant 1/2: every output is 128
+        report("clDedisperser (4 x 256 x 64 trials, timing)", (size_t)nt, t, got == nt && y[0] == 128.0f && y[y.size() / 2] == 128.0f && y.back() == 128.0f);
+    }
+    return g_fail ? 1 : 0;
+}
+
 int main(int argc, char **argv)
 {
     size_t n = 8192;  // the reference's default block size
     int fft_size = 4096, ntaps = 65;
-    bool only_fft = false, only_xcorrelate = false, xc_complex = false, only_loops = false, only_resampler = false, only_synth = false, only_pspec = false, only_xlate = false, only_beamform = false, only_fengine = false;
+    bool only_fft = false, only_xcorrelate = false, xc_complex = false, only_loops = false, only_resampler = false, only_synth = false, only_pspec = false, only_xlate = false, only_beamform = false, only_fengine = false, only_dedisp = false;
     int xc_inputs = 2, xc_maxsearch = 512;
     for (int i = 1; i < argc; i++) {
         if (!strncmp(argv[i], "--device=", 9)) g_dev = atoi(argv[i] + 9);
@@ -948,6 +998,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--xlate-only")) only_xlate = true;
         else if (!strcmp(argv[i], "--beamform-only")) only_beamform = true;
         else if (!strcmp(argv[i], "--fengine-only")) only_fengine = true;
+        else if (!strcmp(argv[i], "--dedisp-only")) only_dedisp = true;
         else if (!strncmp(argv[i], "--num_inputs=", 13)) xc_inputs = atoi(argv[i] + 13);
         else if (!strncmp(argv[i], "--maxsearch=", 12)) xc_maxsearch = atoi(argv[i] + 12);
         else if (!strcmp(argv[i], "--input_complex")) xc_complex = true;
@@ -972,8 +1023,9 @@ int main(int argc, char **argv)
                    "       %s --pspec-only [--iterations N] [block size]\n"
                    "       %s --xlate-only [--iterations N] [block size]\n"
                    "       %s --beamform-only [--iterations N] [block size]\n"
-                   "       %s --fengine-only [--iterations N] [block size]\n",
-                   argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
+                   "       %s --fengine-only [--iterations N] [block size]\n"
+                   "       %s --dedisp-only [--iterations N] [block size]\n",
+                   argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
             return 0;
         } else n = strtoull(argv[i], nullptr, 10);
     }
@@ -1003,6 +1055,10 @@ int main(int argc, char **argv)
     }
     if (only_fengine) {
         try { return fengine_test(n); }
+        catch (const std::exception &e) { std::cerr << "error: " << e.what() << std::endl; return 2; }
+    }
+    if (only_dedisp) {
+        try { return dedisp_test(n); }
         catch (const std::exception &e) { std::cerr << "error: " << e.what() << std::endl; return 2; }
     }
     if (only_xcorrelate) {

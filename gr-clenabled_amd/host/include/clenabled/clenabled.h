@@ -202,5 +202,24 @@ public:
     virtual std::string route() const = 0;
 };
 
+// gr::clenabled::clDedisperser -- exact incoherent dedispersion behind clBeamformer's POWER output: num_rows x num_channels floats per time
+// sample summed over the channels at per-(trial, channel) sample delays, in ascending channel order with one binary32 rounding per
+// addition.  Beyond the reference module; the contract is in mi355_clenabled.h.  A sync_block: one input stream whose item is a time
+// sample of num_rows num_channels floats ([row][chan], the item clBeamformer writes in POWER mode with stokes_i or one polarisation),
+// one output stream whose item is num_rows num_trials floats ([row][trial], TIME_MAJOR), history max_delay + 1.  delays: int32
+// [trial][chan], each 0 .. max_delay or -1 (the channel takes no part in the trial); an empty vector at make() is all zero.
+// (No per-block header of this name is installed by this build yet.)
+class CLENABLED_API clDedisperser : virtual public gr::sync_block {
+public:
+    typedef std::shared_ptr<clDedisperser> sptr;
+    static sptr make(int openCLPlatformType, int devSelector, int platformId, int devId, int num_rows, int num_channels, int num_trials,
+                     int max_delay, const std::vector<int32_t> &delays = std::vector<int32_t>(), int setDebug = 0);
+    virtual void set_delays(const std::vector<int32_t> &delays) = 0;  // num_trials num_channels entries, anything else throws
+    virtual std::vector<int32_t> delays() const = 0;
+    virtual int max_delay() const = 0;
+    virtual void set_generic(bool on) = 0;  // the generic route for every later call
+    virtual std::string route() const = 0;  // may change with set_delays()
+};
+
 }  // namespace clenabled
 }  // namespace gr

@@ -450,4 +450,28 @@ PYBIND11_MODULE(clenabled_python, m)
         .def("decimation", [](clFEngine &b) { return b.decimation(); })
         .def("history", [](clFEngine &b) { return b.history(); })
         .def("work", &call_work<clFEngine>, py::arg("noutput_items"), py::arg("input_items"), py::arg("output_items"));
+
+    // dedisperser (lib/clDedisperser_impl.cc): input items are time samples of R F floats with max_delay samples of look-ahead behind the
+    // call's last output, output items R D floats; the delay table goes in and out as an int32 array
+    using i32array = py::array_t<int32_t, py::array::c_style | py::array::forcecast>;
+    py::class_<clDedisperser SYNC_BASES, std::shared_ptr<clDedisperser>>(m, "clDedisperser")
+        .def(py::init([](int openCLPlatformType, int devSelector, int platformId, int devId, int num_rows, int num_channels, int num_trials,
+                         int max_delay, const i32array &delays, int setDebug) {
+                 return clDedisperser::make(openCLPlatformType, devSelector, platformId, devId, num_rows, num_channels, num_trials, max_delay,
+                                            std::vector<int32_t>(delays.data(), delays.data() + delays.size()), setDebug);
+             }),
+             py::arg("openCLPlatformType"), py::arg("devSelector"), py::arg("platformId"), py::arg("devId"), py::arg("num_rows"),
+             py::arg("num_channels"), py::arg("num_trials"), py::arg("max_delay"), py::arg("delays") = i32array(0), py::arg("setDebug") = 0)
+        .def("set_delays", [](clDedisperser &b, const i32array &t) { b.set_delays(std::vector<int32_t>(t.data(), t.data() + t.size())); },
+             py::arg("delays"))
+        .def("delays",
+             [](clDedisperser &b) {
+                 const std::vector<int32_t> t = b.delays();
+                 return i32array(t.size(), t.data());
+             })
+        .def("max_delay", &clDedisperser::max_delay)
+        .def("set_generic", &clDedisperser::set_generic, py::arg("on"))
+        .def("route", &clDedisperser::route)
+        .def("history", [](clDedisperser &b) { return b.history(); })
+        .def("work", &call_work<clDedisperser>, py::arg("noutput_items"), py::arg("input_items"), py::arg("output_items"));
 }

@@ -832,6 +832,72 @@ long long mi355_fengine_history_items(const mi355_fengine *h);
 int mi355_fengine_work(mi355_fengine *h, long long nframes, const void *const *in_with_history, void *out);
 int mi355_fengine_work_dev(mi355_fengine *h, long long nframes, const void *const *in_with_history, void *out, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Dedisperser: clDedisperser, exact incoherent dedispersion of a filterbank over D dispersion-measure trials -- the first stage of a
+ * pulsar or fast-transient search behind clBeamformer's POWER output.  Beyond the reference module, which has no dedisperser (this
+ * comment is the contract).  The summation order is pinned, so there is no tolerance anywhere.
+ *     R = num_rows (beams) 1 .. 4096;  F = num_channels 1 .. 16384;  D = num_trials 1 .. 4096;  H = max_delay 0 .. 2^20, fixed for
+ *     the life of the handle (it is the block's history);  order = MI355_DEDISP_TRIAL_MAJOR (0) or MI355_DEDISP_TIME_MAJOR (1).
+ * Input: x[t][r][f] float32, channel fastest -- clBeamformer's POWER output with stokes_i = 1 or npol = 1 and B = R.  A call for n
+ * outputs reads the n + H time samples that start at `in` and nothing beyond; the caller advances `in` by n R F floats between calls.
+ * Delay table: delay[d][f] int32, D F entries, each in 0 .. H or -1.  -1 means "channel f takes no part in trial d" (a killed
+ * channel): nothing of that channel is added, a NaN there reaches nothing.  Any other value is MI355_ERR_INVALID_ARG.  delays == NULL
+ * at _create means all zero.
+ * Output, for output sample t of the call:
+ *     y(r, d, t) = (((+0.0f + x[t + delay[d][0]][r][0]) + x[t + delay[d][1]][r][1]) + ...)     skipping every f with delay[d][f] == -1
+ * IEEE binary32 additions, round to nearest even, one rounding per addition, in ascending channel order.  The result is a function of
+ * the inputs alone: either route, any split of a stream into calls, any legal alignment and any n give identical bits.  NaN and +-Inf
+ * propagate exactly where the formula puts them and nowhere else.  Results whose operands or partial sums are subnormal are
+ * unspecified.  (The fixed order rules out float atomics and any split of a channel sum across threads; the R D sums of a time sample
+ * are the parallelism.)
+ * Output layout: TRIAL_MAJOR y[(r D + d) out_pitch + t] with out_pitch >= n in floats; the floats between n and out_pitch are not
+ * touched, so a caller fills long per-trial time series over several calls.  TIME_MAJOR y[t][r][d], out_pitch must be 0.
+ * Routes, decided at _create and again at every _set_delays from the table, named by _route(): "tiled R=64 F=1024 D=1024 fb=8 dt=16
+ * tt=256" -- a workgroup owns (row, dt trials, tt outputs), walks the channels in blocks of fb, stages per block only the window
+ * [t0 + min delay, t0 + tt + max delay) of the (trial tile, channel block) in LDS transposed and keeps its accumulators in registers;
+ * taken when max - min <= 128 in every (trial tile, channel block), -1 entries not counted, and R F <= 2796202 (a window of less than
+ * 2^32 bytes).  "generic R=3 F=5 D=2" -- any other table
+ * and every handle under _set_generic(h, 1): one thread per output.  The route is forced by _set_generic only; there is no
+ * environment switch.  A _set_delays may change the route.
+ * Table updates: a call enqueued before _set_delays returns uses the old table entirely, a later call the new one entirely (versioned
+ * device buffers; an old version is released behind the event of its last launch, when the next update or _destroy finds it complete;
+ * nothing on the work path waits for the device).  A refused update changes nothing.
+ * Errors (nothing launched): NULL pointers, `in` or `out` not 4-byte aligned, `in` overlapping the extent of `out`, out_pitch < n
+ * (TRIAL_MAJOR) or != 0 (TIME_MAJOR), a parameter outside the ranges above, a table entry outside -1 .. H: MI355_ERR_INVALID_ARG.
+ * More than 2^40 bytes per buffer and call, or a table above 1 GiB: MI355_ERR_UNSUPPORTED.
+ *   _plan         in_floats_per_sample = R F, history = H, out_floats_per_sample = R D; no device; any output pointer may be NULL
+ *   _create       everything that can be told without a device is checked before ctx is touched
+ *   _set_delays   replaces the whole table (validated against H);  _get_delays copies the D F entries, cap_entries is the size of `out`
+ *   _history      H
+ *   _set_generic  on != 0: the generic route for every later call of the handle; 0: back
+ *   _route        valid until the next _set_generic / _set_delays / _destroy of the handle; "" for NULL
+ *   _work         host pointers, blocking (pieces of whole samples, each staged with its H samples of look-ahead)
+ *   _work_dev     device pointers, enqueue only; n == 0 is a no-op
+ * mi355_dedisp_delays (host only, no context): the cold-plasma delay table of a band of F channels nu_f = f0 + f df MHz (df may be
+ * negative) against the largest nu_f, for D dispersion measures in pc cm^-3 and a sampling time in seconds:
+ *     delay[d][f] = llrint(((4.148808e3 dm[d]) (1 / (nu_f nu_f) - 1 / (nu_ref nu_ref))) / tsamp_s)
+ * in double, every operation rounded on its own (never contracted), llrint in the default rounding mode (half to even).  *max_delay
+ * (may be NULL) receives the largest entry.  A non-positive or non-finite nu_f, tsamp_s <= 0, a negative or non-finite dm or a delay
+ * above 2^20: MI355_ERR_INVALID_ARG, and `out` is then unspecified.
+ * ------------------------------------------------------------------------------------------------ */
+#define MI355_DEDISP_TRIAL_MAJOR 0
+#define MI355_DEDISP_TIME_MAJOR 1
+typedef struct mi355_dedisp mi355_dedisp;
+int mi355_dedisp_plan(int num_rows, int num_channels, int num_trials, int max_delay, int order, long long *in_floats_per_sample,
+                      long long *history, long long *out_floats_per_sample);
+int mi355_dedisp_create(mi355_ctx *ctx, int num_rows, int num_channels, int num_trials, int max_delay, int order, const int32_t *delays,
+                        mi355_dedisp **out);
+int mi355_dedisp_destroy(mi355_dedisp *h);
+int mi355_dedisp_set_delays(mi355_dedisp *h, const int32_t *delays);
+int mi355_dedisp_get_delays(const mi355_dedisp *h, int32_t *out, long long cap_entries);
+long long mi355_dedisp_history(const mi355_dedisp *h);
+int mi355_dedisp_set_generic(mi355_dedisp *h, int on);
+const char *mi355_dedisp_route(const mi355_dedisp *h);
+int mi355_dedisp_work(mi355_dedisp *h, long long n, const void *in, void *out, long long out_pitch);
+int mi355_dedisp_work_dev(mi355_dedisp *h, long long n, const void *in, void *out, long long out_pitch, void *stream);
+int mi355_dedisp_delays(double f0_mhz, double df_mhz, int num_channels, double tsamp_s, const double *dm, int num_trials, int32_t *out,
+                        int *max_delay);
+
 #ifdef __cplusplus
 }
 #endif
