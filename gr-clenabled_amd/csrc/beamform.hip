@@ -265,12 +265,6 @@ int bf_check_weights(const signed char *w, size_t n)
     return MI355_OK;
 }
 
-struct BfVersion {
-    void *d = nullptr;          // [raw weights | folded operand table]
-    hipEvent_t ev = nullptr;    // recorded behind the last launch that reads this version
-    bool used = false;
-};
-
 }  // namespace
 
 struct mi355_beamform {
@@ -281,8 +275,7 @@ struct mi355_beamform {
     size_t raw_bytes = 0, raw_pad = 0, tab_bytes = 0;
     bool mfma = false, generic = false;
     std::vector<signed char> w;  // the caller's layout
-    BfVersion cur;
-    std::vector<BfVersion> retired;
+    mi355_tables tab;            // [raw weights | folded operand table]
     HostPipe pipe;
     std::string route;
     std::mutex lock;
@@ -297,25 +290,6 @@ void bf_name_route(mi355_beamform *h)
         snprintf(buf, sizeof buf, "mfma S=%d B=%d F=%d npol=%d kblocks=%d beam_tiles=%d", h->S, h->B, h->F, h->npol, h->KB, h->BTW);
     else snprintf(buf, sizeof buf, "generic S=%d B=%d F=%d npol=%d", h->S, h->B, h->F, h->npol);
     h->route = buf;
-}
-
-// frees the retired versions whose last launch has completed (all of them when `wait`); never called on the work path
-void bf_reap(mi355_beamform *h, bool wait)
-{
-    size_t keep = 0;
-    for (BfVersion &v : h->retired) {
-        bool done = !v.used;
-        if (!done) {
-            if (wait) { (void)hipEventSynchronize(v.ev); done = true; }
-            else done = hipEventQuery(v.ev) == hipSuccess;
-        }
-        if (done) {
-            (void)hipFree(v.d);
-            (void)hipEventDestroy(v.ev);
-        } else h->retired[keep++] = v;
-    }
-    h->retired.resize(keep);
-    (void)hipGetLastError();  // hipEventQuery's "not ready" is no error of ours
 }
 
 // a new version from h->w; caller holds the lock (or is create) and has set the device
@@ -338,20 +312,7 @@ int bf_upload(mi355_beamform *h)
                 }
             }
     }
-    BfVersion v;
-    MI355_HIP(hipMalloc(&v.d, img.size()));
-    hipError_t e = hipEventCreateWithFlags(&v.ev, hipEventDisableTiming);
-    if (e == hipSuccess) e = mi355_upload(h->ctx, v.d, img.data(), img.size());
-    if (e != hipSuccess) {
-        if (v.ev) (void)hipEventDestroy(v.ev);
-        (void)hipFree(v.d);
-        mi355_set_error("mi355_beamform: weight upload: %s", hipGetErrorString(e));
-        return MI355_ERR_HIP;
-    }
-    if (h->cur.d) h->retired.push_back(h->cur);
-    h->cur = v;
-    bf_reap(h, false);
-    return MI355_OK;
+    return h->tab.publish(h->ctx, img.data(), img.size(), "mi355_beamform: weight");
 }
 
 template <int KB, int BTW>
@@ -374,12 +335,12 @@ int bf_launch(mi355_beamform *h, long long nunits, const void *in, void *out, hi
 {
     const int cus = h->ctx->num_cus > 0 ? h->ctx->num_cus : 256;
     const long long T = nunits * h->Ti;
-    const signed char *d_raw = (const signed char *)h->cur.d;
+    const signed char *d_raw = (const signed char *)h->tab.current();
     int rc = MI355_OK;
     if (h->mfma && !h->generic && (reinterpret_cast<uintptr_t>(in) & 15u) == 0) {
         BfArgs a = {};
         a.in = (const unsigned char *)in;
-        a.tab = (const v4i *)((const char *)h->cur.d + h->raw_pad);
+        a.tab = (const v4i *)(d_raw + h->raw_pad);
         a.out = out;
         a.S = h->S; a.C = h->C; a.F = h->F; a.B = h->B; a.NBT = h->NBT; a.KBs = h->KBs;
         a.T = T; a.stokes = h->stokes;
@@ -417,9 +378,7 @@ int bf_launch(mi355_beamform *h, long long nunits, const void *in, void *out, hi
         MI355_HIP(hipGetLastError());
     }
     if (rc) return rc;
-    MI355_HIP(hipEventRecord(h->cur.ev, st));  // this version may be released behind this launch
-    h->cur.used = true;
-    return MI355_OK;
+    return h->tab.used(st);  // this version may be released behind this launch
 }
 
 int bf_args(const mi355_beamform *h, long long nunits, const void *in, const void *out)
@@ -508,9 +467,7 @@ extern "C" int mi355_beamform_destroy(mi355_beamform *h)
 {
     if (!h) return MI355_OK;
     (void)hipSetDevice(h->ctx->device);
-    if (h->cur.d) h->retired.push_back(h->cur);
-    h->cur = BfVersion();
-    bf_reap(h, true);
+    h->tab.release();
     h->pipe.release();
     delete h;
     return MI355_OK;

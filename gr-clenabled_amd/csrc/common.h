@@ -9,6 +9,7 @@
 #include <chrono>
 #include <mutex>
 #include <new>
+#include <vector>
 
 #include "mi355_clenabled.h"
 
@@ -28,6 +29,38 @@ struct mi355_ctx {
 hipError_t mi355_upload(mi355_ctx *ctx, void *dst_dev, const void *src_host, size_t bytes);
 // device-side fill on the upload stream, complete when it returns
 hipError_t mi355_fill(mi355_ctx *ctx, void *dst_dev, int value, size_t bytes);
+
+// A device table that a setter may replace while kernels of earlier work_dev calls still read it: the version in use plus the
+// replaced ones that are not known to be idle yet.  Every block with such a table keeps one of these.  The caller holds the
+// handle's lock and has set the device.  publish / drop / release are for create, the setters and destroy: they free, and release
+// waits, so they are never called on the work path.  Nothing here waits for the device as a whole.
+struct mi355_tables {
+    // a new version holding `bytes` of `img`, complete on the device when this returns; the one before is retired and the retired
+    // versions whose readers have finished are freed.  On failure the version in use stays and the error reads "`what` upload: ..."
+    int publish(mi355_ctx *ctx, const void *img, size_t bytes, const char *what);
+    void *current() const { return cur.d; }
+    // retires the version in use without a successor: current() is NULL until the next publish
+    void drop();
+    // after the launches of a call that read current(): the version outlives what `st` holds so far.  Records an event, no more.
+    int used(hipStream_t st);
+    // waits for the readers recorded here (this object's own events only) and frees every version
+    void release();
+    size_t held() const { return retired.size(); }
+
+private:
+    static constexpr int kSlots = 4;
+    struct Version {
+        void *d = nullptr;
+        size_t bytes = 0;
+        // readers, one slot per stream; a slot is in use once it has an event.  A fifth stream takes a slot over (see used)
+        hipStream_t st[kSlots] = {};
+        hipEvent_t ev[kSlots] = {};
+        int next = 0;
+    };
+    Version cur;
+    std::vector<Version> retired;
+    void reap(bool wait);
+};
 
 void mi355_set_error(const char *fmt, ...);
 // one diagnostics line to the registered sink (mi355_set_log_callback) or, by default, to stderr; DEBUG / INFO lines are

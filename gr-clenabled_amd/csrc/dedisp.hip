@@ -193,13 +193,6 @@ int dd_check_table(const int *tab, size_t n, int H)
     return MI355_OK;
 }
 
-struct DdVersion {
-    void *d = nullptr;          // [the caller's table | re-ordered table | min/max table]
-    hipEvent_t ev = nullptr;    // recorded behind the last launch that reads this version
-    bool used = false;
-    bool tiled = false;         // the LDS plan holds every window of this table
-};
-
 }  // namespace
 
 struct mi355_dedisp {
@@ -210,8 +203,8 @@ struct mi355_dedisp {
     bool generic = false;
     bool fits32 = false;   // a block's window spans less than 2^32 bytes: the tiled kernel's lane offsets are 32-bit
     std::vector<int> tab;  // the caller's layout
-    DdVersion cur;
-    std::vector<DdVersion> retired;
+    mi355_tables dtab;     // [the caller's table | re-ordered table | min/max table]
+    bool tiled = false;    // the LDS plan holds every window of the table in use
     HostPipe pipe;
     std::string route;
     std::mutex lock;
@@ -222,29 +215,10 @@ namespace {
 void dd_name_route(mi355_dedisp *h)
 {
     char buf[160];
-    if (h->cur.tiled && h->fits32 && !h->generic)
+    if (h->tiled && h->fits32 && !h->generic)
         snprintf(buf, sizeof buf, "tiled R=%d F=%d D=%d fb=%d dt=%d tt=%d", h->R, h->F, h->D, kDdFB, kDdDT, kDdTT);
     else snprintf(buf, sizeof buf, "generic R=%d F=%d D=%d", h->R, h->F, h->D);
     h->route = buf;
-}
-
-// frees the retired versions whose last launch has completed (all of them when `wait`); never called on the work path
-void dd_reap(mi355_dedisp *h, bool wait)
-{
-    size_t keep = 0;
-    for (DdVersion &v : h->retired) {
-        bool done = !v.used;
-        if (!done) {
-            if (wait) { (void)hipEventSynchronize(v.ev); done = true; }
-            else done = hipEventQuery(v.ev) == hipSuccess;
-        }
-        if (done) {
-            (void)hipFree(v.d);
-            (void)hipEventDestroy(v.ev);
-        } else h->retired[keep++] = v;
-    }
-    h->retired.resize(keep);
-    (void)hipGetLastError();  // hipEventQuery's "not ready" is no error of ours
 }
 
 // a new version from `tab`; caller holds the lock (or is create) and has set the device.  On failure the version in use is unchanged.
@@ -277,32 +251,21 @@ int dd_upload(mi355_dedisp *h, const int *tab)
             if (hi - lo > kDdSpread) tiled = false;
         }
     }
-    DdVersion v;
-    v.tiled = tiled;
-    MI355_HIP(hipMalloc(&v.d, img.size()));
-    hipError_t e = hipEventCreateWithFlags(&v.ev, hipEventDisableTiming);
-    if (e == hipSuccess) e = mi355_upload(h->ctx, v.d, img.data(), img.size());
-    if (e != hipSuccess) {
-        if (v.ev) (void)hipEventDestroy(v.ev);
-        (void)hipFree(v.d);
-        mi355_set_error("mi355_dedisp: table upload: %s", hipGetErrorString(e));
-        return MI355_ERR_HIP;
-    }
-    if (h->cur.d) h->retired.push_back(h->cur);
-    h->cur = v;
-    dd_reap(h, false);
-    return MI355_OK;
+    const int rc = h->dtab.publish(h->ctx, img.data(), img.size(), "mi355_dedisp: table");
+    if (rc == MI355_OK) h->tiled = tiled;
+    return rc;
 }
 
 // caller holds the lock and has set the device
 int dd_launch(mi355_dedisp *h, long long n, const void *in, void *out, long long pitch, hipStream_t st)
 {
     const int cus = h->ctx->num_cus > 0 ? h->ctx->num_cus : 256;
-    const int *d_raw = (const int *)h->cur.d;
-    if (h->cur.tiled && h->fits32 && !h->generic) {
+    const char *d_tab = (const char *)h->dtab.current();
+    const int *d_raw = (const int *)d_tab;
+    if (h->tiled && h->fits32 && !h->generic) {
         DdArgs a = {};
-        const v8i *tabT = (const v8i *)((const char *)h->cur.d + h->raw_pad);
-        const int2 *mm = (const int2 *)((const char *)h->cur.d + h->raw_pad + h->tabT_bytes);
+        const v8i *tabT = (const v8i *)(d_tab + h->raw_pad);
+        const int2 *mm = (const int2 *)(d_tab + h->raw_pad + h->tabT_bytes);
         a.R = h->R; a.F = h->F; a.D = h->D; a.ntd = h->ntd; a.nfb = h->nfb;
         a.n = n; a.ntot = n + h->H; a.pitch = pitch;
         const long long ntt = (n + kDdTT - 1) / kDdTT;
@@ -321,9 +284,7 @@ int dd_launch(mi355_dedisp *h, long long n, const void *in, void *out, long long
             hipLaunchKernelGGL(k_dd_gen<MI355_DEDISP_TIME_MAJOR>, grid, dim3(256), 0, st, (const float *)in, d_raw, (float *)out, h->R, h->F, h->D, n, pitch);
     }
     MI355_HIP(hipGetLastError());
-    MI355_HIP(hipEventRecord(h->cur.ev, st));  // this version may be released behind this launch
-    h->cur.used = true;
-    return MI355_OK;
+    return h->dtab.used(st);  // this version may be released behind this launch
 }
 
 // floats from the first to one past the last that a call for n outputs may write
@@ -417,9 +378,7 @@ extern "C" int mi355_dedisp_destroy(mi355_dedisp *h)
 {
     if (!h) return MI355_OK;
     (void)hipSetDevice(h->ctx->device);
-    if (h->cur.d) h->retired.push_back(h->cur);
-    h->cur = DdVersion();
-    dd_reap(h, true);
+    h->dtab.release();
     h->pipe.release();
     delete h;
     return MI355_OK;

@@ -355,12 +355,6 @@ int fe_check(int S, int npol, int N, int P, int shift)
     return MI355_OK;
 }
 
-struct FeVersion {
-    float *d = nullptr;       // gains [r][N]
-    hipEvent_t ev = nullptr;  // recorded behind the last launch that reads this version
-    bool used = false;
-};
-
 }  // namespace
 
 struct mi355_fengine {
@@ -369,8 +363,7 @@ struct mi355_fengine {
     long long frame_bytes = 0;
     bool fused_ok = false, generic = false;
     std::vector<float> gains;             // the caller's layout, [r][N]
-    FeVersion cur;
-    std::vector<FeVersion> retired;
+    mi355_tables gtab;                    // gains [r][N] on the device
     float *d_taps = nullptr;
     void *d_tw = nullptr;                 // fused route: exp(-2 pi i k / N)
     unsigned long long *d_clips = nullptr;
@@ -415,43 +408,10 @@ void fe_name_route(mi355_fengine *h)
     h->route = buf;
 }
 
-// frees the retired versions whose last launch has completed (all of them when `wait`); never called on the work path
-void fe_reap(mi355_fengine *h, bool wait)
-{
-    size_t keep = 0;
-    for (FeVersion &v : h->retired) {
-        bool done = !v.used;
-        if (!done) {
-            if (wait) { (void)hipEventSynchronize(v.ev); done = true; }
-            else done = hipEventQuery(v.ev) == hipSuccess;
-        }
-        if (done) {
-            (void)hipFree(v.d);
-            (void)hipEventDestroy(v.ev);
-        } else h->retired[keep++] = v;
-    }
-    h->retired.resize(keep);
-    (void)hipGetLastError();  // hipEventQuery's "not ready" is no error of ours
-}
-
 // a new version from h->gains; caller holds the lock (or is create) and has set the device
 int fe_upload(mi355_fengine *h)
 {
-    FeVersion v;
-    const size_t bytes = h->gains.size() * sizeof(float);
-    MI355_HIP(hipMalloc((void **)&v.d, bytes));
-    hipError_t e = hipEventCreateWithFlags(&v.ev, hipEventDisableTiming);
-    if (e == hipSuccess) e = mi355_upload(h->ctx, v.d, h->gains.data(), bytes);
-    if (e != hipSuccess) {
-        if (v.ev) (void)hipEventDestroy(v.ev);
-        (void)hipFree(v.d);
-        mi355_set_error("mi355_fengine: gain upload: %s", hipGetErrorString(e));
-        return MI355_ERR_HIP;
-    }
-    if (h->cur.d) h->retired.push_back(h->cur);
-    h->cur = v;
-    fe_reap(h, false);
-    return MI355_OK;
+    return h->gtab.publish(h->ctx, h->gains.data(), h->gains.size() * sizeof(float), "mi355_fengine: gain");
 }
 
 int fe_ensure(void **p, size_t *have, size_t want)
@@ -503,7 +463,7 @@ int fe_launch_fused(mi355_fengine *h, long long n, const void *const *in, void *
             return MI355_ERR_UNSUPPORTED;
         }
         for (int i = 0; i < ns * h->npol; i++) a.in[i] = (const f2v *)in[s0 * h->npol + i];
-        a.gain = h->cur.d + (long long)s0 * h->npol * N;
+        a.gain = (const float *)h->gtab.current() + (long long)s0 * h->npol * N;
         a.clips = h->d_clips + (long long)s0 * h->npol;
         a.s0 = s0;
         a.gpw = (int)gpw;
@@ -554,7 +514,7 @@ int fe_launch_generic(mi355_fengine *h, long long n, const void *const *in, void
             rc = mi355_fft_work_dev(h->fft, (int)(nr * m), d_z, d_x, (void *)st);
             if (rc) return rc;
             hipLaunchKernelGGL(k_fe_quant, dim3(fe_grid(h->ctx, g.total)), dim3(256), 0, st, (const c32 *)d_x,
-                               (const float *)(h->cur.d + (long long)s0 * npol * N), h->d_clips + (long long)s0 * npol,
+                               (const float *)h->gtab.current() + (long long)s0 * npol * N, h->d_clips + (long long)s0 * npol,
                                (unsigned short *)((char *)out + t0 * h->frame_bytes), N, npol, h->S, s0, ns, (int)m, h->shift ? N / 2 : 0, g.total);
         }
     }
@@ -571,12 +531,7 @@ int fe_launch_generic(mi355_fengine *h, long long n, const void *const *in, void
 int fe_launch(mi355_fengine *h, long long n, const void *const *in, void *out, hipStream_t st)
 {
     const int rc = fe_is_fused(h) ? fe_launch_fused(h, n, in, out, st) : fe_launch_generic(h, n, in, out, st);
-    if (rc) return rc;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return MI355_OK;
-    MI355_HIP(hipEventRecord(h->cur.ev, st));  // this version may be released behind this launch
-    h->cur.used = true;
-    return MI355_OK;
+    return rc ? rc : h->gtab.used(st);  // this version may be released behind this launch
 }
 
 int fe_args(const mi355_fengine *h, long long n, const void *const *in, const void *out)
@@ -678,9 +633,7 @@ extern "C" int mi355_fengine_destroy(mi355_fengine *h)
 {
     if (!h) return MI355_OK;
     (void)hipSetDevice(h->ctx->device);
-    if (h->cur.d) h->retired.push_back(h->cur);
-    h->cur = FeVersion();
-    fe_reap(h, true);
+    h->gtab.release();
     if (h->ws_used) (void)hipEventSynchronize(h->ws_done);
     if (h->fft) (void)mi355_fft_destroy(h->fft);
     for (void *p : {(void *)h->d_taps, h->d_tw, (void *)h->d_clips, h->d_ws, h->d_in, h->d_out})

@@ -946,14 +946,13 @@ struct mi355_filter {
     int nf;                        // FFT size of the fast-convolution kernel (0 in time-domain mode)
     int nseg = 1, seg_len = 0, seg_first = 0;  // partitioned fast convolution of a long filter: segments, taps per segment, taps of segment 0
     std::vector<float> taps_host;  // ntaps floats or 2*ntaps floats
+    mi355_tables tab;       // the six tables below as one allocation; set_taps publishes a new one (upload_taps)
     float *d_taps_rev = nullptr;
     float *d_hb = nullptr;  // matrix-core direct form: zero-padded reversed taps (real taps only)
     int mf_kk = 0;          // MFMA steps per output block, 0 = kernel not applicable
     void *d_H = nullptr, *d_twf = nullptr, *d_twi = nullptr;
     void *d_Hu = nullptr;  // uniformly partitioned long filter (k_ols_ups): spectra of the 2048-tap segments, [ups][4096]
     int ups = 0;           // number of those segments (0: not applicable)
-    std::vector<void *> retired;   // tables of earlier taps, kept alive for kernels still in flight (see retire_dev)
-    size_t retired_bytes = 0, table_bytes = 0;
     // what the last work / work_dev launched (mi355_filter_last_route): a kind and two ints, formatted when asked for
     int rt_kind = 0, rt_a = 0, rt_b = 0;
     char rt_text[64] = "";
@@ -996,50 +995,14 @@ int pick_fft_size(int ntaps)
     return nf;
 }
 
-// tables of the previous taps: possibly still read by kernels in flight on the caller's streams
-void retire_dev(mi355_filter *h)
-{
-    size_t held = 0;
-    for (void *p : {(void *)h->d_taps_rev, (void *)h->d_hb, (void *)h->d_H, (void *)h->d_Hu, (void *)h->d_twf, (void *)h->d_twi})
-        if (p) h->retired.push_back(p);
-    h->retired_bytes += h->table_bytes;
-    held = h->retired_bytes;
-    h->table_bytes = 0;
-    h->d_taps_rev = nullptr;
-    h->d_hb = nullptr;
-    h->d_H = h->d_Hu = h->d_twf = h->d_twi = nullptr;
-    h->ups = 0;
-    if (held > ((size_t)64 << 20)) {  // a long series of retunes: pay one device-wide wait and start over
-        (void)hipDeviceSynchronize();
-        for (void *p : h->retired) (void)hipFree(p);
-        h->retired.clear();
-        h->retired_bytes = 0;
-    }
-}
-
-void free_dev(mi355_filter *h)
-{
-    for (void *p : h->retired) (void)hipFree(p);
-    h->retired.clear();
-    h->retired_bytes = 0;
-    (void)hipSetDevice(h->ctx->device);
-    if (h->d_taps_rev) (void)hipFree(h->d_taps_rev);
-    if (h->d_hb) (void)hipFree(h->d_hb);
-    h->d_hb = nullptr;
-    if (h->d_H) (void)hipFree(h->d_H);
-    if (h->d_Hu) (void)hipFree(h->d_Hu);
-    h->d_Hu = nullptr;
-    h->ups = 0;
-    if (h->d_twf) (void)hipFree(h->d_twf);
-    if (h->d_twi) (void)hipFree(h->d_twi);
-    h->d_taps_rev = nullptr;
-    h->d_H = h->d_twf = h->d_twi = nullptr;
-}
-
-int upload_taps_impl(mi355_filter *h, const void *taps, int ntaps)
+// New taps: every table is built on the host, the six of them leave as one image ([reversed taps | matrix-core taps | H | Hu | forward
+// twiddles | inverse twiddles], each at a 256-byte boundary) and the handle changes only once that image is on the device.  Caller holds
+// h->lock (or is create).  On failure the taps before keep serving.
+int upload_taps(mi355_filter *h, const void *taps, int ntaps)
 {
     MI355_REQUIRE(taps && ntaps >= 1, "taps must hold at least one tap");
     const int per = h->complex_taps ? 2 : 1;
+    const float *t = (const float *)taps;
     int nf = 0, nseg = 1, seg_len = ntaps, seg_first = ntaps;
     if (!h->use_time) {
         if (ntaps <= kOlsMaxTaps) nf = pick_fft_size(ntaps);
@@ -1055,44 +1018,28 @@ int upload_taps_impl(mi355_filter *h, const void *taps, int ntaps)
             nf = 4096;
         }
     }
-    MI355_HIP(hipSetDevice(h->ctx->device));
-    // kernels of earlier device-path calls may still be reading the current tables: they are retired (kept until the handle goes,
-    // or until 64 MiB have piled up), not freed -- hipFree would wait for the whole device, as the hipDeviceSynchronize() that
-    // stood here did, stalling every other block in the flowgraph while one filter is retuned
-    retire_dev(h);
-    h->ntaps = ntaps;
-    h->nf = nf;
-    h->nseg = nseg;
-    h->seg_len = seg_len;
-    h->seg_first = seg_first;
-    h->taps_host.assign((const float *)taps, (const float *)taps + (size_t)per * ntaps);
     // reversed taps for the direct form (lib/fir_filter.cc:187-189 reverses them too)
     const int kpad = (ntaps + kTdU - 1) / kTdU * kTdU;
     std::vector<float> rev((size_t)per * (kpad + kTdU), 0.0f);  // zero padded: the kernel loops to kpad without a bound test and prefetches one block of taps past it
     for (int k = 0; k < ntaps; k++)
-        for (int c = 0; c < per; c++) rev[(size_t)per * k + c] = h->taps_host[(size_t)per * (ntaps - 1 - k) + c];
-    MI355_HIP(hipMalloc((void **)&h->d_taps_rev, rev.size() * sizeof(float)));
-        h->table_bytes += rev.size() * sizeof(float);
-    MI355_HIP(mi355_upload(h->ctx, h->d_taps_rev, rev.data(), rev.size() * sizeof(float)));
-    h->mf_kk = 0;
+        for (int c = 0; c < per; c++) rev[(size_t)per * k + c] = t[(size_t)per * (ntaps - 1 - k) + c];
+    std::vector<float> hb, H, Hu, twf, twi;
+    int mf_kk = 0, ups = 0;
     {
         const int kk = (ntaps + 15 + 3) / 4;
         // the tile's input span must fit the prefetch registers (<= 497 taps).  Longer filters were tried with an in-place fill:
         // no faster than the vector kernel (one workgroup per CU at that LDS size), and the extra path cost the short ones 15 %
         if (kMfTile + 4 * kk <= kMfPre * kMfThreads) {
             const size_t tl = (size_t)4 * kk + 16;
-            std::vector<float> hb(tl * per, 0.0f);  // [real parts | imaginary parts]
+            hb.assign(tl * per, 0.0f);  // [real parts | imaginary parts]
             for (int m = 0; m < ntaps; m++)
-                for (int cpt = 0; cpt < per; cpt++) hb[cpt * tl + m + 15] = h->taps_host[(size_t)per * (ntaps - 1 - m) + cpt];
-            MI355_HIP(hipMalloc((void **)&h->d_hb, hb.size() * sizeof(float)));
-        h->table_bytes += hb.size() * sizeof(float);
-            MI355_HIP(mi355_upload(h->ctx, h->d_hb, hb.data(), hb.size() * sizeof(float)));
-            h->mf_kk = kk;
+                for (int cpt = 0; cpt < per; cpt++) hb[cpt * tl + m + 15] = t[(size_t)per * (ntaps - 1 - m) + cpt];
+            mf_kk = kk;
         }
     }
     if (nf) {
-        // H[k] = sum_n (h[n]/NF) exp(-2 pi i k n / NF), evaluated in double (lib/fft_filter.cc:52-66)
-        std::vector<float> H(2 * (size_t)nf * nseg), twf(2 * (size_t)nf), twi(2 * (size_t)nf);
+        twf.resize(2 * (size_t)nf);
+        twi.resize(2 * (size_t)nf);
         std::vector<double> cs(nf), sn(nf);
         for (int k = 0; k < nf; k++) {
             double a = -2.0 * M_PI * (double)k / (double)nf;
@@ -1100,68 +1047,48 @@ int upload_taps_impl(mi355_filter *h, const void *taps, int ntaps)
             twf[2 * k] = (float)cs[k]; twf[2 * k + 1] = (float)sn[k];
             twi[2 * k] = (float)cs[k]; twi[2 * k + 1] = (float)(-sn[k]);
         }
-        for (int sgm = 0; sgm < nseg; sgm++) {
-            const int t0 = sgm == 0 ? 0 : seg_first + (sgm - 1) * seg_len, tn = sgm == 0 ? seg_first : seg_len;  // taps [t0, t0 + tn)
+        // the spectrum of taps [t0, t0 + tn): H[k] = sum_n (h[n]/NF) exp(-2 pi i k n / NF), evaluated in double (lib/fft_filter.cc:52-66)
+        auto spectrum = [&](float *dst, int t0, int tn) {
             for (int k = 0; k < nf; k++) {
                 double re = 0, im = 0;
                 for (int n = 0; n < tn; n++) {
-                    double hr = h->taps_host[(size_t)per * (t0 + n)], hi = h->complex_taps ? h->taps_host[2 * (size_t)(t0 + n) + 1] : 0.0;
+                    double hr = t[(size_t)per * (t0 + n)], hi = h->complex_taps ? t[2 * (size_t)(t0 + n) + 1] : 0.0;
                     int idx = (int)(((long long)k * n) % nf);
                     re += hr * cs[idx] - hi * sn[idx];
                     im += hr * sn[idx] + hi * cs[idx];
                 }
-                H[2 * ((size_t)sgm * nf + k)] = (float)(re / nf); H[2 * ((size_t)sgm * nf + k) + 1] = (float)(im / nf);
+                dst[2 * (size_t)k] = (float)(re / nf); dst[2 * (size_t)k + 1] = (float)(im / nf);
             }
-        }
-        size_t bytes = 2 * (size_t)nf * sizeof(float);
+        };
+        H.resize(2 * (size_t)nf * nseg);
+        for (int sgm = 0; sgm < nseg; sgm++)
+            spectrum(&H[2 * (size_t)sgm * nf], sgm == 0 ? 0 : seg_first + (sgm - 1) * seg_len, sgm == 0 ? seg_first : seg_len);
         if (nseg > 1 && ntaps <= kUpsMaxSeg * kOlsMaxTaps) {
             // uniform partition for k_ols_ups: segment p = taps [2048 p, 2048 p + 2048), the last one zero padded
-            const int ups = (ntaps + kOlsMaxTaps - 1) / kOlsMaxTaps;
-            std::vector<float> Hu(2 * (size_t)nf * ups);
-            for (int sgm = 0; sgm < ups; sgm++) {
-                const int t0 = sgm * kOlsMaxTaps, tn = std::min(kOlsMaxTaps, ntaps - t0);
-                for (int k = 0; k < nf; k++) {
-                    double re = 0, im = 0;
-                    for (int n = 0; n < tn; n++) {
-                        double hr = h->taps_host[(size_t)per * (t0 + n)], hi = h->complex_taps ? h->taps_host[2 * (size_t)(t0 + n) + 1] : 0.0;
-                        int idx = (int)(((long long)k * n) % nf);
-                        re += hr * cs[idx] - hi * sn[idx];
-                        im += hr * sn[idx] + hi * cs[idx];
-                    }
-                    Hu[2 * ((size_t)sgm * nf + k)] = (float)(re / nf); Hu[2 * ((size_t)sgm * nf + k) + 1] = (float)(im / nf);
-                }
-            }
-            MI355_HIP(hipMalloc(&h->d_Hu, bytes * ups));
-        h->table_bytes += bytes * ups;
-            MI355_HIP(mi355_upload(h->ctx, h->d_Hu, Hu.data(), bytes * ups));
-            h->ups = ups;
+            ups = (ntaps + kOlsMaxTaps - 1) / kOlsMaxTaps;
+            Hu.resize(2 * (size_t)nf * ups);
+            for (int sgm = 0; sgm < ups; sgm++) spectrum(&Hu[2 * (size_t)sgm * nf], sgm * kOlsMaxTaps, std::min(kOlsMaxTaps, ntaps - sgm * kOlsMaxTaps));
         }
-        MI355_HIP(hipMalloc(&h->d_H, bytes * nseg));
-        h->table_bytes += bytes * nseg;
-        MI355_HIP(hipMalloc(&h->d_twf, bytes));
-        h->table_bytes += bytes;
-        MI355_HIP(hipMalloc(&h->d_twi, bytes));
-        h->table_bytes += bytes;
-        MI355_HIP(mi355_upload(h->ctx, h->d_H, H.data(), bytes * nseg));
-        MI355_HIP(mi355_upload(h->ctx, h->d_twf, twf.data(), bytes));
-        MI355_HIP(mi355_upload(h->ctx, h->d_twi, twi.data(), bytes));
     }
-    // (every upload above ran on the context's upload stream and was waited for there: mi355_upload)
+    std::vector<char> img;
+    auto place = [&](const std::vector<float> &v) {
+        const size_t off = (img.size() + 255) & ~(size_t)255;
+        img.resize(off + v.size() * sizeof(float), 0);
+        memcpy(img.data() + off, v.data(), v.size() * sizeof(float));
+        return off;
+    };
+    const size_t o_rev = place(rev), o_hb = place(hb), o_H = place(H), o_Hu = place(Hu), o_twf = place(twf), o_twi = place(twi);
+    MI355_HIP(hipSetDevice(h->ctx->device));
+    const int rc = h->tab.publish(h->ctx, img.data(), img.size(), "mi355_filter: tap table");
+    if (rc) return rc;
+    char *d = (char *)h->tab.current();
+    auto at = [&](const std::vector<float> &v, size_t off) { return v.empty() ? nullptr : (float *)(d + off); };
+    h->d_taps_rev = at(rev, o_rev); h->d_hb = at(hb, o_hb);
+    h->d_H = at(H, o_H); h->d_Hu = at(Hu, o_Hu); h->d_twf = at(twf, o_twf); h->d_twi = at(twi, o_twi);
+    h->ntaps = ntaps; h->nf = nf; h->nseg = nseg; h->seg_len = seg_len; h->seg_first = seg_first;
+    h->mf_kk = mf_kk; h->ups = ups;
+    h->taps_host.assign(t, t + (size_t)per * ntaps);
     return MI355_OK;
-}
-
-// A failure half way (out of memory while the tables are rebuilt) must not leave a handle whose sizes describe tables
-// that do not exist: the handle is marked empty and work() refuses with MI355_ERR_STATE until set_taps succeeds again.
-int upload_taps(mi355_filter *h, const void *taps, int ntaps)
-{
-    const int rc = upload_taps_impl(h, taps, ntaps);
-    if (rc != MI355_OK && rc != MI355_ERR_INVALID_ARG) {
-        free_dev(h);
-        h->ntaps = 0;
-        h->nf = 0;
-        h->mf_kk = 0;
-    }
-    return rc;
 }
 
 template <int NF, class G>
@@ -1258,10 +1185,6 @@ int launch_ols(mi355_filter *h, size_t nout, const void *in, void *out, hipStrea
 
 int launch_filter(mi355_filter *h, size_t nout, const void *in, void *out, hipStream_t st)
 {
-    if (h->ntaps < 1) {
-        mi355_set_error("the filter has no taps (the last set_taps failed)");
-        return MI355_ERR_STATE;
-    }
     if (nout == 0) return MI355_OK;
     if (!h->use_time && h->nf) {
         switch (h->nf) {
@@ -1465,7 +1388,7 @@ extern "C" int mi355_filter_create(mi355_ctx *ctx, int decimation, const void *t
     h->ntaps = 0; h->nf = 0;
     int rc = upload_taps(h, taps, ntaps);
     if (rc == MI355_OK) rc = h->pipe.init(ctx);
-    if (rc != MI355_OK) { free_dev(h); h->pipe.release(); delete h; return rc; }
+    if (rc != MI355_OK) { mi355_filter_destroy(h); return rc; }
     mi355_log(ctx, MI355_LOG_INFO, "%s: %d %s taps, decimation %d: %s (transform size %d)", complex_taps ? "clComplexFilter" : "clFilter", ntaps,
               complex_taps ? "complex" : "real", decimation, h->nf ? "overlap-save in the frequency domain" : "direct form", h->nf);
     *out = h;
@@ -1475,7 +1398,8 @@ extern "C" int mi355_filter_create(mi355_ctx *ctx, int decimation, const void *t
 extern "C" int mi355_filter_destroy(mi355_filter *h)
 {
     if (!h) return MI355_OK;
-    free_dev(h);
+    (void)hipSetDevice(h->ctx->device);
+    h->tab.release();
     h->pipe.release();
     delete h;
     return MI355_OK;
@@ -1531,7 +1455,9 @@ extern "C" int mi355_filter_work_dev(mi355_filter *h, size_t noutput_items, cons
                   "device buffers must be 8-byte aligned");
     std::lock_guard<std::mutex> g(h->lock);
     MI355_HIP(hipSetDevice(h->ctx->device));
-    return launch_filter(h, noutput_items, in, out, mi355_pick_stream(h->ctx, stream));
+    hipStream_t st = mi355_pick_stream(h->ctx, stream);
+    const int rc = launch_filter(h, noutput_items, in, out, st);
+    return rc ? rc : h->tab.used(st);  // these tables may be released behind this launch
 }
 
 extern "C" int mi355_filter_work(mi355_filter *h, size_t noutput_items, const void *in, void *out)

@@ -294,7 +294,7 @@ struct mi355_pspec {
     float scale = 1.f;
     bool has_window = false, force_generic = false;
     std::vector<float> win_host;          // N floats (ones without a window)
-    float *d_window = nullptr;            // fused route
+    mi355_tables win;                     // fused route: the window, N floats
     void *d_tw = nullptr;                 // fused route: exp(-2 pi i k / N)
     mi355_fft *fft = nullptr;             // generic route, made when first needed (and again after set_window)
     std::string route_name;
@@ -305,7 +305,6 @@ struct mi355_pspec {
     hipEvent_t ws_done = nullptr;
     hipStream_t ws_stream = nullptr;
     bool ws_used = false;
-    std::vector<void *> retired;          // windows of earlier set_window calls: kernels of device-path calls may still read them
     void *d_in = nullptr, *d_out = nullptr;  // host path staging
     size_t d_in_bytes = 0, d_out_bytes = 0;
     std::mutex lock;
@@ -380,7 +379,7 @@ int ps_launch_fused(mi355_pspec *h, long long S, const void *in, float *out, hip
     const int N = h->N, K = h->K, C = ps_chunk(N);
     const int nchunks = (K + C - 1) / C;
     PsArgs a;
-    a.window = h->d_window;
+    a.window = (const float *)h->win.current();
     a.tw = (const c32 *)h->d_tw;
     a.H = h->H;
     a.K = K;
@@ -501,22 +500,7 @@ int ps_args(const mi355_pspec *h, long long S, const void *in, void *out, long l
 // caller holds h->lock (or is create) and has set the device
 int ps_upload_window(mi355_pspec *h)
 {
-    float *d = nullptr;
-    MI355_HIP(hipMalloc((void **)&d, (size_t)h->N * sizeof(float)));
-    const hipError_t e = mi355_upload(h->ctx, d, h->win_host.data(), (size_t)h->N * sizeof(float));
-    if (e != hipSuccess) {
-        (void)hipFree(d);
-        mi355_set_error("mi355_pspec: window upload: %s", hipGetErrorString(e));
-        return MI355_ERR_HIP;
-    }
-    if (h->d_window) h->retired.push_back(h->d_window);
-    h->d_window = d;
-    if (h->retired.size() * (size_t)h->N * sizeof(float) > ((size_t)64 << 20)) {  // a long series of new windows: one device-wide wait, then start over
-        (void)hipDeviceSynchronize();
-        for (void *p : h->retired) (void)hipFree(p);
-        h->retired.clear();
-    }
-    return MI355_OK;
+    return h->win.publish(h->ctx, h->win_host.data(), (size_t)h->N * sizeof(float), "mi355_pspec: window");
 }
 
 }  // namespace
@@ -590,8 +574,8 @@ extern "C" int mi355_pspec_destroy(mi355_pspec *h)
     if (!h) return MI355_OK;
     (void)hipSetDevice(h->ctx->device);
     if (h->fft) (void)mi355_fft_destroy(h->fft);
-    for (void *p : h->retired) (void)hipFree(p);
-    for (void *p : {(void *)h->d_window, h->d_tw, h->d_ws, h->d_in, h->d_out})
+    h->win.release();
+    for (void *p : {h->d_tw, h->d_ws, h->d_in, h->d_out})
         if (p) (void)hipFree(p);
     if (h->ws_done) (void)hipEventDestroy(h->ws_done);
     delete h;
@@ -621,7 +605,7 @@ extern "C" int mi355_pspec_set_window(mi355_pspec *h, const float *window, int w
         (void)mi355_fft_destroy(h->fft);
         h->fft = nullptr;
     }
-    if (h->d_window) return ps_upload_window(h);
+    if (h->win.current()) return ps_upload_window(h);
     return MI355_OK;
 }
 
@@ -648,7 +632,9 @@ extern "C" int mi355_pspec_work_dev(mi355_pspec *h, long long nspectra, const vo
     if (rc || nspectra == 0) return rc;
     std::lock_guard<std::mutex> g(h->lock);
     MI355_HIP(hipSetDevice(h->ctx->device));
-    return ps_launch(h, nspectra, in, out, mi355_pick_stream(h->ctx, stream));
+    hipStream_t st = mi355_pick_stream(h->ctx, stream);
+    const int rc2 = ps_launch(h, nspectra, in, out, st);
+    return rc2 || !ps_is_fused(h) ? rc2 : h->win.used(st);  // this window may be released behind this launch
 }
 
 extern "C" int mi355_pspec_work(mi355_pspec *h, long long nspectra, const void *in, void *out)

@@ -232,12 +232,10 @@ struct mi355_resampler {
     int L = 1, M = 1, K = 0, nt = 0, complex_taps = 0;
     int phase = 0;                    // host state: a pure function of the outputs produced so far
     std::vector<float> taps_host;     // K floats, or 2 K for complex taps
-    float *d_rev = nullptr;           // [L][nt] reversed arms
+    mi355_tables rev;                 // [L][nt] reversed arms
     bool lds = false;                 // k_rs_lds serves the handle (else k_rs_plain); fixed by set_taps
     int interp = 0;                   // k_rs_interp with this many window registers serves it instead (0: no)
     int ntp = 0, tile = 0, x_off = 0, y_off = 0, lds_bytes = 0, wg_per_cu = 1;
-    std::vector<void *> retired;      // tables of earlier taps: kernels of device-path calls may still read them
-    size_t retired_bytes = 0, table_bytes = 0;
     void *d_in = nullptr, *d_out = nullptr;  // host path staging
     size_t d_in_items = 0, d_out_items = 0;
     std::mutex lock;
@@ -283,20 +281,6 @@ void rs_choose(mi355_resampler *h)
     h->wg_per_cu = k > 8 ? 8 : (k < 1 ? 1 : k);
 }
 
-void rs_retire(mi355_resampler *h)
-{
-    if (h->d_rev) h->retired.push_back(h->d_rev);
-    h->d_rev = nullptr;
-    h->retired_bytes += h->table_bytes;
-    h->table_bytes = 0;
-    if (h->retired_bytes > ((size_t)64 << 20)) {  // a long series of retunes: one device-wide wait, then start over
-        (void)hipDeviceSynchronize();
-        for (void *p : h->retired) (void)hipFree(p);
-        h->retired.clear();
-        h->retired_bytes = 0;
-    }
-}
-
 // caller holds h->lock (or is create) and has set the device
 int rs_upload(mi355_resampler *h, const void *taps, int K)
 {
@@ -310,17 +294,8 @@ int rs_upload(mi355_resampler *h, const void *taps, int K)
         const int p = k % L, j = k / L;
         for (int e = 0; e < E; e++) rev[((size_t)p * nt + (nt - 1 - j)) * E + e] = t[(size_t)k * E + e];
     }
-    float *d = nullptr;
-    MI355_HIP(hipMalloc((void **)&d, rev.size() * sizeof(float)));
-    const hipError_t e = mi355_upload(h->ctx, d, rev.data(), rev.size() * sizeof(float));
-    if (e != hipSuccess) {
-        (void)hipFree(d);
-        mi355_set_error("mi355_resampler: table upload: %s", hipGetErrorString(e));
-        return MI355_ERR_HIP;
-    }
-    rs_retire(h);
-    h->d_rev = d;
-    h->table_bytes = rev.size() * sizeof(float);
+    const int rc2 = h->rev.publish(h->ctx, rev.data(), rev.size() * sizeof(float), "mi355_resampler: table");
+    if (rc2) return rc2;
     h->K = K; h->nt = nt;
     h->taps_host.assign(t, t + (size_t)K * E);
     rs_choose(h);
@@ -341,13 +316,14 @@ int rs_launch(mi355_resampler *h, long long n, int phase, const void *in, void *
 {
     const c32 *x = (const c32 *)in;
     c32 *y = (c32 *)out;
+    const float *d_rev = (const float *)h->rev.current();
     const int cus = h->ctx->num_cus > 0 ? h->ctx->num_cus : 256;
     if (h->interp) {
         const long long bcount = ((long long)phase + n - 1) / h->L + 1, tiles = (bcount + kRiTile - 1) / kRiTile, cap = (long long)cus * h->wg_per_cu;
         const dim3 grid((unsigned)(tiles < cap ? tiles : cap));
 #define RI_CASE(CT, NTB)                                                                                                          \
     if ((h->complex_taps != 0) == CT && h->interp == NTB)                                                                         \
-        hipLaunchKernelGGL((k_rs_interp<CT, NTB>), grid, dim3(kRsThreads), (size_t)h->lds_bytes, st, x, y, h->d_rev, h->L, h->nt, phase, n, h->x_off, h->y_off);
+        hipLaunchKernelGGL((k_rs_interp<CT, NTB>), grid, dim3(kRsThreads), (size_t)h->lds_bytes, st, x, y, d_rev, h->L, h->nt, phase, n, h->x_off, h->y_off);
         RI_CASE(false, 8) RI_CASE(false, 16) RI_CASE(false, 24) RI_CASE(false, 32) RI_CASE(false, 40)
         RI_CASE(true, 8) RI_CASE(true, 16) RI_CASE(true, 24) RI_CASE(true, 32) RI_CASE(true, 40)
 #undef RI_CASE
@@ -355,16 +331,16 @@ int rs_launch(mi355_resampler *h, long long n, int phase, const void *in, void *
         const long long tiles = (n + h->tile - 1) / h->tile, cap = (long long)cus * h->wg_per_cu;
         const dim3 grid((unsigned)(tiles < cap ? tiles : cap));
         if (h->complex_taps)
-            hipLaunchKernelGGL(k_rs_lds<true>, grid, dim3(kRsThreads), (size_t)h->lds_bytes, st, x, y, h->d_rev, h->L, h->M, h->nt, h->ntp, phase, n, h->tile, h->x_off);
+            hipLaunchKernelGGL(k_rs_lds<true>, grid, dim3(kRsThreads), (size_t)h->lds_bytes, st, x, y, d_rev, h->L, h->M, h->nt, h->ntp, phase, n, h->tile, h->x_off);
         else
-            hipLaunchKernelGGL(k_rs_lds<false>, grid, dim3(kRsThreads), (size_t)h->lds_bytes, st, x, y, h->d_rev, h->L, h->M, h->nt, h->ntp, phase, n, h->tile, h->x_off);
+            hipLaunchKernelGGL(k_rs_lds<false>, grid, dim3(kRsThreads), (size_t)h->lds_bytes, st, x, y, d_rev, h->L, h->M, h->nt, h->ntp, phase, n, h->tile, h->x_off);
     } else {
         const long long blocks = (n + kRsThreads - 1) / kRsThreads, cap = (long long)cus * 32;
         const dim3 grid((unsigned)(blocks < cap ? blocks : cap));
         if (h->complex_taps)
-            hipLaunchKernelGGL(k_rs_plain<true>, grid, dim3(kRsThreads), 0, st, x, y, h->d_rev, h->L, h->M, h->nt, phase, n);
+            hipLaunchKernelGGL(k_rs_plain<true>, grid, dim3(kRsThreads), 0, st, x, y, d_rev, h->L, h->M, h->nt, phase, n);
         else
-            hipLaunchKernelGGL(k_rs_plain<false>, grid, dim3(kRsThreads), 0, st, x, y, h->d_rev, h->L, h->M, h->nt, phase, n);
+            hipLaunchKernelGGL(k_rs_plain<false>, grid, dim3(kRsThreads), 0, st, x, y, d_rev, h->L, h->M, h->nt, phase, n);
     }
     MI355_HIP(hipGetLastError());
     return MI355_OK;
@@ -452,8 +428,7 @@ extern "C" int mi355_resampler_destroy(mi355_resampler *h)
 {
     if (!h) return MI355_OK;
     (void)hipSetDevice(h->ctx->device);
-    for (void *p : h->retired) (void)hipFree(p);
-    if (h->d_rev) (void)hipFree(h->d_rev);
+    h->rev.release();
     if (h->d_in) (void)hipFree(h->d_in);
     if (h->d_out) (void)hipFree(h->d_out);
     delete h;
@@ -509,7 +484,9 @@ extern "C" int mi355_resampler_work_dev(mi355_resampler *h, long long noutput, c
     MI355_REQUIRE(!rs_overlap(in_with_history, rs_needed(h->L, h->M, h->nt, h->phase, noutput), out, noutput),
                   "clRationalResampler does not work in place: in and out overlap");
     MI355_HIP(hipSetDevice(h->ctx->device));
-    rc = rs_launch(h, noutput, h->phase, in_with_history, out, mi355_pick_stream(h->ctx, stream));
+    hipStream_t st = mi355_pick_stream(h->ctx, stream);
+    rc = rs_launch(h, noutput, h->phase, in_with_history, out, st);
+    if (rc == MI355_OK) rc = h->rev.used(st);  // this table may be released behind this launch
     if (rc) return rc;
     const long long adv = (long long)h->phase + noutput * h->M;  // the phase is a kernel argument: no device state
     if (consumed) *consumed = adv / h->L;

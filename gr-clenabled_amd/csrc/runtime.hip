@@ -187,6 +187,86 @@ hipError_t mi355_fill(mi355_ctx *ctx, void *dst_dev, int value, size_t bytes)
     return e;
 }
 
+// ---------------------------------------------------------------------------
+// mi355_tables (common.h)
+// ---------------------------------------------------------------------------
+int mi355_tables::publish(mi355_ctx *ctx, const void *img, size_t bytes, const char *what)
+{
+    Version v;
+    v.bytes = bytes;
+    hipError_t e = hipMalloc(&v.d, bytes ? bytes : 1);
+    if (e == hipSuccess) e = mi355_upload(ctx, v.d, img, bytes);
+    if (e != hipSuccess) {
+        if (v.d) (void)hipFree(v.d);
+        mi355_set_error("%s upload: %s", what, hipGetErrorString(e));
+        return MI355_ERR_HIP;
+    }
+    drop();
+    cur = v;
+    reap(false);
+    size_t held_bytes = 0;
+    for (const Version &r : retired) held_bytes += r.bytes;
+    mi355_log(ctx, MI355_LOG_DEBUG, "tables: %zu retired versions held (%zu bytes)", retired.size(), held_bytes);
+    return MI355_OK;
+}
+
+void mi355_tables::drop()
+{
+    if (cur.d) retired.push_back(cur);
+    cur = Version();
+}
+
+int mi355_tables::used(hipStream_t st)
+{
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return MI355_OK;  // a graph orders its own nodes
+    int s = -1;
+    for (int i = 0; i < kSlots && s < 0; i++)
+        if (cur.ev[i] && cur.st[i] == st) s = i;
+    for (int i = 0; i < kSlots && s < 0; i++)
+        if (!cur.ev[i]) {
+            MI355_HIP(hipEventCreateWithFlags(&cur.ev[i], hipEventDisableTiming));
+            s = i;
+        }
+    if (s < 0) {
+        // more streams than slots: `st` takes one over, round-robin, and first waits for what the slot stood for, so that the
+        // record below covers the displaced stream's readers as well
+        s = cur.next;
+        cur.next = (cur.next + 1) % kSlots;
+        MI355_HIP(hipStreamWaitEvent(st, cur.ev[s], 0));
+    }
+    cur.st[s] = st;
+    MI355_HIP(hipEventRecord(cur.ev[s], st));
+    return MI355_OK;
+}
+
+// frees the retired versions whose readers have all finished (every one, after waiting for them, when `wait`)
+void mi355_tables::reap(bool wait)
+{
+    size_t keep = 0;
+    for (Version &v : retired) {
+        bool done = true;
+        for (int i = 0; i < kSlots; i++) {
+            if (!v.ev[i]) continue;
+            if (wait) (void)hipEventSynchronize(v.ev[i]);
+            else if (hipEventQuery(v.ev[i]) != hipSuccess) done = false;
+        }
+        if (done) {
+            (void)hipFree(v.d);
+            for (int i = 0; i < kSlots; i++)
+                if (v.ev[i]) (void)hipEventDestroy(v.ev[i]);
+        } else retired[keep++] = v;
+    }
+    retired.resize(keep);
+    (void)hipGetLastError();  // hipEventQuery's "not ready" is no error of ours
+}
+
+void mi355_tables::release()
+{
+    drop();
+    reap(true);
+}
+
 extern "C" int mi355_ctx_device(const mi355_ctx *ctx) { return ctx ? ctx->device : MI355_ERR_INVALID_ARG; }
 
 extern "C" void *mi355_ctx_stream(mi355_ctx *ctx) { return ctx ? (void *)ctx->stream[0] : nullptr; }

@@ -196,7 +196,7 @@ struct mi355_synth {
     bool ident = true;                // ch_map = 0 .. M-1
     bool force_generic = false;       // MI355_SYNTH_GENERIC at create
     std::vector<float> taps_host;
-    float *d_taps = nullptr;          // T x M, zero padded
+    mi355_tables taps;                // T x M, zero padded
     void *d_tw = nullptr;             // exp(+2 pi i k / M), k < M
     int *d_map = nullptr;             // nmap entries (also for the identity: the generic kernel of a partial identity needs none, but the table is tiny)
     int route = kRouteGeneric;
@@ -206,8 +206,6 @@ struct mi355_synth {
     MrSynthGeo mg;
     void *d_ws = nullptr;             // generic route: transformed frames of one piece
     size_t ws_items = 0;
-    std::vector<void *> retired;      // tables of earlier taps: kernels of device-path calls may still read them
-    size_t retired_bytes = 0, table_bytes = 0;
     void *d_in = nullptr, *d_out = nullptr;  // host path staging
     size_t d_in_items = 0, d_out_items = 0;
     std::mutex lock;
@@ -264,20 +262,6 @@ int syn_choose(mi355_synth *h)
     return MI355_OK;
 }
 
-void syn_retire(mi355_synth *h)
-{
-    if (h->d_taps) h->retired.push_back(h->d_taps);
-    h->d_taps = nullptr;
-    h->retired_bytes += h->table_bytes;
-    h->table_bytes = 0;
-    if (h->retired_bytes > ((size_t)64 << 20)) {  // a long series of retunes: one device-wide wait, then start over
-        (void)hipDeviceSynchronize();
-        for (void *p : h->retired) (void)hipFree(p);
-        h->retired.clear();
-        h->retired_bytes = 0;
-    }
-}
-
 // caller holds h->lock (or is create) and has set the device
 int syn_upload(mi355_synth *h, const float *taps, int K)
 {
@@ -287,17 +271,8 @@ int syn_upload(mi355_synth *h, const float *taps, int K)
     const int T = syn_T(K, h->M);
     std::vector<float> pad((size_t)T * h->M, 0.f);
     for (int k = 0; k < K; k++) pad[k] = taps[k];  // g[r + M p] at p M + r: the padded taps as they are
-    float *d = nullptr;
-    MI355_HIP(hipMalloc((void **)&d, pad.size() * sizeof(float)));
-    const hipError_t e = mi355_upload(h->ctx, d, pad.data(), pad.size() * sizeof(float));
-    if (e != hipSuccess) {
-        (void)hipFree(d);
-        mi355_set_error("mi355_synth: tap upload: %s", hipGetErrorString(e));
-        return MI355_ERR_HIP;
-    }
-    syn_retire(h);
-    h->d_taps = d;
-    h->table_bytes = pad.size() * sizeof(float);
+    rc = h->taps.publish(h->ctx, pad.data(), pad.size() * sizeof(float), "mi355_synth: tap");
+    if (rc) return rc;
     h->K = K;
     h->T = T;
     h->taps_host.assign(taps, taps + K);
@@ -325,7 +300,8 @@ int syn_launch(mi355_synth *h, long long nframes, const void *in, void *out, hip
     const int M = h->M, T = h->T;
     const int cus = h->ctx->num_cus > 0 ? h->ctx->num_cus : 256;
     const int *map = h->ident ? nullptr : h->d_map;
-    if (h->route == kRouteMr) return mi355_fft_mr_synth_launch(h->plan, h->mg, h->ctx, in, out, h->d_taps, map, h->nmap, T, nframes, st);
+    const float *d_taps = (const float *)h->taps.current();
+    if (h->route == kRouteMr) return mi355_fft_mr_synth_launch(h->plan, h->mg, h->ctx, in, out, d_taps, map, h->nmap, T, nframes, st);
     if (h->route == kRoutePow2) {
         const int F = kSynPts / M;
         int per_cu = kSynLds / h->lds_bytes;
@@ -340,7 +316,7 @@ int syn_launch(mi355_synth *h, long long nframes, const void *in, void *out, hip
         SynP2 a;
         a.in = (const v2f *)in;
         a.out = (v2f *)out;
-        a.taps = h->d_taps;
+        a.taps = d_taps;
         a.tw = (const c32 *)h->d_tw;
         a.ch_map = map;
         a.nmap = h->nmap;
@@ -374,7 +350,7 @@ int syn_launch(mi355_synth *h, long long nframes, const void *in, void *out, hip
         if (g2 > (long long)cus * 32) g2 = (long long)cus * 32;
         hipLaunchKernelGGL(k_synth_dft, dim3((unsigned)g1), dim3(256), 0, st, (const c32 *)in, (c32 *)h->d_ws, (const c32 *)h->d_tw, map, h->nmap, M, l0,
                            tv);
-        hipLaunchKernelGGL(k_synth_fir, dim3((unsigned)g2), dim3(256), 0, st, (const c32 *)h->d_ws, (c32 *)out + l0 * M, h->d_taps, M, T, to);
+        hipLaunchKernelGGL(k_synth_fir, dim3((unsigned)g2), dim3(256), 0, st, (const c32 *)h->d_ws, (c32 *)out + l0 * M, d_taps, M, T, to);
     }
     MI355_HIP(hipGetLastError());
     return MI355_OK;
@@ -486,8 +462,7 @@ extern "C" int mi355_synth_destroy(mi355_synth *h)
 {
     if (!h) return MI355_OK;
     (void)hipSetDevice(h->ctx->device);
-    for (void *p : h->retired) (void)hipFree(p);
-    if (h->d_taps) (void)hipFree(h->d_taps);
+    h->taps.release();
     if (h->d_tw) (void)hipFree(h->d_tw);
     if (h->d_map) (void)hipFree(h->d_map);
     if (h->plan.d_tw) (void)hipFree(h->plan.d_tw);
@@ -532,7 +507,9 @@ extern "C" int mi355_synth_work_dev(mi355_synth *h, long long nframes, const voi
     MI355_REQUIRE(!syn_overlap(in_with_history, ((long long)h->T - 1 + nframes) * h->nmap, out, nframes * h->M),
                   "clPolyphaseSynthesizer does not work in place: in and out overlap");
     MI355_HIP(hipSetDevice(h->ctx->device));
-    return syn_launch(h, nframes, in_with_history, out, mi355_pick_stream(h->ctx, stream));
+    hipStream_t st = mi355_pick_stream(h->ctx, stream);
+    const int rc2 = syn_launch(h, nframes, in_with_history, out, st);
+    return rc2 ? rc2 : h->taps.used(st);  // this table may be released behind this launch
 }
 
 extern "C" int mi355_synth_work(mi355_synth *h, long long nframes, const void *in_with_history, void *out)

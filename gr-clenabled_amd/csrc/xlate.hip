@@ -199,9 +199,7 @@ struct mi355_xlate {
     std::vector<u64> phase, inc;            // host state: P_c of the next output, and its increment per output
     bool fused = false, generic = false;    // the shape has a fused route; the generic route is forced
     int tile_out = 0, sh = 31, lds_bytes = 0, cb = 1, wg_per_cu = 1;
-    float *d_tab = nullptr;                 // [C][2 KP] reversed, zero padded (fused shapes only)
-    size_t tab_bytes = 0, retired_bytes = 0;
-    std::vector<void *> retired;            // tables of earlier taps / frequencies: kernels of device-path calls may still read them
+    mi355_tables tab;                       // [C][2 KP] reversed, zero padded (fused shapes only)
     std::vector<mi355_filter *> filt;       // generic route: one internal clComplexFilter handle per channel (made when first needed)
     HostPipe pipe;
     std::string route;
@@ -264,24 +262,10 @@ void xl_bandpass(mi355_xlate *h, int c)
     }
 }
 
-void xl_retire(mi355_xlate *h)
-{
-    if (h->d_tab) h->retired.push_back(h->d_tab);
-    h->d_tab = nullptr;
-    h->retired_bytes += h->tab_bytes;
-    h->tab_bytes = 0;
-    if (h->retired_bytes > ((size_t)64 << 20)) {  // a long series of retunes: one device-wide wait, then start over
-        (void)hipDeviceSynchronize();
-        for (void *p : h->retired) (void)hipFree(p);
-        h->retired.clear();
-        h->retired_bytes = 0;
-    }
-}
-
 // the device table of the fused route from bp[]; caller holds the lock (or is create) and has set the device
 int xl_upload(mi355_xlate *h)
 {
-    if (!h->fused) { xl_retire(h); return MI355_OK; }
+    if (!h->fused) { h->tab.drop(); return MI355_OK; }
     const size_t per = (size_t)2 * h->KP;
     std::vector<float> tab(per * h->C, 0.f);
     for (int c = 0; c < h->C; c++)
@@ -289,18 +273,7 @@ int xl_upload(mi355_xlate *h)
             tab[c * per + 2 * (size_t)i] = h->bp[c][2 * (size_t)(h->K - 1 - i)];
             tab[c * per + 2 * (size_t)i + 1] = h->bp[c][2 * (size_t)(h->K - 1 - i) + 1];
         }
-    float *d = nullptr;
-    MI355_HIP(hipMalloc((void **)&d, tab.size() * sizeof(float)));
-    const hipError_t e = mi355_upload(h->ctx, d, tab.data(), tab.size() * sizeof(float));
-    if (e != hipSuccess) {
-        (void)hipFree(d);
-        mi355_set_error("mi355_xlate: table upload: %s", hipGetErrorString(e));
-        return MI355_ERR_HIP;
-    }
-    xl_retire(h);
-    h->d_tab = d;
-    h->tab_bytes = tab.size() * sizeof(float);
-    return MI355_OK;
+    return h->tab.publish(h->ctx, tab.data(), tab.size() * sizeof(float), "mi355_xlate: table");
 }
 
 void xl_drop_filters(mi355_xlate *h)
@@ -380,7 +353,7 @@ int xl_launch(mi355_xlate *h, long long n, const void *in, void *const *outs, co
 #define XL_LAUNCH(CB, OD)                                                                                                              \
     do {                                                                                                                               \
         MI355_HIP(hipFuncSetAttribute((const void *)k_xlate<CB, OD>, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_bytes));        \
-        hipLaunchKernelGGL((k_xlate<CB, OD>), grid, dim3(kXlThreads), (size_t)h->lds_bytes, st, (const c32 *)in, a, h->d_tab, h->C, h->K, \
+        hipLaunchKernelGGL((k_xlate<CB, OD>), grid, dim3(kXlThreads), (size_t)h->lds_bytes, st, (const c32 *)in, a, (const float *)h->tab.current(), h->C, h->K, \
                            h->KP, h->D, n, h->tile_out, h->sh, aoff);                                                                  \
     } while (0)
 #define XL_CASE(CB) do { if (h->D % 2) XL_LAUNCH(CB, true); else XL_LAUNCH(CB, false); } while (0)
@@ -490,8 +463,7 @@ extern "C" int mi355_xlate_destroy(mi355_xlate *h)
     if (!h) return MI355_OK;
     (void)hipSetDevice(h->ctx->device);
     xl_drop_filters(h);
-    for (void *p : h->retired) (void)hipFree(p);
-    if (h->d_tab) (void)hipFree(h->d_tab);
+    h->tab.release();
     h->pipe.release();
     delete h;
     return MI355_OK;
@@ -609,7 +581,9 @@ extern "C" int mi355_xlate_work_dev(mi355_xlate *h, long long noutput, const voi
     if (rc || noutput == 0) return rc;
     std::lock_guard<std::mutex> g(h->lock);
     MI355_HIP(hipSetDevice(h->ctx->device));
-    rc = xl_launch(h, noutput, in_with_history, outs, h->phase.data(), mi355_pick_stream(h->ctx, stream));
+    hipStream_t st = mi355_pick_stream(h->ctx, stream);
+    rc = xl_launch(h, noutput, in_with_history, outs, h->phase.data(), st);
+    if (rc == MI355_OK && h->fused && !h->generic) rc = h->tab.used(st);  // this table may be released behind this launch
     if (rc) return rc;
     for (int c = 0; c < h->C; c++) h->phase[c] += h->inc[c] * (u64)noutput;  // the phase is a kernel argument: no device state
     return MI355_OK;

@@ -196,6 +196,7 @@ int mi355_fft_work_dev(mi355_fft *h, int nvec, const void *in, void *out, void *
 int mi355_filter_create(mi355_ctx *ctx, int decimation, const void *taps, int ntaps, int complex_taps,
                         int use_time, mi355_filter **out);
 int mi355_filter_destroy(mi355_filter *h);
+/* takes effect at the next call; calls already enqueued keep what they were given */
 int mi355_filter_set_taps(mi355_filter *h, const void *taps, int ntaps);
 int mi355_filter_ntaps(const mi355_filter *h);
 int mi355_filter_get_taps(const mi355_filter *h, void *taps_out, int cap);
@@ -547,6 +548,7 @@ long long mi355_resampler_noutput_for(int interpolation, int decimation, int nta
 int mi355_resampler_create(mi355_ctx *ctx, int interpolation, int decimation, const void *taps, int ntaps, int complex_taps,
                            mi355_resampler **out);
 int mi355_resampler_destroy(mi355_resampler *h);
+/* takes effect at the next call; calls already enqueued keep what they were given */
 int mi355_resampler_set_taps(mi355_resampler *h, const void *taps, int ntaps);
 int mi355_resampler_ntaps(const mi355_resampler *h);
 int mi355_resampler_get_taps(const mi355_resampler *h, void *taps_out, int cap);
@@ -593,6 +595,7 @@ int mi355_synth_plan(int ntaps, int num_channels, int nmap, long long nframes, i
                      long long *noutput_items);
 int mi355_synth_create(mi355_ctx *ctx, const float *taps, int ntaps, int num_channels, const int *ch_map, int nmap, mi355_synth **out);
 int mi355_synth_destroy(mi355_synth *h);
+/* takes effect at the next call; calls already enqueued keep what they were given */
 int mi355_synth_set_taps(mi355_synth *h, const float *taps, int ntaps);
 int mi355_synth_ntaps(const mi355_synth *h);
 int mi355_synth_get_taps(const mi355_synth *h, float *taps_out, int cap);
@@ -694,11 +697,13 @@ int mi355_xlate_plan(int decimation, int ntaps, long long noutput, long long *ni
 int mi355_xlate_create(mi355_ctx *ctx, int decimation, const void *taps, int ntaps, int complex_taps, double samp_rate,
                        const double *center_freqs, int nfreq, int use_time, mi355_xlate **out);
 int mi355_xlate_destroy(mi355_xlate *h);
+/* takes effect at the next call; calls already enqueued keep what they were given */
 int mi355_xlate_set_taps(mi355_xlate *h, const void *taps, int ntaps);
 int mi355_xlate_ntaps(const mi355_xlate *h);
 int mi355_xlate_get_taps(const mi355_xlate *h, void *taps_out, int cap);
 int mi355_xlate_num_channels(const mi355_xlate *h);
 int mi355_xlate_decimation(const mi355_xlate *h);
+/* takes effect at the next call; calls already enqueued keep what they were given */
 int mi355_xlate_set_center_freq(mi355_xlate *h, int c, double freq);
 int mi355_xlate_get_center_freq(const mi355_xlate *h, int c, double *freq);
 int mi355_xlate_get_bandpass_taps(const mi355_xlate *h, int c, void *out, int cap);

@@ -255,6 +255,36 @@ def test_set_weights_between_enqueued_calls(gpu, pkg):
         assert np.array_equal(o2.cpu().numpy(), ref.voltage(x, w_new).reshape(-1)), r
 
 
+def test_set_weights_with_two_streams_on_one_handle(gpu, pkg):
+    """weights 1 read on stream A, then on stream B; weights 2 on B, weights 3 on A; one synchronisation at the end.  A weight table is
+    released only behind its readers on every stream, not behind the stream that happened to read it last."""
+    import torch
+    S, B, F, npol, T = 4, 1, 8, 1, 1
+    reps = 512  # T frames, repeated: a few thousand items per call
+    x, w1 = _data(S, B, F, npol, T)
+    ws = [w1, _data(S, B, F, npol, T, 9)[1], _data(S, B, F, npol, T, 10)[1]]
+    x = np.ascontiguousarray(np.concatenate([x] * reps))
+    blk = pkg.clBeamformer(*GPU_ARGS, ref.VOLTAGE, npol, S, F, B, 1, False, w1)
+    assert blk.route().startswith("mfma")
+    d_x = torch.from_numpy(x.reshape(-1)).cuda()
+    outs = [torch.full((T * reps * B * F * npol,), complex(np.nan, np.nan), dtype=torch.complex64, device="cuda") for _ in range(4)]
+    sA, sB = torch.cuda.Stream(), torch.cuda.Stream()
+    torch.cuda.synchronize()
+    with torch.cuda.stream(sA):
+        blk.work_device(T * reps, [d_x], [outs[0]])
+    with torch.cuda.stream(sB):
+        blk.work_device(T * reps, [d_x], [outs[1]])
+    blk.set_weights(ws[1])
+    with torch.cuda.stream(sB):
+        blk.work_device(T * reps, [d_x], [outs[2]])
+    blk.set_weights(ws[2])
+    with torch.cuda.stream(sA):
+        blk.work_device(T * reps, [d_x], [outs[3]])
+    torch.cuda.synchronize()
+    for i, w in enumerate((ws[0], ws[0], ws[1], ws[2])):
+        assert np.array_equal(outs[i].cpu().numpy(), ref.voltage(x, w).reshape(-1)), i
+
+
 def test_host_work_equals_device_work(gpu, pkg):
     S, B, F, npol, T = 20, 5, 8, 2, 17
     x, w = _data(S, B, F, npol, T)

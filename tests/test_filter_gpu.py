@@ -334,3 +334,113 @@ def test_lds_staged_decimators_agree(gpu, oracle, monkeypatch, ntaps, decim, cta
     torch.cuda.synchronize()
     assert relerr(y2.cpu().numpy().view(np.complex64).reshape(-1), ref) <= TOL
     assert relerr(got, y2.cpu().numpy().view(np.complex64).reshape(-1)) <= 2e-6  # (same products, same order; the compiler may contract differently)
+
+
+# ---- set_taps while device-path calls are still enqueued: the tables of the taps before stay alive behind them ----
+
+def _dev(x):
+    import torch
+    return torch.from_numpy(x.view(np.float32).reshape(-1, 2)).cuda()
+
+
+def _nan_out(n):
+    import torch
+    return torch.full((n, 2), float("nan"), device="cuda")
+
+
+def _host(y):
+    return y.cpu().numpy().view(np.complex64).reshape(-1)
+
+
+RETUNE = {  # ntaps, outputs, complex taps, use_time
+    "fft-65": (65, 4096, False, False),
+    "time-65": (65, 4096, False, True),
+    "fft-3000": (3000, 8192, False, False),  # the partitioned kernels: H and Hu of the packed table
+    "complex-65": (65, 4096, True, True),
+}
+
+
+def _retune_taps(rng, ntaps, cplx):
+    t = rng.standard_normal(ntaps) / np.sqrt(ntaps)
+    if cplx:
+        return ((t + 1j * rng.standard_normal(ntaps) / np.sqrt(ntaps)) / np.sqrt(2)).astype(np.complex64)
+    return t.astype(np.float32)
+
+
+@pytest.mark.parametrize("case", sorted(RETUNE))
+def test_set_taps_between_enqueued_calls(gpu, oracle, case):
+    """two work_device calls on one stream with set_taps between them and no synchronisation: the old taps entirely, then the new"""
+    import torch
+    ntaps, n, cplx, use_time = RETUNE[case]
+    rng = np.random.default_rng(900 + ntaps + n)
+    t1, t2 = _retune_taps(rng, ntaps, cplx), _retune_taps(rng, ntaps, cplx)
+    xh = crandn(rng, n + ntaps - 1)
+    fir = oracle.fir_ccc if cplx else oracle.fir_ccf
+    blk = (gpu.clComplexFilter if cplx else gpu.clFilter)(*GPU_ARGS, 1, t1, 1, 0, use_time)
+    d_x, o1, o2 = _dev(xh), _nan_out(n), _nan_out(n)
+    torch.cuda.synchronize()
+    blk.work_device(n, [d_x], [o1])
+    blk.set_taps2(t2)
+    blk.work_device(n, [d_x], [o2])
+    torch.cuda.synchronize()
+    assert relerr(_host(o1), fir(t1, xh, n)) <= TOL
+    assert relerr(_host(o2), fir(t2, xh, n)) <= TOL
+
+
+def test_set_taps_with_two_streams_on_one_handle(gpu, oracle):
+    """taps 1 read on stream A, then on stream B; taps 2 on B, taps 3 on A; one synchronisation at the end.  A table is released only
+    behind its readers on every stream, not behind the stream that happened to read it last."""
+    import torch
+    ntaps, n = 65, 4096
+    rng = np.random.default_rng(931)
+    taps = [_retune_taps(rng, ntaps, False) for _ in range(3)]
+    xh = crandn(rng, n + ntaps - 1)
+    blk = gpu.clFilter(*GPU_ARGS, 1, taps[0])
+    d_x = _dev(xh)
+    outs = [_nan_out(n) for _ in range(4)]
+    sA, sB = torch.cuda.Stream(), torch.cuda.Stream()
+    torch.cuda.synchronize()
+    with torch.cuda.stream(sA):
+        blk.work_device(n, [d_x], [outs[0]])
+    with torch.cuda.stream(sB):
+        blk.work_device(n, [d_x], [outs[1]])
+    blk.set_taps2(taps[1])
+    with torch.cuda.stream(sB):
+        blk.work_device(n, [d_x], [outs[2]])
+    blk.set_taps2(taps[2])
+    with torch.cuda.stream(sA):
+        blk.work_device(n, [d_x], [outs[3]])
+    torch.cuda.synchronize()
+    for i, t in enumerate((taps[0], taps[0], taps[1], taps[2])):
+        assert relerr(_host(outs[i]), oracle.fir_ccf(t, xh, n)) <= TOL, i
+
+
+def test_replaced_tables_are_released(gpu):
+    """the "tables:" debug line of every set_taps: with the device idle no replaced table is kept, and right behind a call at most the
+    one that call reads"""
+    import re
+    import torch
+    ntaps, n = 65, 4096
+    rng = np.random.default_rng(932)
+    d_x, d_y = _dev(crandn(rng, n + ntaps - 1)), _nan_out(n)
+    held = []
+
+    def sink(level, msg):
+        m = re.match(r"tables: (\d+) retired versions held", msg)
+        if m:
+            held.append(int(m.group(1)))
+
+    gpu.set_log_callback(sink)
+    try:
+        blk = gpu.clFilter(*GPU_ARGS, 1, _retune_taps(rng, ntaps, False), 1, 1)
+        for _ in range(6):
+            blk.set_taps2(_retune_taps(rng, ntaps, False))
+            blk.work_device(n, [d_x], [d_y])
+            torch.cuda.synchronize()
+        assert held == [0] * 7, held  # create and six set_taps
+        blk.work_device(n, [d_x], [d_y])
+        blk.set_taps2(_retune_taps(rng, ntaps, False))  # no synchronisation since the call
+        torch.cuda.synchronize()
+    finally:
+        gpu.set_log_callback(None)
+    assert len(held) == 8 and held[7] <= 1, held

@@ -281,6 +281,28 @@ def test_db_output(gpu, N):
     blk.stop()
 
 
+def test_set_window_between_enqueued_calls(gpu):
+    """two work_device calls on one stream with set_window between them and no synchronisation: the old window entirely, then the new"""
+    import torch
+    N, K, S = 256, 2, 4
+    w1 = ref.hann(N)
+    w2 = (w1 * np.linspace(0.5, 1.5, N)).astype(np.float32)
+    x = ref.make_input(ref.plan(N, K, N, S)[0], seed=21)
+    blk = gpu.clPowerSpectrum(*GPU_ARGS, N, K, w1)
+    assert blk.route().startswith("fused")
+    d_x = torch.from_numpy(x).cuda()
+    o1 = torch.full((S * N,), float("nan"), dtype=torch.float32, device="cuda")
+    o2 = torch.full_like(o1, float("nan"))
+    torch.cuda.synchronize()
+    assert blk.work_device(S, [d_x], [o1]) == S * N
+    blk.set_window(w2)
+    assert blk.work_device(S, [d_x], [o2]) == S * N
+    torch.cuda.synchronize()
+    assert relerr(o1.cpu().numpy().reshape(S, N), ref.pspec(x, N, K, N, S, w1)) <= ref.TOL
+    assert relerr(o2.cpu().numpy().reshape(S, N), ref.pspec(x, N, K, N, S, w2)) <= ref.TOL
+    blk.stop()
+
+
 def test_handle_behaviour(gpu):
     import torch
     N, K, H = 256, 6, 100

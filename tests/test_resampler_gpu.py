@@ -194,6 +194,28 @@ def test_host_pointer_work(gpu, case, n):
     blk.stop()
 
 
+def test_set_taps_between_enqueued_calls(gpu):
+    """two work_device calls on one stream with set_taps (24 -> 36 taps: the history changes) between them and no synchronisation:
+    the old taps entirely, then the new, from the phase the first call left"""
+    import torch
+    L, M, n = 3, 2, 2000
+    h1, h2 = ref.make_taps(24), ref.make_taps(36, seed=1)
+    c2 = ref.plan(L, M, 24, 0, n)[3]
+    x1, x2 = ref.make_input(L, M, 24, 0, n), ref.make_input(L, M, 36, c2, n, seed=1)
+    blk = gpu.clRationalResampler(*GPU_ARGS, L, M, h1)
+    d_x1, d_x2 = torch.from_numpy(x1).cuda(), torch.from_numpy(x2).cuda()
+    o1 = torch.full((n,), float("nan"), dtype=torch.complex64, device="cuda")
+    o2 = torch.full_like(o1, float("nan"))
+    torch.cuda.synchronize()
+    assert blk.work_device(n, [d_x1], [o1])[0] == n and blk.phase() == c2
+    blk.set_taps(h2)
+    assert blk.work_device(n, [d_x2], [o2])[0] == n
+    torch.cuda.synchronize()
+    assert ref.within(o1.cpu().numpy(), ref.resample(h1, L, M, x1, n, 0)[0], ref.bound(h1, L, x1, 0, M, n))
+    assert ref.within(o2.cpu().numpy(), ref.resample(h2, L, M, x2, n, c2)[0], ref.bound(h2, L, x2, c2, M, n))
+    blk.stop()
+
+
 def test_handle_behaviour(gpu):
     import torch
     L, M = 3, 2

@@ -294,6 +294,28 @@ def test_host_pointer_general_work(gpu, case, n):
     blk.stop()
 
 
+def test_set_taps_between_enqueued_calls(gpu):
+    """two work_device calls on one stream with set_taps (4 -> 6 taps per arm: the history changes) between them and no
+    synchronisation: the old taps entirely, then the new"""
+    import torch
+    M, n = 16, 40
+    g1, g2 = ref.make_taps(4 * M), ref.make_taps(6 * M, seed=1)
+    x1, x2 = ref.make_input(g1.size, M, M, n), ref.make_input(g2.size, M, M, n, seed=1)
+    blk = gpu.clPolyphaseSynthesizer(*GPU_ARGS, g1, M)
+    d_x1, d_x2 = torch.from_numpy(x1).cuda(), torch.from_numpy(x2).cuda()
+    o1 = torch.full((n * M,), float("nan"), dtype=torch.complex64, device="cuda")
+    o2 = torch.full_like(o1, float("nan"))
+    torch.cuda.synchronize()
+    assert blk.work_device(n, [d_x1], [o1]) == n * M
+    blk.set_taps(g2)
+    assert blk.taps_per_arm() == 6
+    assert blk.work_device(n, [d_x2], [o2]) == n * M
+    torch.cuda.synchronize()
+    assert relerr(o1.cpu().numpy(), ref.synth(g1, M, None, x1, n).astype(np.complex64)) <= ref.TOL
+    assert relerr(o2.cpu().numpy(), ref.synth(g2, M, None, x2, n).astype(np.complex64)) <= ref.TOL
+    blk.stop()
+
+
 def test_handle_behaviour(gpu):
     import torch
     M = 64

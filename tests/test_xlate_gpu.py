@@ -303,6 +303,41 @@ def test_retune_keeps_the_phase(gpu):
         blk.stop()
 
 
+@pytest.mark.parametrize("generic", [False, True])
+@pytest.mark.parametrize("setter", ["set_taps", "set_center_freq"])
+def test_setter_between_enqueued_calls(gpu, setter, generic):
+    """two work_device calls on one stream with a setter between them and no synchronisation: the old table entirely, then the new.
+    The yardstick's taps and phases are read from the handle before each call."""
+    import torch
+    D, K, C, n = 4, 33, 2, 1000
+    blk = gpu.clFreqXlatingFIRFilter(*GPU_ARGS, D, ref.make_taps(K, False, seed=3), [250000.0, -37.5], FS)
+    assert blk.route().startswith("fused")
+    blk.set_generic(generic)
+    assert blk.route().startswith("generic" if generic else "fused")
+    x = ref.make_input(ref.plan(D, K, 2 * n), seed=9)
+    d_x = torch.from_numpy(x).cuda()
+    outs = [[torch.full((n,), complex(np.nan, np.nan), dtype=torch.complex64, device="cuda") for _ in range(C)] for _ in range(2)]
+    torch.cuda.synchronize()
+    seen = []
+    for call in range(2):
+        if call == 1:
+            if setter == "set_taps":
+                blk.set_taps(ref.make_taps(K, False, seed=4))
+            else:
+                blk.set_center_freq(-123456.789, 1)
+        seen.append(([blk.bandpass_taps(c) for c in range(C)], [blk.state(c) for c in range(C)]))
+        assert blk.work_device(n, [d_x[call * n * D:]], outs[call]) == n
+    torch.cuda.synchronize()
+    assert not np.array_equal(seen[0][0][1], seen[1][0][1])
+    for call, (bs, states) in enumerate(seen):
+        xin = x[call * n * D:][:ref.plan(D, K, n)]
+        for c in range(C):
+            want, s = ref.xlate(bs[c], xin, D, n, states[c][0], states[c][1])
+            w = ref.worst(outs[call][c].cpu().numpy(), want, ref.bound(bs[c], xin, D, n, s))
+            assert w <= 1.0, (call, c, w)
+    blk.stop()
+
+
 def test_skip_is_exact_far_into_a_stream(gpu):
     """skip(2^40), then a call: the phase is inc 2^40 mod 2^64 exactly (a float or double accumulator is not), and the outputs match the
     yardstick at that index"""
