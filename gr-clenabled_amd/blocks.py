@@ -210,6 +210,10 @@ class clFFT(_Block):
                                              _dp(y, n * 8, "output"), st), "mi355_fft_work_dev")
         return noutput_items
 
+    def last_route(self):
+        """The kernels the last work() / work_device() launched and their parameters (mi355_fft_last_route); "" before the first call."""
+        return self._L.mi355_fft_last_route(self._h).decode()
+
 
 class _FilterBase(_Block):
     _destroy = "mi355_filter_destroy"

@@ -599,9 +599,23 @@ __global__ __launch_bounds__(256, (N / 4096 == 8 ? 1 : 2)) void k_fft_s(const vo
     }
 }
 
+// What a call launched (mi355_fft_last_route): a kind and a few ints, stored plainly at launch (no lock, nothing per frame) and
+// formatted when asked for.  Two streams on one handle: "last" is either call's.
+enum { kRtNone = 0, kRtFft, kRtFftS, kRtFft32k, kRtTile, kRtSub, kRtMr, kRtMrTile, kRtChirpz, kRtBluestein };
+struct FftRoute {
+    int kind = kRtNone;
+    int a = 0, b = 0, c = 0, d = 0;  // kRtFft: N, PF, schedule (1 = claims), grid; kRtFftS: N; kRtSub: S, passes; kRtChirpz / kRtBluestein: m
+    int wave = 0;                    // kRtFft in one-wave workgroups (MI355_FFT_WAVE_GEO)
+};
+inline void set_route(FftRoute *rt, int kind, int a = 0, int b = 0, int c = 0, int d = 0, int wave = 0)
+{
+    if (!rt) return;
+    rt->kind = kind; rt->a = a; rt->b = b; rt->c = c; rt->d = d; rt->wave = wave;
+}
+
 template <int N>
 int launch_s(mi355_ctx *ctx, int sign, const void *in, void *out, const float *window, const void *tw, int nframes, int shift,
-             int real_in, hipStream_t st)
+             int real_in, hipStream_t st, FftRoute *rt)
 {
     // interleaved A/B (tools/probe.py ab fft<N>, 2^26 samples): 16384 points 229 us with the two resident workgroups per CU as the grid,
     // 217 with 8 per CU, 206 with 12-16 (one or two frames per workgroup: nothing but the base twiddles is kept across frames, so short
@@ -615,6 +629,7 @@ int launch_s(mi355_ctx *ctx, int sign, const void *in, void *out, const float *w
             if (sign < 0) { if (real_in) LAUNCH_32K(-1, true); else LAUNCH_32K(-1, false); }
             else          { if (real_in) LAUNCH_32K(1, true);  else LAUNCH_32K(1, false); }
 #undef LAUNCH_32K
+            set_route(rt, kRtFft32k);
             MI355_HIP(hipGetLastError());
             return MI355_OK;
         }
@@ -624,6 +639,7 @@ int launch_s(mi355_ctx *ctx, int sign, const void *in, void *out, const float *w
     if (sign < 0) { if (real_in) LAUNCH_S(-1, true); else LAUNCH_S(-1, false); }
     else          { if (real_in) LAUNCH_S(1, true);  else LAUNCH_S(1, false); }
 #undef LAUNCH_S
+    set_route(rt, kRtFftS, N);
     MI355_HIP(hipGetLastError());
     return MI355_OK;
 }
@@ -1081,7 +1097,7 @@ int dump_stamps(const unsigned long long *d_ts, int n, int sign, int sched, int 
 
 template <int N, class G>
 int launch_g(mi355_ctx *ctx, int sign, const void *in, void *out, const float *window, const void *tw, int nframes, int shift,
-             int real_in, hipStream_t st, unsigned *claims)
+             int real_in, hipStream_t st, unsigned *claims, FftRoute *rt)
 {
     constexpr int F = G::F, TH = G::TH, WAVES = TH / 64;
     int ngroups = (nframes + F - 1) / F;
@@ -1133,6 +1149,7 @@ int launch_g(mi355_ctx *ctx, int sign, const void *in, void *out, const float *w
     else          { if (real_in) LAUNCH_FFT(1, true);  else LAUNCH_FFT(1, false); }
 #undef LAUNCH_FFT
 #undef LAUNCH_FFT_K
+    set_route(rt, kRtFft, N, pf, sched, grid, TH == 64);
     MI355_HIP(hipGetLastError());
     if (ts) return dump_stamps(ts, N, sign, sched, grid, ngroups, st);
     return MI355_OK;
@@ -1140,30 +1157,30 @@ int launch_g(mi355_ctx *ctx, int sign, const void *in, void *out, const float *w
 
 template <int N>
 int launch_n(mi355_ctx *ctx, int sign, const void *in, void *out, const float *window, const void *tw, int nframes, int shift,
-             int real_in, hipStream_t st, unsigned *claims)
+             int real_in, hipStream_t st, unsigned *claims, FftRoute *rt)
 {
     if constexpr (N >= 16 && N <= 1024) {
         // MI355_FFT_WAVE_GEO=1: one-wave workgroups (no workgroup barriers); measured slower for N >= 256, off by default
         static const bool wave = getenv("MI355_FFT_WAVE_GEO") ? atoi(getenv("MI355_FFT_WAVE_GEO")) != 0 : false;
         if (wave) MI355_SWITCH_NOTE(ctx, "MI355_FFT_WAVE_GEO", "k_fft in one-wave workgroups");
-        if (wave) return launch_g<N, GeoW<N>>(ctx, sign, in, out, window, tw, nframes, shift, real_in, st, claims);
+        if (wave) return launch_g<N, GeoW<N>>(ctx, sign, in, out, window, tw, nframes, shift, real_in, st, claims, rt);
     }
-    if constexpr (N == 32768) return launch_s<N>(ctx, sign, in, out, window, tw, nframes, shift, real_in, st);
+    if constexpr (N == 32768) return launch_s<N>(ctx, sign, in, out, window, tw, nframes, shift, real_in, st, rt);
     else if constexpr (N == 8192 || N == 16384) {
         // MI355_FFT_WHOLE_FRAME=1 selects the whole-frame kernel (512/1024 threads, frame image in LDS) for comparison
         static const bool whole = getenv("MI355_FFT_WHOLE_FRAME") ? atoi(getenv("MI355_FFT_WHOLE_FRAME")) != 0 : false;
-        if (!whole) return launch_s<N>(ctx, sign, in, out, window, tw, nframes, shift, real_in, st);
+        if (!whole) return launch_s<N>(ctx, sign, in, out, window, tw, nframes, shift, real_in, st, rt);
         MI355_SWITCH_NOTE(ctx, "MI355_FFT_WHOLE_FRAME", "k_fft with the whole frame in LDS instead of k_fft_s");
     }
-    if constexpr (N != 32768) return launch_g<N, Geo<N>>(ctx, sign, in, out, window, tw, nframes, shift, real_in, st, claims);
+    if constexpr (N != 32768) return launch_g<N, Geo<N>>(ctx, sign, in, out, window, tw, nframes, shift, real_in, st, claims, rt);
 }
 
 // claims: a word set of the calling handle for the dynamic schedule of the persistent path (NULL: the static schedule)
 int launch_fft(mi355_ctx *ctx, int n, int sign, const void *in, void *out, const float *window, const void *tw, int nframes,
-               int shift, int real_in, hipStream_t st, unsigned *claims = nullptr)
+               int shift, int real_in, hipStream_t st, unsigned *claims = nullptr, FftRoute *rt = nullptr)
 {
     switch (n) {
-#define CASE_N(NN) case NN: return launch_n<NN>(ctx, sign, in, out, window, tw, nframes, shift, real_in, st, claims)
+#define CASE_N(NN) case NN: return launch_n<NN>(ctx, sign, in, out, window, tw, nframes, shift, real_in, st, claims, rt)
         CASE_N(2); CASE_N(4); CASE_N(8); CASE_N(16); CASE_N(32); CASE_N(64); CASE_N(128); CASE_N(256); CASE_N(512);
         CASE_N(1024); CASE_N(2048); CASE_N(4096); CASE_N(8192); CASE_N(16384); CASE_N(32768);
 #undef CASE_N
@@ -1206,6 +1223,9 @@ struct mi355_fft {
     hipStream_t claim_st[kClaimSets] = {};
     int nclaim_st = 0;
     std::mutex claim_lock;
+    // what the last work / work_dev launched (mi355_fft_last_route); rt_sub: the size-m transform inside the unfused chirp-z path
+    FftRoute rt, rt_sub;
+    char rt_text[160] = "";
 };
 
 namespace {
@@ -1348,6 +1368,7 @@ int launch_chirpz_m(mi355_fft *h, const void *in, void *out, int nframes, hipStr
         hipLaunchKernelGGL((k_chirpz<M, false>), dim3(grid), dim3(TH), lds_bytes, st, in, (c32 *)out, (const c32 *)h->d_pre, src, (const c32 *)h->d_post,
                            (const c32 *)h->d_bspec, (const c32 *)h->d_twm_f, (const c32 *)h->d_twm_i, h->n, nframes, ngroups, lo);
     }
+    set_route(&h->rt, kRtChirpz, M);
     MI355_HIP(hipGetLastError());
     return MI355_OK;
 }
@@ -1415,7 +1436,7 @@ int launch_bluestein(mi355_fft *h, const void *in, void *out, int nframes, hipSt
         hipLaunchKernelGGL(k_blu_pre, dim3(grid_for(tm)), dim3(256), 0, st, (const char *)in + f0 * N * isz, (c32 *)h->d_wa,
                            (const c32 *)h->d_pre, (const int *)((const char *)h->d_post + (size_t)N * 8), N, M, tm,
                            h->dtype == MI355_DTYPE_FLOAT ? 1 : 0);
-        int rc = h->sub_f ? launch_handle(h->sub_f, h->d_wa, h->d_wb, nf, st) : launch_fft(h->ctx, M, -1, h->d_wa, h->d_wb, h->d_ones, h->d_twm_f, nf, 0, 0, st);
+        int rc = h->sub_f ? launch_handle(h->sub_f, h->d_wa, h->d_wb, nf, st) : launch_fft(h->ctx, M, -1, h->d_wa, h->d_wb, h->d_ones, h->d_twm_f, nf, 0, 0, st, nullptr, &h->rt_sub);
         if (rc) return rc;
         hipLaunchKernelGGL(k_blu_mul, dim3(grid_for(tm)), dim3(256), 0, st, (c32 *)h->d_wb, (const c32 *)h->d_bspec, M, tm);
         rc = h->sub_i ? launch_handle(h->sub_i, h->d_wb, h->d_wa, nf, st) : launch_fft(h->ctx, M, 1, h->d_wb, h->d_wa, h->d_ones, h->d_twm_i, nf, 0, 0, st);
@@ -1424,6 +1445,7 @@ int launch_bluestein(mi355_fft *h, const void *in, void *out, int nframes, hipSt
                            (const c32 *)h->d_post, N, M, tn, (h->sign < 0 && h->shift) ? len : 0);
         MI355_HIP(hipGetLastError());
     }
+    set_route(&h->rt, kRtBluestein, M);
     return ws_release(h, st);
 }
 
@@ -1539,8 +1561,10 @@ int launch_big(mi355_fft *h, const void *in, void *out, int nframes, hipStream_t
             if (rc) return rc;
             rc = launch_tile_nr<true>(h, n2, h->d_wa, (c32 *)out + f0 * N, tw2, n1, nf, (h->sign < 0 && h->shift) ? n2 / 2 : 0, false, st);
             if (rc) return rc;
+            set_route(&h->rt, kRtTile, n1, n2);
             continue;
         }
+        set_route(&h->rt, kRtSub, S, four_pass ? 4 : three_pass ? 3 : 2);
 #define SUB(SG, RL) hipLaunchKernelGGL((k_fft_sub<SG, RL>), dim3(grid), dim3(256), 0, st, src, (c32 *)h->d_wa, h->d_window, tw4096, S, nsub, in_xor)
         if (h->sign < 0) { if (h->dtype == MI355_DTYPE_FLOAT) SUB(-1, true); else SUB(-1, false); }
         else             { if (h->dtype == MI355_DTYPE_FLOAT) SUB(1, true);  else SUB(1, false); }
@@ -1640,6 +1664,7 @@ int launch_mr_tile(mi355_fft *h, const void *in, void *out, int nframes, hipStre
                                                 h->shift, h->dtype == MI355_DTYPE_FLOAT, st);
         if (rc) return rc;
     }
+    set_route(&h->rt, kRtMrTile);
     return ws_release(h, st);
 }
 
@@ -1669,11 +1694,14 @@ unsigned *claim_words(mi355_fft *h, hipStream_t st)
 int launch_handle(mi355_fft *h, const void *in, void *out, int nvec, hipStream_t st)
 {
     if (h->mrt.n) return launch_mr_tile(h, in, out, nvec, st);
-    if (h->mr.n) return mi355_fft_mr_launch(h->mr, h->ctx, h->sign, in, out, h->d_window, nvec, h->shift, h->dtype == MI355_DTYPE_FLOAT, st);
+    if (h->mr.n) {
+        set_route(&h->rt, kRtMr);
+        return mi355_fft_mr_launch(h->mr, h->ctx, h->sign, in, out, h->d_window, nvec, h->shift, h->dtype == MI355_DTYPE_FLOAT, st);
+    }
     if (h->m) return launch_bluestein(h, in, out, nvec, st);
     if (h->n > 32768 || (h->n == 32768 && h->two_kernel)) return launch_big(h, in, out, nvec, st);
     return launch_fft(h->ctx, h->n, h->sign, in, out, h->d_window, h->d_tw, nvec, h->shift, h->dtype == MI355_DTYPE_FLOAT, st,
-                      claim_words(h, st));
+                      claim_words(h, st), &h->rt);
 }
 
 // iterative radix-2 FFT in double (host side, used once per handle for the chirp spectrum)
@@ -1975,6 +2003,57 @@ extern "C" int mi355_fft_plan_text(int fft_size, char *buf, int buf_len)
     while (m < 2 * fft_size - 1) m <<= 1;
     snprintf(buf, (size_t)buf_len, "chirp-z, m = %d%s", m, m <= 16384 ? " (fused)" : "");
     return MI355_OK;
+}
+
+namespace {
+int route_text(const FftRoute &r, char *t, size_t n)
+{
+    switch (r.kind) {
+    case kRtFft:
+        if (r.b == 1) return snprintf(t, n, "k_fft<%d> PF=1 %s grid=%d%s", r.a, r.c == 1 ? "dyn" : "static", r.d, r.wave ? " wave" : "");
+        return snprintf(t, n, "k_fft<%d> PF=%d%s", r.a, r.b, r.wave ? " wave" : "");
+    case kRtFftS: return snprintf(t, n, "k_fft_s<%d>", r.a);
+    case kRtFft32k: return snprintf(t, n, "k_fft_32k");
+    default: t[0] = 0; return 0;
+    }
+}
+}  // namespace
+
+extern "C" const char *mi355_fft_last_route(mi355_fft *h)
+{
+    if (!h) return "";
+    char *t = h->rt_text;
+    const size_t n = sizeof(h->rt_text);
+    const FftRoute r = h->rt;
+    int at = 0;
+    switch (r.kind) {
+    case kRtTile: snprintf(t, n, "k_fft_tile %dx%d", r.a, r.b); break;
+    case kRtSub:
+        if (r.b == 2) snprintf(t, n, "k_fft_sub+combine S=%d", r.a);
+        else if (r.b == 3) snprintf(t, n, "k_fft_sub+combine2 S=16x%d", r.a / 16);
+        else snprintf(t, n, "k_fft_sub+combine2 S=16x16x%d", r.a / 256);
+        break;
+    case kRtMr:
+        at = snprintf(t, n, "k_fft_mr ");
+        for (int p = 0; p < h->mr.npass && at < (int)n; p++) at += snprintf(t + at, n - (size_t)at, p ? "x%d" : "%d", h->mr.pass[p].radix);
+        if (at < (int)n) snprintf(t + at, n - (size_t)at, " threads=%d frames=%d", h->mr.threads, h->mr.frames);
+        break;
+    case kRtMrTile:
+        at = snprintf(t, n, "k_fft_mr_tile %d x %d (", h->mrt.n1, h->mrt.n2);
+        for (const MrPlan *pl : {&h->mrt.a, &h->mrt.b}) {
+            for (int p = 0; p < pl->npass && at < (int)n; p++) at += snprintf(t + at, n - (size_t)at, p ? "x%d" : "%d", pl->pass[p].radix);
+            if (at < (int)n) at += snprintf(t + at, n - (size_t)at, pl == &h->mrt.a ? ", " : ")");
+        }
+        break;
+    case kRtChirpz: snprintf(t, n, "k_chirpz<%d>", r.a); break;
+    case kRtBluestein:
+        at = snprintf(t, n, "bluestein m=%d: ", r.a);
+        if (h->sub_f) snprintf(t + at, n - (size_t)at, "%s", mi355_fft_last_route(h->sub_f));
+        else route_text(h->rt_sub, t + at, n - (size_t)at);
+        break;
+    default: route_text(r, t, n); break;
+    }
+    return t;
 }
 
 const MrPlan *mi355_fft_mr_plan_of(const mi355_fft *h, int *sign)

@@ -177,6 +177,18 @@ int mi355_fft_work(mi355_fft *h, int nvec, const void *const *in_streams, void *
  * stream for overlap.  Sizes: powers of two 2 .. 16777216, any other length 3 .. 8388608 (chirp-z); larger ones return
  * MI355_ERR_UNSUPPORTED. */
 int mi355_fft_work_dev(mi355_fft *h, int nvec, const void *in, void *out, void *stream);
+/* The kernels the last work / work_dev of this handle launched and the parameters that change the arithmetic or the schedule:
+ * "k_fft<64> PF=0", "k_fft<4096> PF=1 dyn grid=512" (persistent loop with the next group in flight; dyn / static: frame groups by claims
+ * or by the grid stride), "k_fft_s<8192>", "k_fft_32k", "k_fft_tile 256x512", "k_fft_sub+combine2 S=16x16x2" (2^21 points and more; the
+ * last factor is the radix of the last combine), "k_fft_mr 10x10x10 threads=256 frames=3", "k_fft_mr_tile 100 x 160 (10x10, 10x16)" (two passes and the radices inside either), "k_chirpz<8192>",
+ * "bluestein m=65536: k_fft_tile 256x256" (the unfused chirp-z path and the route of its size-m transforms).  "" before the first
+ * call.  Valid until the handle's next call; recorded without a lock, so with two streams on one handle it is either call's. */
+const char *mi355_fft_last_route(mi355_fft *h);
+/* Which input items an output depends on.  Output frame f (items [f N, (f + 1) N) of out) depends on input frame f alone, on every route
+ * and schedule, however many frames a workgroup holds and whichever workgroup picks the frame up.  A non-finite item in frame f
+ * makes every bin of frame f non-finite -- complex input with both components non-finite: both components of every bin; real
+ * input: at least one component of every bin (a bin whose twiddle is 1 or -1 keeps the imaginary part 0 + 0) -- and every other frame
+ * has the bits of the same call without it.  A frame of zeros comes out as zeros. */
 
 /* ---------------------------------------------------------------------------
  * clFilter / clComplexFilter: decimating FIR on a complex stream,

@@ -130,8 +130,17 @@ def fft_bound(n):
     return 3e-6 if m == 1 else TOL
 
 
+def fft_used(blk, got, n, fwd, w, shift, x):
+    """the largest used fraction of the per-bin and per-frame bounds of tests/fft_ref.py (bound 1.0), with the multiples of the route blk's last
+    call took; a zero frame that did not come out as zeros counts as inf (fft_bound_check returns that)"""
+    from fft_ref import fft_bound_check, fft_bound_kind, fft_frames64
+    x = np.asarray(x)
+    return max(fft_bound_check(got, fft_frames64(n, fwd, w, shift, x, not np.iscomplexobj(x)), n, fft_bound_kind(blk.last_route()), check=False))
+
+
 def run_fft(pkg, oracle, n, frames, mode, pick=None):
-    """device path, NaN-filled output; every frame (or the frames of `pick`) against numpy's float64 FFT: the largest relerr of a batch"""
+    """device path, NaN-filled output; every frame (or the frames of `pick`) against numpy's float64 FFT: the largest relerr of a batch,
+    and the largest used fraction of the per-bin and per-frame bounds (tests/fft_ref.py, the multiples of the route that ran; bound 1.0)"""
     import torch
     from fft_ref import np_fft_block as _np_fft_block
     fwd, shift, win, real = MODES[mode]
@@ -153,13 +162,15 @@ def run_fft(pkg, oracle, n, frames, mode, pick=None):
             j += 1
         runs.append((want[i], want[j] + 1))
         i = j + 1
-    errs = []
+    errs, used = [], []
     for f0, f1 in runs:
         xs = x[f0 * n * k:f1 * n * k].cpu().numpy()
-        ref = _np_fft_block(n, fwd, w, shift, xs if real else xs.view(np.complex64))
-        errs.append(relerr(y[f0 * n * 2:f1 * n * 2].cpu().numpy().view(np.complex64), ref))
+        xs = xs if real else xs.view(np.complex64)
+        got = y[f0 * n * 2:f1 * n * 2].cpu().numpy().view(np.complex64)
+        errs.append(relerr(got, _np_fft_block(n, fwd, w, shift, xs)))
+        used.append(fft_used(blk, got, n, fwd, w, shift, xs))
     blk.stop()
-    return float(np.max(np.array(errs)))
+    return float(np.max(np.array(errs))), float(np.max(np.array(used)))
 
 
 def fft_case(name, shapes, env=None, group=None, note=None, plan=None, switches=None, taken=True, modes=SMALL, pick=None, bound=fft_bound):
@@ -170,7 +181,9 @@ def fft_case(name, shapes, env=None, group=None, note=None, plan=None, switches=
         for n, fr in shapes:
             for m in modes:
                 m0 = len(LOG)
-                checks.append(("clFFT %d x %d %s" % (n, fr, m), run_fft(pkg, oracle, n, fr, m, pick and pick(fr)), bound(n)))
+                err, used = run_fft(pkg, oracle, n, fr, m, pick and pick(fr))
+                checks.append(("clFFT %d x %d %s" % (n, fr, m), err, bound(n)))
+                checks.append(("clFFT %d x %d %s: per-bin / per-frame bounds used" % (n, fr, m), used, 1.0))
                 if plan:
                     line = said("clFFT: %d points" % n, m0)
                     ok = line.endswith(": " + plan)
@@ -252,8 +265,10 @@ def _fft_sched(pkg, oracle):
     from fft_ref import np_fft_block as _np_fft_block
     f0 = frames - 64
     ref = _np_fft_block(n, True, None, True, x[f0 * n * 2:].cpu().numpy().view(np.complex64))
-    err = relerr(outs[1][f0 * n * 2:].cpu().numpy().view(np.complex64), ref)
-    return result(None, "", [("static stride, last 64 frames", err, 2e-6), ("claims == static stride", 0.0 if torch.equal(outs[0].view(torch.int32), outs[1].view(torch.int32)) else 1.0, 0.0)])
+    got = outs[1][f0 * n * 2:].cpu().numpy().view(np.complex64)
+    err = relerr(got, ref)
+    used = fft_used(blk, got, n, True, None, True, x[f0 * n * 2:].cpu().numpy().view(np.complex64))
+    return result(None, "", [("static stride, last 64 frames", err, 2e-6), ("static stride, last 64 frames: per-bin / per-frame bounds used", used, 1.0), ("claims == static stride", 0.0 if torch.equal(outs[0].view(torch.int32), outs[1].view(torch.int32)) else 1.0, 0.0)])
 
 
 add("fft_sched", _fft_sched, {"MI355_FFT_SCHED": "0"}, taken=None)
@@ -591,8 +606,10 @@ def _host_small(pkg, oracle):
     checks.append(("clMathOp multiply 8192", relerr(c, a.astype(np.complex128) * b.astype(np.complex128)), TOL))
     w = oracle.window(oracle.WIN_BLACKMAN_HARRIS, 1024)
     y = np.full(n, np.nan, np.complex64)
-    pkg.clFFT(1024, pkg.CLFFT_FORWARD, w, pkg.DTYPE_COMPLEX, *GPU_ARGS, 1, 1, True).work(8, [a], [y])
+    blk = pkg.clFFT(1024, pkg.CLFFT_FORWARD, w, pkg.DTYPE_COMPLEX, *GPU_ARGS, 1, 1, True)
+    blk.work(8, [a], [y])
     checks.append(("clFFT 1024 x 8", relerr(y, oracle.fft_block(1024, True, w, True, oracle.DTYPE_COMPLEX, a, f64=True)), 2e-6))
+    checks.append(("clFFT 1024 x 8: per-bin / per-frame bounds used", fft_used(blk, y, 1024, True, w, True, a), 1.0))
     taps = oracle.firdes_low_pass(1.0, 10e6, 1e6, 372000.0)
     xh = crandn(rng, n * 2 + taps.size - 1)
     yf = np.full(n, np.nan, np.complex64)
@@ -633,8 +650,10 @@ def _host_chunks(pkg, oracle):
     checks.append(("clFilter 129 taps decim 3 x 400000", relerr(yf, conv64(xh, taps)[nt - 1::d][:nout]), TOL))
     x = crandn(rng, 100 * 4096)
     y = np.full(x.size, np.nan, np.complex64)
-    pkg.clFFT(4096, pkg.CLFFT_FORWARD, [], pkg.DTYPE_COMPLEX, *GPU_ARGS, 1, 1, False).work(100, [x], [y])
+    blk = pkg.clFFT(4096, pkg.CLFFT_FORWARD, [], pkg.DTYPE_COMPLEX, *GPU_ARGS, 1, 1, False)
+    blk.work(100, [x], [y])
     checks.append(("clFFT 4096 x 100", relerr(y, oracle.fft_block(4096, True, None, False, oracle.DTYPE_COMPLEX, x, f64=True)), 2e-6))
+    checks.append(("clFFT 4096 x 100: per-bin / per-frame bounds used", fft_used(blk, y, 4096, True, None, False, x), 1.0))
     ev = [noted(k) for k in ("MI355_CHUNK_MB", "MI355_COPY_STREAM", "MI355_COPY_THREADS")]
     return result(all(e is not None for e in ev), " | ".join(str(e) for e in ev), checks)
 

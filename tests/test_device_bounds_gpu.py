@@ -22,6 +22,7 @@ import pytest
 import torch
 
 from conftest import GPU_ARGS, crandn, relerr
+from fft_ref import fft_bound_check, fft_bound_kind, fft_frames64
 from guarded import SENTINEL, GuardError, check_guards, guarded_input, guarded_output, pad_items, to_numpy
 from test_fft_gpu import _np_fft_block
 from test_fft_sched_gpu import _frames
@@ -156,8 +157,8 @@ _REF_CACHE = {}
 
 
 def _fft_data(oracle, n, frames, mode, sampled):
-    """input, window and reference of a case; kept for the next case when only a per-call switch differs (the persistent-sized calls
-    are 128 MiB each way)"""
+    """input, window, reference and unrounded float64 reference (fft_ref.fft_frames64, for the per-frame bounds) of a case; kept for the
+    next case when only a per-call switch differs (the persistent-sized calls are 128 MiB each way)"""
     key = (n, frames, mode)
     if key not in _REF_CACHE:
         _REF_CACHE.clear()
@@ -167,9 +168,11 @@ def _fft_data(oracle, n, frames, mode, sampled):
         w = oracle.window(oracle.WIN_BLACKMAN_HARRIS, n) if win else None
         if sampled:  # (the oracle's DFT of a length that is not a power of two is O(n^2): first, middle and last frames, as the route's own test does)
             ref = {f0: _fft_ref(oracle, n, fwd, w, shift, x[f0 * n:(f0 + 3) * n], real) for f0 in (0, frames // 2, frames - 3)}
+            ref64 = {f0: fft_frames64(n, fwd, w, shift, x[f0 * n:(f0 + 3) * n], real) for f0 in ref}
         else:
             ref = _fft_ref(oracle, n, fwd, w, shift, x, real)
-        _REF_CACHE[key] = (x, w, ref)
+            ref64 = fft_frames64(n, fwd, w, shift, x, real)
+        _REF_CACHE[key] = (x, w, ref, ref64)
     return _REF_CACHE[key]
 
 
@@ -185,7 +188,7 @@ def test_clfft_stays_inside_its_buffers(gpu, oracle, monkeypatch, route, n, fram
     if route == "chirpz_fused":
         assert 2 * n - 1 <= 16384
     _setenv(monkeypatch, env)
-    x, w, ref = _fft_data(oracle, n, frames, mode, sampled=frames > 10000 and n == 1000)
+    x, w, ref, ref64 = _fft_data(oracle, n, frames, mode, sampled=frames > 10000 and n == 1000)
     blk = gpu.clFFT(n, gpu.CLFFT_FORWARD if fwd else gpu.CLFFT_BACKWARD, [] if w is None else w, gpu.DTYPE_FLOAT if real else gpu.DTYPE_COMPLEX,
                     *GPU_ARGS, 0, 1, shift)
     # the input of a length above 4096 that is not a chirp-z length must be 16-byte aligned (its refusal: test_refusals); a float
@@ -194,13 +197,16 @@ def test_clfft_stays_inside_its_buffers(gpu, oracle, monkeypatch, route, n, fram
     offsets = [(oi * step, oo) for oi, oo in ALL4 if oi == 0 or chirpz or n <= 4096]
 
     def check(outs):
+        kind = fft_bound_kind(blk.last_route())  # every frame inside the per-bin and per-frame bounds of the route that ran
         if isinstance(ref, dict):
             for f0, r in ref.items():
                 assert relerr(outs[0][f0 * n:(f0 + 3) * n], r) <= TOL, f0
+                fft_bound_check(outs[0][f0 * n:(f0 + 3) * n], ref64[f0], n, kind, what=blk.last_route())
         else:
             err = relerr(outs[0], ref)
             print("relerr %.3g" % err)
             assert err <= TOL
+            print("bounds used %.3f (bin) %.3f (rss)" % fft_bound_check(outs[0], ref64, n, kind, what=blk.last_route()))
 
     _run_offsets(lambda i, o: blk.work_device(frames, i, o), [(x, n)], [(frames * n, np.complex64, n)], offsets, check,
                  bitwise=route.startswith(("one_pass", "persistent", "mixed_radix_one_pass")))

@@ -99,6 +99,9 @@ def test_dynamic_matches_numpy(gpu):
     got = y.view(frames, n, 2).cpu().numpy()[idx]
     got = got[..., 0] + 1j * got[..., 1]
     assert np.abs(got - ref).max() <= 1e-5 * np.abs(ref).max()
+    from fft_ref import fft_bound_check, fft_bound_kind
+    assert blk.last_route() == "k_fft<4096> PF=1 dyn grid=%d" % (2 * _cus())
+    fft_bound_check(got.astype(np.complex64), ref, n, fft_bound_kind(blk.last_route()))
 
 
 @pytest.mark.parametrize("n,default", [(4096, "1"), (1024, "0")])
