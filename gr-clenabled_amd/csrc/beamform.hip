@@ -556,17 +556,12 @@ extern "C" int mi355_beamform_work(mi355_beamform *h, long long nunits, const vo
     const size_t in_cap = piece * unit_in;
     rc = h->pipe.ensure(1, &in_cap, piece * unit_out, 1);
     if (rc) return rc;
-    HostPipe &p = h->pipe;
-    hipStream_t st = h->ctx->stream[0];
-    for (size_t off = 0; off < (size_t)nunits; off += piece) {
-        const size_t m = (size_t)nunits - off < piece ? (size_t)nunits - off : piece;
-        mi355_copy(p.h_in[0][0], (const char *)in + off * unit_in, m * unit_in);
-        MI355_HIP(hipMemcpyAsync(p.d_in[0][0], p.h_in[0][0], m * unit_in, hipMemcpyHostToDevice, st));
-        rc = bf_launch(h, (long long)m, p.d_in[0][0], p.d_out[0], st);
-        if (rc) return rc;
-        MI355_HIP(hipMemcpyAsync(p.h_out[0], p.d_out[0], m * unit_out, hipMemcpyDeviceToHost, st));
-        MI355_HIP(hipStreamSynchronize(st));
-        mi355_copy((char *)out + off * unit_out, p.h_out[0], m * unit_out);
-    }
-    return MI355_OK;
+    const HostPipe::Plan plan{1, true, false};  // one slot, stream[0], never direct
+    auto units = [&](size_t ci) { return HostPipe::part((size_t)nunits, piece, ci); };
+    return h->pipe.run(
+        ((size_t)nunits + piece - 1) / piece, plan,
+        [&](size_t ci) {
+            return HostPipe::Chunk{{(const char *)in + ci * piece * unit_in}, {units(ci) * unit_in}, (char *)out + ci * piece * unit_out, units(ci) * unit_out};
+        },
+        [&](size_t ci, void *const *d_in, void *d_out, hipStream_t st) { return bf_launch(h, (long long)units(ci), d_in[0], d_out, st); });
 }

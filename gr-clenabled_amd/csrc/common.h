@@ -9,6 +9,7 @@
 #include <chrono>
 #include <mutex>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "mi355_clenabled.h"
@@ -138,10 +139,9 @@ static inline int mi355_balanced_grid(const mi355_ctx *ctx, long long units, int
 }
 
 // ---------------------------------------------------------------------------
-// Pinned double-buffered staging for the host-pointer work() path.
-// Two slots; slot s runs H2D -> kernel -> D2H on ctx->stream[s], so the copy-in
-// of chunk c+1 overlaps the kernel / copy-out of chunk c (north_star: "pinned
-// double-buffered H2D/D2H overlapping compute on HIP streams").
+// Pinned staging for the host-pointer work() path (HostPipe below): slot s runs H2D -> kernel -> D2H on
+// ctx->stream[s & 1], so the copy-in of chunk c+1 overlaps the kernel / copy-out of chunk c (north_star:
+// "pinned double-buffered H2D/D2H overlapping compute on HIP streams").
 // ---------------------------------------------------------------------------
 // Host calls whose buffers are at most this large (a scheduler-sized work() call) skip the H2D / D2H copy submissions: the
 // kernel reads and writes the pinned staging buffers across PCIe itself -- one launch and one synchronisation per call
@@ -206,4 +206,98 @@ struct HostPipe {
     int ensure(int nin, const size_t *in_bytes, size_t out_bytes, int nslots = kSlots);
     int slots_ready = 0;
     void release();
+
+    // One chunk of a host call as its block describes it: where the caller's inputs lie (in_bytes 0 = no such input) and where the
+    // output goes.  out_bytes 0 = nothing comes back for this chunk; `dst` is not read when run() is given a deliver callback.
+    struct Chunk {
+        const void *src[MAXIN] = {};
+        size_t in_bytes[MAXIN] = {};
+        void *dst = nullptr;
+        size_t out_bytes = 0;
+    };
+    // units in part i of `total` units cut `per` at a time (the last part is the ragged one)
+    static size_t part(size_t total, size_t per, size_t i) { return total - i * per < per ? total - i * per : per; }
+    struct Plan {
+        int nslots = kSlots;      // 1: the chunks run strictly one after the other
+        bool one_stream = false;  // every chunk on ctx->stream[0] (kernels that share work buffers)
+        bool direct = false;      // the kernel works on the pinned staging itself (mi355_direct_ok, decided by the block)
+    };
+    // The host-pointer work() of a block: chunks 0 .. nchunks-1 through the staging slots, chunk i in slot i % nslots.  The block has
+    // called ensure() for its largest chunk and holds its locks; the device is set.
+    //   describe(i) -> Chunk
+    //   launch(i, void *const *in, void *out, hipStream_t) -> MI355_* code; `in` / `out` are the slot's device buffers (direct: pinned)
+    //   deliver(i, const void *pinned_out): for a block whose output is not one contiguous copy; nullptr = copy to Chunk::dst
+    // Per chunk: wait for the slot if it is busy, its previous result out beside its next input in (mi355_copy2), H2D per input,
+    // launch, D2H, event record.  On any failure the slots in flight are waited for before the code is returned, so no DMA or
+    // kernel outlives the call on this staging, and nothing more is delivered.
+    template <class Describe, class Launch, class Deliver = std::nullptr_t>
+    int run(size_t nchunks, const Plan &plan, Describe &&describe, Launch &&launch, Deliver &&deliver = nullptr);
 };
+
+template <class Describe, class Launch, class Deliver>
+int HostPipe::run(size_t nchunks, const Plan &plan, Describe &&describe, Launch &&launch, Deliver &&deliver)
+{
+    constexpr bool custom = !std::is_same<typename std::decay<Deliver>::type, std::nullptr_t>::value;
+    auto copy_out = [&](size_t ci, void *dst, const void *pinned, size_t bytes) {
+        if (bytes == 0) return;
+        if constexpr (custom) deliver(ci, pinned);
+        else mi355_copy(dst, pinned, bytes);
+    };
+    hipStream_t st = ctx->stream[0];
+    struct { bool busy; size_t ci; void *dst; size_t bytes; } pend[kSlots] = {};
+    const int nslots = plan.nslots < 1 ? 1 : plan.nslots > kSlots ? kSlots : plan.nslots;
+    // With one slot nothing else is queued on the stream, so the stream itself is waited for and no event is recorded: the record
+    // and the wait for its marker behind the D2H cost a one-transfer call (the channelizer's 80 us) about 9 us.
+    const bool events = nslots > 1;
+    auto wait = [&](int s) { return events ? hipEventSynchronize(done[s]) : hipStreamSynchronize(ctx->stream[0]); };
+    const int rc = [&]() -> int {
+        if (plan.direct) {
+            for (size_t ci = 0; ci < nchunks; ci++) {
+                const Chunk c = describe(ci);
+                for (int i = 0; i < MAXIN; i++)
+                    if (c.in_bytes[i]) mi355_copy(h_in[0][i], c.src[i], c.in_bytes[i]);
+                const int lrc = launch(ci, h_in[0], h_out[0], st);
+                if (lrc) return lrc;
+                MI355_HIP(mi355_direct_sync(st));
+                copy_out(ci, c.dst, h_out[0], c.out_bytes);
+            }
+            return MI355_OK;
+        }
+        for (size_t ci = 0; ci < nchunks; ci++) {
+            const int s = (int)(ci % nslots);
+            st = ctx->stream[plan.one_stream ? 0 : (s & 1)];
+            if (pend[s].busy) MI355_HIP(wait(s));  // slot busy with chunk ci - nslots: drain it
+            const Chunk c = describe(ci);
+            const auto was = pend[s];
+            pend[s] = {};
+            // the slot's previous result out and its next input in, side by side
+            if constexpr (custom) {
+                copy_out(was.ci, nullptr, h_out[s], was.bytes);
+                mi355_copy(h_in[s][0], c.src[0], c.in_bytes[0]);
+            } else mi355_copy2(was.dst, h_out[s], was.bytes, h_in[s][0], c.src[0], c.in_bytes[0]);
+            if (c.in_bytes[1]) mi355_copy(h_in[s][1], c.src[1], c.in_bytes[1]);
+            for (int i = 0; i < MAXIN; i++)
+                if (c.in_bytes[i]) MI355_HIP(hipMemcpyAsync(d_in[s][i], h_in[s][i], c.in_bytes[i], hipMemcpyHostToDevice, st));
+            const int lrc = launch(ci, d_in[s], d_out[s], st);
+            if (lrc) return lrc;
+            if (c.out_bytes) MI355_HIP(hipMemcpyAsync(h_out[s], d_out[s], c.out_bytes, hipMemcpyDeviceToHost, st));
+            if (events) MI355_HIP(hipEventRecord(done[s], st));
+            pend[s] = {true, ci, c.dst, c.out_bytes};
+        }
+        for (int q = 0; q < nslots; q++) {
+            const int s = (int)((nchunks + q) % nslots);  // oldest slot first
+            if (!pend[s].busy) continue;
+            MI355_HIP(wait(s));
+            pend[s].busy = false;
+            copy_out(pend[s].ci, pend[s].dst, h_out[s], pend[s].bytes);
+        }
+        return MI355_OK;
+    }();
+    if (rc != MI355_OK) {
+        // what the slots still hold is waited for, then what the failed chunk itself had queued on its stream
+        for (int s = 0; s < nslots; s++)
+            if (pend[s].busy) (void)wait(s);
+        (void)hipStreamSynchronize(st);
+    }
+    return rc;
+}

@@ -449,22 +449,21 @@ extern "C" int mi355_dedisp_work(mi355_dedisp *h, long long n, const void *in, v
     const size_t in_cap = (piece + h->H) * per_in;
     rc = h->pipe.ensure(1, &in_cap, piece * per_out, 1);
     if (rc) return rc;
-    HostPipe &p = h->pipe;
-    hipStream_t st = h->ctx->stream[0];
-    for (size_t off = 0; off < (size_t)n; off += piece) {
-        const size_t m = (size_t)n - off < piece ? (size_t)n - off : piece;
-        mi355_copy(p.h_in[0][0], (const char *)in + off * per_in, (m + h->H) * per_in);
-        MI355_HIP(hipMemcpyAsync(p.d_in[0][0], p.h_in[0][0], (m + h->H) * per_in, hipMemcpyHostToDevice, st));
-        rc = dd_launch(h, (long long)m, p.d_in[0][0], p.d_out[0], h->order == MI355_DEDISP_TIME_MAJOR ? 0 : (long long)m, st);
-        if (rc) return rc;
-        MI355_HIP(hipMemcpyAsync(p.h_out[0], p.d_out[0], m * per_out, hipMemcpyDeviceToHost, st));
-        MI355_HIP(hipStreamSynchronize(st));
-        if (h->order == MI355_DEDISP_TIME_MAJOR) mi355_copy((char *)out + off * per_out, p.h_out[0], m * per_out);
-        else
-            for (size_t i = 0; i < rd; i++)
-                memcpy((float *)out + i * (size_t)out_pitch + off, (const float *)p.h_out[0] + i * m, m * 4);
-    }
-    return MI355_OK;
+    const HostPipe::Plan plan{1, true, false};  // one slot, stream[0], never direct
+    const bool time_major = h->order == MI355_DEDISP_TIME_MAJOR;
+    auto samples = [&](size_t ci) { return HostPipe::part((size_t)n, piece, ci); };
+    return h->pipe.run(
+        ((size_t)n + piece - 1) / piece, plan,
+        [&](size_t ci) { return HostPipe::Chunk{{(const char *)in + ci * piece * per_in}, {(samples(ci) + h->H) * per_in}, nullptr, samples(ci) * per_out}; },
+        [&](size_t ci, void *const *d_in, void *d_out, hipStream_t st) {
+            return dd_launch(h, (long long)samples(ci), d_in[0], d_out, time_major ? 0 : (long long)samples(ci), st);
+        },
+        [&](size_t ci, const void *h_out) {
+            const size_t off = ci * piece, m = samples(ci);
+            if (time_major) mi355_copy((char *)out + off * per_out, h_out, m * per_out);
+            else  // channel-major: row i of the piece goes to its place in the caller's row
+                for (size_t i = 0; i < rd; i++) memcpy((float *)out + i * (size_t)out_pitch + off, (const float *)h_out + i * m, m * 4);
+        });
 }
 
 // host only: delay[d][f] = llrint(4.148808e3 dm[d] (nu_f^-2 - nu_ref^-2) / tsamp), nu^-2 = 1 / (nu nu), every operation rounded on its own

@@ -2101,6 +2101,7 @@ extern "C" int mi355_fft_work(mi355_fft *h, int nvec, const void *const *in_stre
     MI355_REQUIRE(h != nullptr, "handle is NULL");
     if (nvec <= 0) return MI355_OK;
     MI355_REQUIRE(in_streams && out_streams, "NULL stream arrays");
+    for (int s_i = 0; s_i < h->nstreams; s_i++) MI355_REQUIRE(in_streams[s_i] && out_streams[s_i], "NULL stream buffer");
     std::lock_guard<std::mutex> g(h->ctx->lock);
     MI355_HIP(hipSetDevice(h->ctx->device));
     const size_t isz = mi355_dtype_size(h->dtype), in_frame = isz * (size_t)h->n, out_frame = 8 * (size_t)h->n;
@@ -2111,55 +2112,18 @@ extern "C" int mi355_fft_work(mi355_fft *h, int nvec, const void *const *in_stre
     const int nslots = first * out_frame >= ((size_t)32 << 20) ? 2 : HostPipe::kSlots;  // (a 2^22-point frame is 32 MiB: two staging slots)
     int rc = h->pipe.ensure(1, &inb, first * out_frame, nslots);
     if (rc) return rc;
-    HostPipe &p = h->pipe;
-    if ((size_t)nvec <= chunk_frames && mi355_direct_ok((size_t)nvec * out_frame, h->ctx)) {
-        // small call: the kernels work on the pinned staging themselves (see common.h); streams one after the other
-        hipStream_t st = h->ctx->stream[0];
-        for (int s_i = 0; s_i < h->nstreams; s_i++) {
-            MI355_REQUIRE(in_streams[s_i] && out_streams[s_i], "NULL stream buffer");
-            mi355_copy(p.h_in[0][0], in_streams[s_i], (size_t)nvec * in_frame);
-            rc = launch_handle(h, p.h_in[0][0], p.h_out[0], nvec, st);
-            if (rc) return rc;
-            MI355_HIP(mi355_direct_sync(st));
-            mi355_copy(out_streams[s_i], p.h_out[0], (size_t)nvec * out_frame);
-        }
-        return MI355_OK;
-    }
-    // all (stream, chunk) pairs run through the staging slots back to back
-    size_t nchunks = ((size_t)nvec + chunk_frames - 1) / chunk_frames;
-    char *pend_dst[HostPipe::kSlots] = {};
-    size_t pend_bytes[HostPipe::kSlots] = {};
-    size_t seq = 0;
+    // all (stream, chunk) pairs run through the staging slots back to back; a small call is one chunk per stream on the direct path,
+    // the kernels working on the pinned staging themselves (see common.h)
+    const size_t nchunks = ((size_t)nvec + chunk_frames - 1) / chunk_frames;
     const bool one_stream = h->m || h->mrt.n || h->n > 32768 || (h->n == 32768 && h->two_kernel);  // chirp-z / multi-pass sizes share work buffers: one stream
-    for (int s_i = 0; s_i < h->nstreams; s_i++) {
-        MI355_REQUIRE(in_streams[s_i] && out_streams[s_i], "NULL stream buffer");
-        const char *pin = (const char *)in_streams[s_i];
-        char *pout = (char *)out_streams[s_i];
-        for (size_t ci = 0; ci < nchunks; ci++, seq++) {
-            int s = (int)(seq % nslots);
-            hipStream_t st = h->ctx->stream[one_stream ? 0 : (s & 1)];
-            size_t f0 = ci * chunk_frames;
-            size_t nf = (size_t)nvec - f0 < chunk_frames ? (size_t)nvec - f0 : chunk_frames;
-            if (pend_bytes[s]) MI355_HIP(hipEventSynchronize(p.done[s]));
-            // the slot's previous result out and its next input in, side by side
-            mi355_copy2(pend_dst[s], p.h_out[s], pend_bytes[s], p.h_in[s][0], pin + f0 * in_frame, nf * in_frame);
-            pend_bytes[s] = 0;
-            MI355_HIP(hipMemcpyAsync(p.d_in[s][0], p.h_in[s][0], nf * in_frame, hipMemcpyHostToDevice, st));
-            rc = launch_handle(h, p.d_in[s][0], p.d_out[s], (int)nf, st);
-            if (rc) return rc;
-            MI355_HIP(hipMemcpyAsync(p.h_out[s], p.d_out[s], nf * out_frame, hipMemcpyDeviceToHost, st));
-            MI355_HIP(hipEventRecord(p.done[s], st));
-            pend_dst[s] = pout + f0 * out_frame;
-            pend_bytes[s] = nf * out_frame;
-        }
-    }
-    for (int q = 0; q < nslots; q++) {
-        int s = (int)((seq + q) % nslots);  // oldest slot first
-        if (pend_bytes[s]) {
-            MI355_HIP(hipEventSynchronize(p.done[s]));
-            mi355_copy(pend_dst[s], p.h_out[s], pend_bytes[s]);
-            pend_bytes[s] = 0;
-        }
-    }
-    return MI355_OK;
+    const HostPipe::Plan plan{nslots, one_stream, (size_t)nvec <= chunk_frames && mi355_direct_ok((size_t)nvec * out_frame, h->ctx)};
+    auto frames = [&](size_t i) { return HostPipe::part((size_t)nvec, chunk_frames, i % nchunks); };
+    return h->pipe.run(
+        (size_t)h->nstreams * nchunks, plan,
+        [&](size_t i) {
+            const size_t f0 = i % nchunks * chunk_frames, nf = frames(i);
+            return HostPipe::Chunk{{(const char *)in_streams[i / nchunks] + f0 * in_frame}, {nf * in_frame},
+                                   (char *)out_streams[i / nchunks] + f0 * out_frame, nf * out_frame};
+        },
+        [&](size_t i, void *const *d_in, void *d_out, hipStream_t st) { return launch_handle(h, d_in[0], d_out, (int)frames(i), st); });
 }

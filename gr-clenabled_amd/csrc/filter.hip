@@ -1478,44 +1478,14 @@ extern "C" int mi355_filter_work(mi355_filter *h, size_t noutput_items, const vo
     size_t inb = (first * h->decim + hist) * 8;
     int rc = h->pipe.ensure(1, &inb, first * 8);
     if (rc) return rc;
-    HostPipe &p = h->pipe;
-    const char *pin = (const char *)in;
-    char *pout = (char *)out;
-    if (noutput_items <= chunk_out && mi355_direct_ok(inb, h->ctx)) {  // small call: the kernel works on the pinned staging itself
-        hipStream_t st = h->ctx->stream[0];
-        mi355_copy(p.h_in[0][0], pin, inb);
-        rc = launch_filter(h, noutput_items, p.h_in[0][0], p.h_out[0], st);
-        if (rc) return rc;
-        MI355_HIP(mi355_direct_sync(st));
-        mi355_copy(pout, p.h_out[0], noutput_items * 8);
-        return MI355_OK;
-    }
-    size_t nchunks = (noutput_items + chunk_out - 1) / chunk_out;
-    size_t pend_off[HostPipe::kSlots] = {}, pend_bytes[HostPipe::kSlots] = {};
-    for (size_t ci = 0; ci < nchunks; ci++) {
-        int s = (int)(ci % HostPipe::kSlots);
-        hipStream_t st = h->ctx->stream[s & 1];
-        if (pend_bytes[s]) MI355_HIP(hipEventSynchronize(p.done[s]));
-        size_t o0 = ci * chunk_out;
-        size_t no = noutput_items - o0 < chunk_out ? noutput_items - o0 : chunk_out;
-        size_t in_bytes = (no * h->decim + hist) * 8;
-        // the slot's previous result out and its next input in, side by side
-        mi355_copy2(pout + pend_off[s], p.h_out[s], pend_bytes[s], p.h_in[s][0], pin + o0 * h->decim * 8, in_bytes);
-        pend_bytes[s] = 0;
-        MI355_HIP(hipMemcpyAsync(p.d_in[s][0], p.h_in[s][0], in_bytes, hipMemcpyHostToDevice, st));
-        rc = launch_filter(h, no, p.d_in[s][0], p.d_out[s], st);
-        if (rc) return rc;
-        MI355_HIP(hipMemcpyAsync(p.h_out[s], p.d_out[s], no * 8, hipMemcpyDeviceToHost, st));
-        MI355_HIP(hipEventRecord(p.done[s], st));
-        pend_off[s] = o0 * 8; pend_bytes[s] = no * 8;
-    }
-    for (int q = 0; q < HostPipe::kSlots; q++) {
-        int s = (int)((nchunks + q) % HostPipe::kSlots);  // oldest slot first
-        if (pend_bytes[s]) {
-            MI355_HIP(hipEventSynchronize(p.done[s]));
-            mi355_copy(pout + pend_off[s], p.h_out[s], pend_bytes[s]);
-            pend_bytes[s] = 0;
-        }
-    }
-    return MI355_OK;
+    // small call: the kernel works on the pinned staging itself
+    const HostPipe::Plan plan{HostPipe::kSlots, false, noutput_items <= chunk_out && mi355_direct_ok(inb, h->ctx)};
+    auto outputs = [&](size_t ci) { return HostPipe::part(noutput_items, chunk_out, ci); };
+    return h->pipe.run(
+        (noutput_items + chunk_out - 1) / chunk_out, plan,
+        [&](size_t ci) {
+            const size_t o0 = ci * chunk_out, no = outputs(ci);
+            return HostPipe::Chunk{{(const char *)in + o0 * h->decim * 8}, {(no * h->decim + hist) * 8}, (char *)out + o0 * 8, no * 8};
+        },
+        [&](size_t ci, void *const *d_in, void *d_out, hipStream_t st) { return launch_filter(h, outputs(ci), d_in[0], d_out, st); });
 }

@@ -305,51 +305,17 @@ extern "C" int mi355_mathop_work(mi355_mathop *h, size_t nitems, const void *a, 
     size_t inb[2] = {first * h->isize, first * h->isize};
     int rc = h->pipe.ensure(2, inb, first * h->isize);
     if (rc) return rc;
-    HostPipe &p = h->pipe;
-    const char *pa = (const char *)a, *pb = (const char *)b;
-    char *pc = (char *)c;
-    if (mi355_direct_ok(nitems * h->isize, h->ctx)) {
-        // Small call (a scheduler-sized buffer): the kernel reads and writes the pinned staging buffers across PCIe
-        // itself.  One launch + one synchronisation instead of three copy submissions + a launch + a synchronisation.
-        const size_t bytes = nitems * h->isize;
-        hipStream_t st = h->ctx->stream[0];
-        mi355_copy(p.h_in[0][0], pa, bytes);
-        mi355_copy(p.h_in[0][1], pb, bytes);
-        rc = dispatch2(h, nitems, p.h_in[0][0], p.h_in[0][1], p.h_out[0], st);
-        if (rc) return rc;
-        MI355_HIP(mi355_direct_sync(st));
-        mi355_copy(pc, p.h_out[0], bytes);
-        return MI355_OK;
-    }
-    size_t nchunks = (nitems + chunk_items - 1) / chunk_items;
-    size_t pend_off[HostPipe::kSlots] = {}, pend_bytes[HostPipe::kSlots] = {};
-    for (size_t ci = 0; ci < nchunks; ci++) {
-        int s = (int)(ci % HostPipe::kSlots);
-        hipStream_t st = h->ctx->stream[s & 1];
-        if (pend_bytes[s]) MI355_HIP(hipEventSynchronize(p.done[s]));  // slot busy with chunk ci - kSlots: drain it
-        size_t off_items = ci * chunk_items;
-        size_t n = nitems - off_items < chunk_items ? nitems - off_items : chunk_items;
-        size_t bytes = n * h->isize, off = off_items * h->isize;
-        mi355_copy2(pc + pend_off[s], p.h_out[s], pend_bytes[s], p.h_in[s][0], pa + off, bytes);  // previous result out, next input in, side by side
-        pend_bytes[s] = 0;
-        mi355_copy(p.h_in[s][1], pb + off, bytes);
-        MI355_HIP(hipMemcpyAsync(p.d_in[s][0], p.h_in[s][0], bytes, hipMemcpyHostToDevice, st));
-        MI355_HIP(hipMemcpyAsync(p.d_in[s][1], p.h_in[s][1], bytes, hipMemcpyHostToDevice, st));
-        rc = dispatch2(h, n, p.d_in[s][0], p.d_in[s][1], p.d_out[s], st);
-        if (rc) return rc;
-        MI355_HIP(hipMemcpyAsync(p.h_out[s], p.d_out[s], bytes, hipMemcpyDeviceToHost, st));
-        MI355_HIP(hipEventRecord(p.done[s], st));
-        pend_off[s] = off; pend_bytes[s] = bytes;
-    }
-    for (int q = 0; q < HostPipe::kSlots; q++) {
-        int s = (int)((nchunks + q) % HostPipe::kSlots);  // oldest slot first
-        if (pend_bytes[s]) {
-            MI355_HIP(hipEventSynchronize(p.done[s]));
-            mi355_copy(pc + pend_off[s], p.h_out[s], pend_bytes[s]);
-            pend_bytes[s] = 0;
-        }
-    }
-    return MI355_OK;
+    // a small call (a scheduler-sized buffer) is one chunk on the direct path: the kernel reads and writes the pinned staging buffers
+    // across PCIe itself, one launch + one synchronisation instead of three copy submissions + a launch + a synchronisation
+    const HostPipe::Plan plan{HostPipe::kSlots, false, mi355_direct_ok(nitems * h->isize, h->ctx)};
+    auto items = [&](size_t ci) { return HostPipe::part(nitems, chunk_items, ci); };
+    return h->pipe.run(
+        (nitems + chunk_items - 1) / chunk_items, plan,
+        [&](size_t ci) {
+            const size_t off = ci * chunk_items * h->isize, bytes = items(ci) * h->isize;
+            return HostPipe::Chunk{{(const char *)a + off, (const char *)b + off}, {bytes, bytes}, (char *)c + off, bytes};
+        },
+        [&](size_t ci, void *const *in, void *out, hipStream_t st) { return dispatch2(h, items(ci), in[0], in[1], out, st); });
 }
 
 // ---------------------------------------------------------------------------
@@ -423,45 +389,15 @@ extern "C" int mi355_mathconst_work(mi355_mathconst *h, size_t nitems, const voi
     size_t inb = first * h->isize;
     int rc = h->pipe.ensure(1, &inb, inb);
     if (rc) return rc;
-    HostPipe &p = h->pipe;
-    const char *pa = (const char *)a;
-    char *pc = (char *)c;
-    if (mi355_direct_ok(nitems * h->isize, h->ctx)) {  // small call: the kernel works on the pinned staging itself (see common.h)
-        const size_t bytes = nitems * h->isize;
-        hipStream_t st = h->ctx->stream[0];
-        mi355_copy(p.h_in[0][0], pa, bytes);
-        rc = dispatch1(h, nitems, p.h_in[0][0], p.h_out[0], k, st);
-        if (rc) return rc;
-        MI355_HIP(mi355_direct_sync(st));
-        if (h->op != MI355_OP_EMPTY) mi355_copy(pc, p.h_out[0], bytes);
-        return MI355_OK;
-    }
-    size_t nchunks = (nitems + chunk_items - 1) / chunk_items;
-    size_t pend_off[HostPipe::kSlots] = {}, pend_bytes[HostPipe::kSlots] = {};
-    for (size_t ci = 0; ci < nchunks; ci++) {
-        int s = (int)(ci % HostPipe::kSlots);
-        hipStream_t st = h->ctx->stream[s & 1];
-        if (pend_bytes[s]) MI355_HIP(hipEventSynchronize(p.done[s]));
-        size_t off_items = ci * chunk_items;
-        size_t n = nitems - off_items < chunk_items ? nitems - off_items : chunk_items;
-        size_t bytes = n * h->isize, off = off_items * h->isize;
-        // previous result out (nothing to deliver for MATHOP_EMPTY), next input in, side by side
-        mi355_copy2(pc + pend_off[s], p.h_out[s], h->op != MI355_OP_EMPTY ? pend_bytes[s] : 0, p.h_in[s][0], pa + off, bytes);
-        pend_bytes[s] = 0;
-        MI355_HIP(hipMemcpyAsync(p.d_in[s][0], p.h_in[s][0], bytes, hipMemcpyHostToDevice, st));
-        rc = dispatch1(h, n, p.d_in[s][0], p.d_out[s], k, st);
-        if (rc) return rc;
-        MI355_HIP(hipMemcpyAsync(p.h_out[s], p.d_out[s], bytes, hipMemcpyDeviceToHost, st));
-        MI355_HIP(hipEventRecord(p.done[s], st));
-        pend_off[s] = off; pend_bytes[s] = bytes;
-    }
-    for (int q = 0; q < HostPipe::kSlots; q++) {
-        int s = (int)((nchunks + q) % HostPipe::kSlots);  // oldest slot first
-        if (pend_bytes[s]) {
-            MI355_HIP(hipEventSynchronize(p.done[s]));
-            if (h->op != MI355_OP_EMPTY) mi355_copy(pc + pend_off[s], p.h_out[s], pend_bytes[s]);
-            pend_bytes[s] = 0;
-        }
-    }
-    return MI355_OK;
+    // small call: the kernel works on the pinned staging itself (see common.h)
+    const HostPipe::Plan plan{HostPipe::kSlots, false, mi355_direct_ok(nitems * h->isize, h->ctx)};
+    auto items = [&](size_t ci) { return HostPipe::part(nitems, chunk_items, ci); };
+    return h->pipe.run(
+        (nitems + chunk_items - 1) / chunk_items, plan,
+        [&](size_t ci) {
+            const size_t off = ci * chunk_items * h->isize, bytes = items(ci) * h->isize;
+            // nothing to deliver for MATHOP_EMPTY
+            return HostPipe::Chunk{{(const char *)a + off}, {bytes}, (char *)c + off, h->op != MI355_OP_EMPTY ? bytes : 0};
+        },
+        [&](size_t ci, void *const *in, void *out, hipStream_t st) { return dispatch1(h, items(ci), in[0], out, k, st); });
 }

@@ -1325,21 +1325,9 @@ extern "C" int mi355_pfb_work(mi355_pfb *h, const void *in, void *out)
     size_t inb = (size_t)mi355_pfb_ninput(h) * 8, outb = (size_t)mi355_pfb_noutput(h) * 8;
     int rc = h->pipe.ensure(1, &inb, outb);
     if (rc) return rc;
-    HostPipe &p = h->pipe;
-    hipStream_t st = h->ctx->stream[0];
-    mi355_copy(p.h_in[0][0], in, inb);
-    if (mi355_direct_ok(inb > outb ? inb : outb, h->ctx)) {  // small call: the kernel works on the pinned staging itself (common.h)
-        rc = launch_pfb(h, p.h_in[0][0], p.h_out[0], st, h->nsteps, h->buf_items);
-        if (rc) return rc;
-        MI355_HIP(mi355_direct_sync(st));
-        mi355_copy(out, p.h_out[0], outb);
-        return MI355_OK;
-    }
-    MI355_HIP(hipMemcpyAsync(p.d_in[0][0], p.h_in[0][0], inb, hipMemcpyHostToDevice, st));
-    rc = launch_pfb(h, p.d_in[0][0], p.d_out[0], st, h->nsteps, h->buf_items);
-    if (rc) return rc;
-    MI355_HIP(hipMemcpyAsync(p.h_out[0], p.d_out[0], outb, hipMemcpyDeviceToHost, st));
-    MI355_HIP(hipStreamSynchronize(st));
-    mi355_copy(out, p.h_out[0], outb);
-    return MI355_OK;
+    // small call: the kernel works on the pinned staging itself (common.h)
+    const HostPipe::Plan plan{1, true, mi355_direct_ok(inb > outb ? inb : outb, h->ctx)};
+    return h->pipe.run(
+        1, plan, [&](size_t) { return HostPipe::Chunk{{in}, {inb}, out, outb}; },
+        [&](size_t, void *const *d_in, void *d_out, hipStream_t st) { return launch_pfb(h, d_in[0], d_out, st, h->nsteps, h->buf_items); });
 }

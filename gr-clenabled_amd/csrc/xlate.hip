@@ -606,25 +606,27 @@ extern "C" int mi355_xlate_work(mi355_xlate *h, long long noutput, const void *i
     const size_t in_cap = (piece * h->D + hist) * 8;
     rc = h->pipe.ensure(1, &in_cap, piece * 8 * h->C, 1);
     if (rc) return rc;
-    HostPipe &p = h->pipe;
-    hipStream_t st = h->ctx->stream[0];
-    std::vector<u64> ph(h->phase);
+    const HostPipe::Plan plan{1, true, false};  // one slot, stream[0], never direct
+    auto outputs = [&](size_t ci) { return HostPipe::part((size_t)noutput, piece, ci); };
+    std::vector<u64> ph(h->C);
     std::vector<void *> d_outs(h->C);
-    for (int c = 0; c < h->C; c++) d_outs[c] = (char *)p.d_out[0] + (size_t)c * piece * 8;
-    for (size_t off = 0; off < (size_t)noutput; off += piece) {
-        const size_t m = (size_t)noutput - off < piece ? (size_t)noutput - off : piece;
-        const size_t in_bytes = (m * h->D + hist) * 8;
-        mi355_copy(p.h_in[0][0], (const char *)in_with_history + off * h->D * 8, in_bytes);
-        MI355_HIP(hipMemcpyAsync(p.d_in[0][0], p.h_in[0][0], in_bytes, hipMemcpyHostToDevice, st));
-        rc = xl_launch(h, (long long)m, p.d_in[0][0], d_outs.data(), ph.data(), st);
-        if (rc) return rc;
-        MI355_HIP(hipMemcpyAsync(p.h_out[0], p.d_out[0], piece * 8 * h->C, hipMemcpyDeviceToHost, st));
-        MI355_HIP(hipStreamSynchronize(st));
-        for (int c = 0; c < h->C; c++) {
-            mi355_copy((char *)outs[c] + off * 8, (const char *)p.h_out[0] + (size_t)c * piece * 8, m * 8);
-            ph[c] += h->inc[c] * (u64)m;
-        }
-    }
-    h->phase = ph;
+    rc = h->pipe.run(
+        ((size_t)noutput + piece - 1) / piece, plan,
+        [&](size_t ci) {  // channel c of a piece lies at c * piece outputs, whatever the piece holds
+            return HostPipe::Chunk{{(const char *)in_with_history + ci * piece * h->D * 8}, {(outputs(ci) * h->D + hist) * 8}, nullptr, piece * 8 * h->C};
+        },
+        [&](size_t ci, void *const *d_in, void *d_out, hipStream_t st) {
+            for (int c = 0; c < h->C; c++) {
+                d_outs[c] = (char *)d_out + (size_t)c * piece * 8;
+                ph[c] = h->phase[c] + h->inc[c] * (u64)(ci * piece);  // the phase is a kernel argument: where this piece starts
+            }
+            return xl_launch(h, (long long)outputs(ci), d_in[0], d_outs.data(), ph.data(), st);
+        },
+        [&](size_t ci, const void *h_out) {
+            for (int c = 0; c < h->C; c++)
+                mi355_copy((char *)outs[c] + ci * piece * 8, (const char *)h_out + (size_t)c * piece * 8, outputs(ci) * 8);
+        });
+    if (rc) return rc;
+    for (int c = 0; c < h->C; c++) h->phase[c] += h->inc[c] * (u64)noutput;
     return MI355_OK;
 }

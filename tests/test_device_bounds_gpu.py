@@ -482,14 +482,21 @@ def _host_check(whole, lo, n):
 
 DIRECT = 512 << 10  # kDirectBytes (common.h): a call whose largest buffer is at most this runs its kernels on the pinned staging itself
 # (block, path, items).  Which paths a block's work() has differs, and the ids say which one a case takes:
-#   clMathOp / clMathConst / clFFT / clFilter: the direct path, and the pipeline of staging chunks (total / 6 bytes each, 1 ... 8 MiB;
-#     3.3 MiB = four chunks over three slots: the pend_bytes bookkeeping).  The filter sizes both by its INPUT, decim x the output.
+#   clMathOp / clMathConst / clFFT / clFilter: the direct path, and the pipeline of staging chunks (total / 6 bytes each, 1 ... 8 MiB)
+#     over HostPipe's four slots: 3.3 MiB = four chunks of 1 MiB, every slot used once; 5.5 MiB = six chunks, slots 0 and 1 used twice
+#     (the wait for a slot's event and the delivery of its previous result beside the next input).  The filter sizes both by its
+#     INPUT, decim x the output.
 #   clPolyphaseChannelizer, elementwise: the direct path, else ONE staged transfer per call whatever its size (no chunks).
 #   clxcorrelate_fft_vcf: no direct path; staged chunks of 64 MiB of input (all inputs together), so one chunk or, above that, two.
+CHUNKS = {"four_chunks": 4, "six_chunks": 6}  # of 1 MiB: the call's sizing bytes lie in (chunks - 1, chunks] MiB
 HOST_CASES = [("clMathOp", "direct", DIRECT // 8), ("clMathOp", "four_chunks", (3400 << 10) // 8 - 77),
+              ("clMathOp", "six_chunks", (5600 << 10) // 8 - 77),
               ("clMathConst", "direct", DIRECT // 8), ("clMathConst", "four_chunks", (3400 << 10) // 8 - 77),
+              ("clMathConst", "six_chunks", (5600 << 10) // 8 - 77),
               ("clFFT", "direct", DIRECT // 8), ("clFFT", "four_chunks", (3400 << 10) // 8 - 77),
+              ("clFFT", "six_chunks", (5600 << 10) // 8 - 77),
               ("clFilter", "direct", 32700), ("clFilter", "four_chunks", (3400 << 10) // 16 - 77),
+              ("clFilter", "six_chunks", (5600 << 10) // 16 - 77),
               ("clPolyphaseChannelizer", "direct", 64 * 900), ("clPolyphaseChannelizer", "one_staged_transfer", 64 * 6800),
               ("clComplexToMagPhase", "direct", 60001), ("clComplexToMagPhase", "one_staged_transfer", 435123),
               ("clxcorrelate_fft_vcf", "one_staged_chunk", 256 * 100), ("clxcorrelate_fft_vcf", "two_staged_chunks", 256 * 11000)]
@@ -504,6 +511,8 @@ def test_host_path_copy_back_stays_inside_the_output(gpu, oracle, block, path, i
     direct = path == "direct"
     if block in ("clMathOp", "clMathConst", "clFFT"):
         assert (items * 8 <= DIRECT) == direct and (direct or items * 8 // 6 <= 1 << 20 < items * 8 // 3)
+        sized = items // 1024 * 1024 * 8 if block == "clFFT" else items * 8  # clFFT: whole 1024-point frames
+        assert direct or (CHUNKS[path] - 1) << 20 < sized <= CHUNKS[path] << 20
     if block == "clMathOp":
         a, b = crandn(rng, items), crandn(rng, items)
         outs, ref = [_host_out(items, np.complex64)], [oracle.mathop(oracle.DTYPE_COMPLEX, oracle.OP_MULTIPLY, a, b)]
@@ -523,6 +532,7 @@ def test_host_path_copy_back_stays_inside_the_output(gpu, oracle, block, path, i
         taps = oracle.firdes_low_pass(1.0, 10e6, 1e6, 372000.0)
         inb = (items * 2 + taps.size - 1) * 8  # mi355_filter_work: direct when the call's input fits
         assert (inb <= DIRECT) == direct and (direct or items * 16 // 6 <= 1 << 20 < items * 16 // 3)
+        assert direct or (CHUNKS[path] - 1) << 20 < items * 16 <= CHUNKS[path] << 20
         xh = crandn(rng, items * 2 + taps.size - 1)
         outs, ref = [_host_out(items, np.complex64)], [oracle.fir_ccf(taps, xh, items, 2)]
         gpu.clFilter(*GPU_ARGS, 2, taps).work(items, [xh], [outs[0][1]])
