@@ -301,3 +301,46 @@ int HostPipe::run(size_t nchunks, const Plan &plan, Describe &&describe, Launch 
     }
     return rc;
 }
+
+// ---------------------------------------------------------------------------
+// The host-pointer work() of the blocks that copy straight from and to the caller's pageable memory (clPowerSpectrum, the
+// synthesizer, the resampler, clFEngine, clSignalSource, clCostasLoop, clxcorrelate_fft_vcf): device scratch and the piece loop.
+// ---------------------------------------------------------------------------
+// Grow-only device scratch of a handle; sizes are bytes.  The caller holds the handle's lock and has set the device, and nothing
+// queued may still use the buffer when reserve() has to grow it (these paths wait for their stream after every piece).
+struct DevBuf {
+    // no-op when the buffer holds `want` bytes already; otherwise the old block is freed and a new one allocated.  After a failed
+    // allocation the buffer is empty, no HIP error is left behind and a later reserve() starts from scratch.
+    int reserve(size_t want);
+    void release();
+    void *get() const { return p; }
+    size_t bytes() const { return n; }
+
+private:
+    void *p = nullptr;
+    size_t n = 0;
+};
+
+// units in a piece of a call of `total` >= 1 units that would like `want` per piece
+template <class T> static inline T mi355_piece_units(T want, T total) { return want < 1 ? 1 : want > total ? total : want; }
+
+// The piece loop of such a work(): units [0, total) in pieces of `per` (the last one ragged), strictly one after the other on
+// ctx->stream[0].  piece(first, count, stream) -> MI355_* queues its copies from the caller's memory, its launches and its copies
+// to the caller's memory; the stream is waited for before the next piece starts, so a piece may reuse the scratch of the one
+// before.  On the first non-zero code, from piece() or from the wait, the stream is waited for once more (whatever that wait says)
+// and the code is returned: no copy from or to the caller's arrays outlives the call, and no later piece is started.
+template <class T, class Piece> int mi355_pageable_run(mi355_ctx *ctx, T total, T per, Piece &&piece)
+{
+    hipStream_t st = ctx->stream[0];
+    per = mi355_piece_units(per, total);
+    const int rc = [&]() -> int {
+        for (T first = 0; first < total; first += per) {
+            const int prc = piece(first, total - first < per ? total - first : per, st);
+            if (prc) return prc;
+            MI355_HIP(hipStreamSynchronize(st));
+        }
+        return MI355_OK;
+    }();
+    if (rc != MI355_OK) (void)hipStreamSynchronize(st);
+    return rc;
+}

@@ -369,13 +369,11 @@ struct mi355_fengine {
     unsigned long long *d_clips = nullptr;
     mi355_fft *fft = nullptr;             // generic route, made when first needed
     // generic route: one workspace per handle; calls on different streams are ordered on it
-    void *d_ws = nullptr;
-    size_t ws_bytes = 0;
+    DevBuf ws;
     hipEvent_t ws_done = nullptr;
     hipStream_t ws_stream = nullptr;
     bool ws_used = false;
-    void *d_in = nullptr, *d_out = nullptr;  // host path staging
-    size_t d_in_bytes = 0, d_out_bytes = 0;
+    DevBuf d_in, d_out;  // host path staging
     std::string route;
     std::mutex lock;
 };
@@ -412,17 +410,6 @@ void fe_name_route(mi355_fengine *h)
 int fe_upload(mi355_fengine *h)
 {
     return h->gtab.publish(h->ctx, h->gains.data(), h->gains.size() * sizeof(float), "mi355_fengine: gain");
-}
-
-int fe_ensure(void **p, size_t *have, size_t want)
-{
-    if (*have >= want) return MI355_OK;
-    if (*p) MI355_HIP(hipFree(*p));
-    *p = nullptr;
-    *have = 0;
-    MI355_HIP(hipMalloc(p, want));
-    *have = want;
-    return MI355_OK;
 }
 
 unsigned fe_grid(const mi355_ctx *ctx, long long total)
@@ -494,10 +481,10 @@ int fe_launch_generic(mi355_fengine *h, long long n, const void *const *in, void
     if (nb > n) nb = n;
     const size_t half = (size_t)Sb * npol * nb * N * 8;
     if (h->ws_used && h->ws_stream != st) MI355_HIP(hipStreamWaitEvent(st, h->ws_done, 0));
-    if (2 * half > h->ws_bytes && h->ws_used) MI355_HIP(hipEventSynchronize(h->ws_done));  // kernels of an earlier call still use the old one
-    int rc = fe_ensure(&h->d_ws, &h->ws_bytes, 2 * half);
+    if (2 * half > h->ws.bytes() && h->ws_used) MI355_HIP(hipEventSynchronize(h->ws_done));  // kernels of an earlier call still use the old one
+    int rc = h->ws.reserve(2 * half);
     if (rc) return rc;
-    c32 *d_z = (c32 *)h->d_ws, *d_x = (c32 *)((char *)h->d_ws + half);
+    c32 *d_z = (c32 *)h->ws.get(), *d_x = (c32 *)((char *)h->ws.get() + half);
     FeGenArgs g = {};
     g.taps = h->d_taps;
     g.z = d_z;
@@ -636,8 +623,9 @@ extern "C" int mi355_fengine_destroy(mi355_fengine *h)
     h->gtab.release();
     if (h->ws_used) (void)hipEventSynchronize(h->ws_done);
     if (h->fft) (void)mi355_fft_destroy(h->fft);
-    for (void *p : {(void *)h->d_taps, h->d_tw, (void *)h->d_clips, h->d_ws, h->d_in, h->d_out})
+    for (void *p : {(void *)h->d_taps, h->d_tw, (void *)h->d_clips})
         if (p) (void)hipFree(p);
+    for (DevBuf *b : {&h->ws, &h->d_in, &h->d_out}) b->release();
     if (h->ws_done) (void)hipEventDestroy(h->ws_done);
     delete h;
     return MI355_OK;
@@ -723,24 +711,19 @@ extern "C" int mi355_fengine_work(mi355_fengine *h, long long nframes, const voi
     // pieces of whole frames; a piece re-sends the (P - 1) N items of history it shares with the piece before
     const long long hist = (long long)(h->P - 1) * h->N;
     const long long per_frame = 8ll * h->N * h->R > h->frame_bytes ? 8ll * h->N * h->R : h->frame_bytes;
-    long long piece = kFeHostBytes / per_frame;
-    if (piece < 1) piece = 1;
-    if (piece > nframes) piece = nframes;
+    const long long piece = mi355_piece_units(kFeHostBytes / per_frame, nframes);
     const size_t stride = (size_t)(piece * h->N + hist) * 8;  // bytes per input in the staging buffer
-    if ((rc = fe_ensure(&h->d_in, &h->d_in_bytes, stride * h->R))) return rc;
-    if ((rc = fe_ensure(&h->d_out, &h->d_out_bytes, (size_t)(piece * h->frame_bytes)))) return rc;
+    if ((rc = h->d_in.reserve(stride * h->R))) return rc;
+    if ((rc = h->d_out.reserve((size_t)(piece * h->frame_bytes)))) return rc;
     std::vector<const void *> ptrs((size_t)h->R);
-    for (int r = 0; r < h->R; r++) ptrs[r] = (const char *)h->d_in + stride * r;
-    hipStream_t st = h->ctx->stream[0];
-    for (long long t0 = 0; t0 < nframes; t0 += piece) {
-        const long long m = nframes - t0 < piece ? nframes - t0 : piece;
+    for (int r = 0; r < h->R; r++) ptrs[r] = (const char *)h->d_in.get() + stride * r;
+    return mi355_pageable_run(h->ctx, nframes, piece, [&](long long t0, long long m, hipStream_t st) -> int {
         for (int r = 0; r < h->R; r++)
-            MI355_HIP(hipMemcpyAsync((char *)h->d_in + stride * r, (const char *)in_with_history[r] + t0 * h->N * 8, (size_t)(m * h->N + hist) * 8,
+            MI355_HIP(hipMemcpyAsync((char *)h->d_in.get() + stride * r, (const char *)in_with_history[r] + t0 * h->N * 8, (size_t)(m * h->N + hist) * 8,
                                      hipMemcpyHostToDevice, st));
-        rc = fe_launch(h, m, ptrs.data(), h->d_out, st);
-        if (rc) return rc;
-        MI355_HIP(hipMemcpyAsync((char *)out + t0 * h->frame_bytes, h->d_out, (size_t)(m * h->frame_bytes), hipMemcpyDeviceToHost, st));
-        MI355_HIP(hipStreamSynchronize(st));
-    }
-    return MI355_OK;
+        const int lrc = fe_launch(h, m, ptrs.data(), h->d_out.get(), st);
+        if (lrc) return lrc;
+        MI355_HIP(hipMemcpyAsync((char *)out + t0 * h->frame_bytes, h->d_out.get(), (size_t)(m * h->frame_bytes), hipMemcpyDeviceToHost, st));
+        return MI355_OK;
+    });
 }

@@ -1,7 +1,32 @@
-// HostPipe (common.h): the staging buffers and per-slot events of the host-pointer work() path.  This unit and the driver,
-// HostPipe::run in common.h, use the HIP runtime's host API only, so that tests/hostpipe_host_main.cc can compile both with a
-// host compiler over stubs of those calls.
+// HostPipe (common.h): the staging buffers and per-slot events of the host-pointer work() path, and DevBuf, the device scratch of
+// the pageable host paths.  This unit and the drivers, HostPipe::run and mi355_pageable_run in common.h, use the HIP runtime's host
+// API only, so that tests/hostpipe_host_main.cc can compile them with a host compiler over stubs of those calls.
 #include "common.h"
+
+int DevBuf::reserve(size_t want)
+{
+    if (n >= want) return MI355_OK;
+    void *old = p;
+    p = nullptr;
+    n = 0;
+    if (old) MI355_HIP(hipFree(old));
+    const hipError_t e = hipMalloc(&p, want);
+    if (e != hipSuccess) {
+        p = nullptr;
+        (void)hipGetLastError();
+        mi355_set_error("hipMalloc of %zu bytes of device scratch -> %s", want, hipGetErrorString(e));
+        return MI355_ERR_HIP;
+    }
+    n = want;
+    return MI355_OK;
+}
+
+void DevBuf::release()
+{
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    n = 0;
+}
 
 int HostPipe::init(mi355_ctx *c)
 {

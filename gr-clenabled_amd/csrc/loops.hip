@@ -257,8 +257,7 @@ struct mi355_sigsource {
     double pos = 0, inc = 0;
     std::mutex lock;
     bool literal = false;    // one sincos per item: int output always; MI355_SIGSOURCE_LITERAL=1 at create (comparison variant)
-    void *d_buf = nullptr;   // host path staging
-    size_t d_items = 0;
+    DevBuf d_buf;            // host path staging
 };
 
 namespace {
@@ -334,9 +333,9 @@ extern "C" int mi355_sigsource_create(mi355_ctx *ctx, int dtype, double samp_rat
 extern "C" int mi355_sigsource_destroy(mi355_sigsource *h)
 {
     if (!h) return MI355_OK;
-    if (h->d_buf) {
+    if (h->d_buf.get()) {
         (void)hipSetDevice(h->ctx->device);
-        (void)hipFree(h->d_buf);
+        h->d_buf.release();
     }
     delete h;
     return MI355_OK;
@@ -390,21 +389,16 @@ extern "C" int mi355_sigsource_work(mi355_sigsource *h, size_t n, void *out_host
     std::lock_guard<std::mutex> g(h->lock);
     MI355_HIP(hipSetDevice(h->ctx->device));
     const size_t isz = h->dtype == MI355_DTYPE_COMPLEX ? 8 : 4;
-    const size_t chunk = n < kHostChunkItems ? n : kHostChunkItems;
-    if (h->d_items < chunk) {
-        if (h->d_buf) MI355_HIP(hipFree(h->d_buf));
-        h->d_buf = nullptr; h->d_items = 0;
-        MI355_HIP(hipMalloc(&h->d_buf, chunk * isz));
-        h->d_items = chunk;
-    }
-    hipStream_t st = h->ctx->stream[0];
-    for (size_t off = 0; off < n; off += chunk) {
-        const size_t m = n - off < chunk ? n - off : chunk;
-        const int rc = sigsource_launch(h, m, off, h->pos, h->d_buf, st);
-        if (rc) return rc;
-        MI355_HIP(hipMemcpyAsync((char *)out_host + off * isz, h->d_buf, m * isz, hipMemcpyDeviceToHost, st));
-        MI355_HIP(hipStreamSynchronize(st));
-    }
+    const size_t chunk = mi355_piece_units(kHostChunkItems, n);
+    int rc = h->d_buf.reserve(chunk * isz);
+    if (rc) return rc;
+    rc = mi355_pageable_run(h->ctx, n, chunk, [&](size_t off, size_t m, hipStream_t st) -> int {
+        const int lrc = sigsource_launch(h, m, off, h->pos, h->d_buf.get(), st);
+        if (lrc) return lrc;
+        MI355_HIP(hipMemcpyAsync((char *)out_host + off * isz, h->d_buf.get(), m * isz, hipMemcpyDeviceToHost, st));
+        return MI355_OK;
+    });
+    if (rc) return rc;
     sigsource_advance(h, n);
     return MI355_OK;
 }
@@ -420,8 +414,7 @@ struct mi355_costas {
     bool used = false;
     bool one_lane = false;           // MI355_COSTAS_ONE_LANE=1 at create: a single stream through k_costas_lanes (comparison variant)
     std::mutex lock;
-    void *d_in = nullptr, *d_out = nullptr, *d_freq = nullptr;  // host path staging
-    size_t d_items = 0;
+    DevBuf d_in, d_out, d_freq;      // host path staging
 };
 
 namespace {
@@ -466,9 +459,7 @@ void costas_free(mi355_costas *h)
 {
     (void)hipSetDevice(h->ctx->device);
     if (h->d_state) (void)hipFree(h->d_state);
-    if (h->d_in) (void)hipFree(h->d_in);
-    if (h->d_out) (void)hipFree(h->d_out);
-    if (h->d_freq) (void)hipFree(h->d_freq);
+    for (DevBuf *b : {&h->d_in, &h->d_out, &h->d_freq}) b->release();
     if (h->done) (void)hipEventDestroy(h->done);
     delete h;
 }
@@ -584,28 +575,15 @@ extern "C" int mi355_costas_work(mi355_costas *h, size_t nitems, const void *in,
     std::lock_guard<std::mutex> g(h->lock);
     MI355_HIP(hipSetDevice(h->ctx->device));
     const size_t S = (size_t)h->S;
-    size_t chunk = kHostChunkItems / S;  // items per stream and piece; any split gives the same bits
-    if (chunk > nitems) chunk = nitems;
-    if (h->d_items < chunk * S) {
-        for (void **p : {&h->d_in, &h->d_out, &h->d_freq}) {
-            if (*p) MI355_HIP(hipFree(*p));
-            *p = nullptr;
-        }
-        h->d_items = 0;
-        MI355_HIP(hipMalloc(&h->d_in, chunk * S * 8));
-        MI355_HIP(hipMalloc(&h->d_out, chunk * S * 8));
-        MI355_HIP(hipMalloc(&h->d_freq, chunk * S * 4));
-        h->d_items = chunk * S;
-    }
-    hipStream_t st = h->ctx->stream[0];
-    for (size_t off = 0; off < nitems; off += chunk) {
-        const size_t m = nitems - off < chunk ? nitems - off : chunk;
-        MI355_HIP(hipMemcpyAsync(h->d_in, (const char *)in + off * S * 8, m * S * 8, hipMemcpyHostToDevice, st));
-        const int rc = costas_launch(h, m, h->d_in, h->d_out, freq_out ? (float *)h->d_freq : nullptr, st);
-        if (rc) return rc;
-        MI355_HIP(hipMemcpyAsync((char *)out + off * S * 8, h->d_out, m * S * 8, hipMemcpyDeviceToHost, st));
-        if (freq_out) MI355_HIP(hipMemcpyAsync(freq_out + off * S, h->d_freq, m * S * 4, hipMemcpyDeviceToHost, st));
-        MI355_HIP(hipStreamSynchronize(st));
-    }
-    return MI355_OK;
+    const size_t chunk = mi355_piece_units(kHostChunkItems / S, nitems);  // items per stream and piece; any split gives the same bits
+    int rc;
+    if ((rc = h->d_in.reserve(chunk * S * 8)) || (rc = h->d_out.reserve(chunk * S * 8)) || (rc = h->d_freq.reserve(chunk * S * 4))) return rc;
+    return mi355_pageable_run(h->ctx, nitems, chunk, [&](size_t off, size_t m, hipStream_t st) -> int {
+        MI355_HIP(hipMemcpyAsync(h->d_in.get(), (const char *)in + off * S * 8, m * S * 8, hipMemcpyHostToDevice, st));
+        const int lrc = costas_launch(h, m, h->d_in.get(), h->d_out.get(), freq_out ? (float *)h->d_freq.get() : nullptr, st);
+        if (lrc) return lrc;
+        MI355_HIP(hipMemcpyAsync((char *)out + off * S * 8, h->d_out.get(), m * S * 8, hipMemcpyDeviceToHost, st));
+        if (freq_out) MI355_HIP(hipMemcpyAsync(freq_out + off * S, h->d_freq.get(), m * S * 4, hipMemcpyDeviceToHost, st));
+        return MI355_OK;
+    });
 }

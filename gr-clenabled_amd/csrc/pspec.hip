@@ -300,13 +300,11 @@ struct mi355_pspec {
     std::string route_name;
     // one workspace per handle (fused K > C: partial sums; generic: gathered frames, transformed frames, carried sums); calls on different
     // streams are ordered on it: the later stream waits for the earlier call's kernels
-    void *d_ws = nullptr;
-    size_t ws_bytes = 0;
+    DevBuf ws;
     hipEvent_t ws_done = nullptr;
     hipStream_t ws_stream = nullptr;
     bool ws_used = false;
-    void *d_in = nullptr, *d_out = nullptr;  // host path staging
-    size_t d_in_bytes = 0, d_out_bytes = 0;
+    DevBuf d_in, d_out;  // host path staging
     std::mutex lock;
 };
 
@@ -328,17 +326,6 @@ void ps_name(mi355_pspec *h)
     h->route_name = name;
 }
 
-int ps_ensure(void **p, size_t *have, size_t want)
-{
-    if (*have >= want) return MI355_OK;
-    if (*p) MI355_HIP(hipFree(*p));
-    *p = nullptr;
-    *have = 0;
-    MI355_HIP(hipMalloc(p, want));
-    *have = want;
-    return MI355_OK;
-}
-
 // caller holds h->lock (or is create) and has set the device
 int ps_ensure_fft(mi355_pspec *h)
 {
@@ -350,8 +337,8 @@ int ps_ensure_fft(mi355_pspec *h)
 int ps_ws_acquire(mi355_pspec *h, size_t bytes, hipStream_t st)
 {
     if (h->ws_used && h->ws_stream != st) MI355_HIP(hipStreamWaitEvent(st, h->ws_done, 0));
-    if (bytes > h->ws_bytes && h->ws_used) MI355_HIP(hipEventSynchronize(h->ws_done));  // kernels of an earlier call still use the old one
-    return ps_ensure(&h->d_ws, &h->ws_bytes, bytes);
+    if (bytes > h->ws.bytes() && h->ws_used) MI355_HIP(hipEventSynchronize(h->ws_done));  // kernels of an earlier call still use the old one
+    return h->ws.reserve(bytes);
 }
 
 int ps_ws_release(mi355_pspec *h, hipStream_t st)
@@ -406,13 +393,13 @@ int ps_launch_fused(mi355_pspec *h, long long S, const void *in, float *out, hip
     for (long long s0 = 0; s0 < S; s0 += per) {
         const long long n = S - s0 < per ? S - s0 : per;
         a.in = (const f2v *)in + s0 * K * (long long)h->H;
-        a.out = nchunks > 1 ? (float *)h->d_ws : out + s0 * N;
+        a.out = nchunks > 1 ? (float *)h->ws.get() : out + s0 * N;
         const unsigned grid = (unsigned)(n * nchunks);
 #define X(NN) if (N == NN) hipLaunchKernelGGL((k_pspec<NN>), dim3(grid), dim3(256), 0, st, a);
         PS_SIZES(X)
 #undef X
         if (nchunks > 1)
-            hipLaunchKernelGGL(k_pspec_finish, dim3(ps_grid(h->ctx, n * N)), dim3(256), 0, st, (const float *)h->d_ws, out + s0 * N, N, nchunks,
+            hipLaunchKernelGGL(k_pspec_finish, dim3(ps_grid(h->ctx, n * N)), dim3(256), 0, st, (const float *)h->ws.get(), out + s0 * N, N, nchunks,
                                h->shift ? N / 2 : 0, a.sk, h->log_output, n * N);
     }
     MI355_HIP(hipGetLastError());
@@ -440,7 +427,7 @@ int ps_launch_generic(mi355_pspec *h, long long S, const void *in, float *out, h
     const size_t frames_bytes = (size_t)nb * N * 8, acc_bytes = (size_t)N * sizeof(float);
     rc = ps_ws_acquire(h, (gather ? 2 : 1) * frames_bytes + acc_bytes, st);
     if (rc) return rc;
-    char *ws = (char *)h->d_ws;
+    char *ws = (char *)h->ws.get();
     f2v *d_g = (f2v *)ws;
     c32 *d_x = (c32 *)(ws + (gather ? frames_bytes : 0));
     float *d_acc = (float *)(ws + (gather ? 2 : 1) * frames_bytes);
@@ -575,8 +562,8 @@ extern "C" int mi355_pspec_destroy(mi355_pspec *h)
     (void)hipSetDevice(h->ctx->device);
     if (h->fft) (void)mi355_fft_destroy(h->fft);
     h->win.release();
-    for (void *p : {h->d_tw, h->d_ws, h->d_in, h->d_out})
-        if (p) (void)hipFree(p);
+    if (h->d_tw) (void)hipFree(h->d_tw);
+    for (DevBuf *b : {&h->ws, &h->d_in, &h->d_out}) b->release();
     if (h->ws_done) (void)hipEventDestroy(h->ws_done);
     delete h;
     return MI355_OK;
@@ -647,22 +634,17 @@ extern "C" int mi355_pspec_work(mi355_pspec *h, long long nspectra, const void *
     MI355_HIP(hipSetDevice(h->ctx->device));
     // pieces of whole spectra; a piece re-sends the max(N - H, 0) items it shares with the piece before
     const long long per_spec = (long long)h->K * h->H * 8;
-    long long piece = kPsHostBytes / per_spec;
-    if (piece < 1) piece = 1;
-    if (piece > nspectra) piece = nspectra;
+    const long long piece = mi355_piece_units(kPsHostBytes / per_spec, nspectra);
     long long pin, pout;
     (void)ps_counts(h->N, h->K, h->H, piece, &pin, &pout);
-    if ((rc = ps_ensure(&h->d_in, &h->d_in_bytes, (size_t)pin * 8))) return rc;
-    if ((rc = ps_ensure(&h->d_out, &h->d_out_bytes, (size_t)pout * 4))) return rc;
-    hipStream_t st = h->ctx->stream[0];
-    for (long long s0 = 0; s0 < nspectra; s0 += piece) {
-        const long long n = nspectra - s0 < piece ? nspectra - s0 : piece;
+    if ((rc = h->d_in.reserve((size_t)pin * 8))) return rc;
+    if ((rc = h->d_out.reserve((size_t)pout * 4))) return rc;
+    return mi355_pageable_run(h->ctx, nspectra, piece, [&](long long s0, long long n, hipStream_t st) -> int {
         (void)ps_counts(h->N, h->K, h->H, n, &pin, &pout);
-        MI355_HIP(hipMemcpyAsync(h->d_in, (const char *)in + s0 * per_spec, (size_t)pin * 8, hipMemcpyHostToDevice, st));
-        rc = ps_launch(h, n, h->d_in, h->d_out, st);
-        if (rc) return rc;
-        MI355_HIP(hipMemcpyAsync((char *)out + s0 * h->N * 4, h->d_out, (size_t)pout * 4, hipMemcpyDeviceToHost, st));
-        MI355_HIP(hipStreamSynchronize(st));
-    }
-    return MI355_OK;
+        MI355_HIP(hipMemcpyAsync(h->d_in.get(), (const char *)in + s0 * per_spec, (size_t)pin * 8, hipMemcpyHostToDevice, st));
+        const int lrc = ps_launch(h, n, h->d_in.get(), h->d_out.get(), st);
+        if (lrc) return lrc;
+        MI355_HIP(hipMemcpyAsync((char *)out + s0 * h->N * 4, h->d_out.get(), (size_t)pout * 4, hipMemcpyDeviceToHost, st));
+        return MI355_OK;
+    });
 }

@@ -236,8 +236,7 @@ struct mi355_resampler {
     bool lds = false;                 // k_rs_lds serves the handle (else k_rs_plain); fixed by set_taps
     int interp = 0;                   // k_rs_interp with this many window registers serves it instead (0: no)
     int ntp = 0, tile = 0, x_off = 0, y_off = 0, lds_bytes = 0, wg_per_cu = 1;
-    void *d_in = nullptr, *d_out = nullptr;  // host path staging
-    size_t d_in_items = 0, d_out_items = 0;
+    DevBuf d_in, d_out;  // host path staging
     std::mutex lock;
 };
 
@@ -429,8 +428,8 @@ extern "C" int mi355_resampler_destroy(mi355_resampler *h)
     if (!h) return MI355_OK;
     (void)hipSetDevice(h->ctx->device);
     h->rev.release();
-    if (h->d_in) (void)hipFree(h->d_in);
-    if (h->d_out) (void)hipFree(h->d_out);
+    h->d_in.release();
+    h->d_out.release();
     delete h;
     return MI355_OK;
 }
@@ -505,37 +504,23 @@ extern "C" int mi355_resampler_work(mi355_resampler *h, long long noutput, const
                   "clRationalResampler does not work in place: in and out overlap");
     MI355_HIP(hipSetDevice(h->ctx->device));
     // pieces of outputs whose larger side is about kRsHostChunk items; each piece re-sends its nt - 1 samples of history
-    long long piece = h->M > h->L ? kRsHostChunk * h->L / h->M : kRsHostChunk;
-    if (piece < 1) piece = 1;
-    if (piece > noutput) piece = noutput;
-    const size_t in_cap = (size_t)rs_needed(h->L, h->M, h->nt, h->L - 1, piece), out_cap = (size_t)piece;
-    if (h->d_in_items < in_cap) {
-        if (h->d_in) MI355_HIP(hipFree(h->d_in));
-        h->d_in = nullptr; h->d_in_items = 0;
-        MI355_HIP(hipMalloc(&h->d_in, in_cap * 8));
-        h->d_in_items = in_cap;
-    }
-    if (h->d_out_items < out_cap) {
-        if (h->d_out) MI355_HIP(hipFree(h->d_out));
-        h->d_out = nullptr; h->d_out_items = 0;
-        MI355_HIP(hipMalloc(&h->d_out, out_cap * 8));
-        h->d_out_items = out_cap;
-    }
-    hipStream_t st = h->ctx->stream[0];
+    const long long piece = mi355_piece_units(h->M > h->L ? kRsHostChunk * h->L / h->M : kRsHostChunk, noutput);
+    if ((rc = h->d_in.reserve((size_t)rs_needed(h->L, h->M, h->nt, h->L - 1, piece) * 8))) return rc;
+    if ((rc = h->d_out.reserve((size_t)piece * 8))) return rc;
     const char *pin = (const char *)in_with_history;
-    long long used = 0;
+    long long used = 0;  // inputs consumed by, and the phase behind, the pieces queued so far
     int c = h->phase;
-    for (long long off = 0; off < noutput; off += piece) {
-        const long long m = noutput - off < piece ? noutput - off : piece;
+    rc = mi355_pageable_run(h->ctx, noutput, piece, [&](long long off, long long m, hipStream_t st) -> int {
         const long long need = rs_needed(h->L, h->M, h->nt, c, m), adv = (long long)c + m * h->M;
-        MI355_HIP(hipMemcpyAsync(h->d_in, pin + used * 8, (size_t)need * 8, hipMemcpyHostToDevice, st));
-        rc = rs_launch(h, m, c, h->d_in, h->d_out, st);
-        if (rc) return rc;
-        MI355_HIP(hipMemcpyAsync((char *)out + off * 8, h->d_out, (size_t)m * 8, hipMemcpyDeviceToHost, st));
-        MI355_HIP(hipStreamSynchronize(st));
+        MI355_HIP(hipMemcpyAsync(h->d_in.get(), pin + used * 8, (size_t)need * 8, hipMemcpyHostToDevice, st));
+        const int lrc = rs_launch(h, m, c, h->d_in.get(), h->d_out.get(), st);
+        if (lrc) return lrc;
+        MI355_HIP(hipMemcpyAsync((char *)out + off * 8, h->d_out.get(), (size_t)m * 8, hipMemcpyDeviceToHost, st));
         used += adv / h->L;
         c = (int)(adv % h->L);
-    }
+        return MI355_OK;
+    });
+    if (rc) return rc;
     h->phase = c;
     if (consumed) *consumed = used;
     return MI355_OK;

@@ -204,10 +204,8 @@ struct mi355_synth {
     int nreg = 0, taps_lds = 0, lds_bytes = 0;  // pow2
     MrPlan plan;                      // mixed radix (plan.n = 0: none)
     MrSynthGeo mg;
-    void *d_ws = nullptr;             // generic route: transformed frames of one piece
-    size_t ws_items = 0;
-    void *d_in = nullptr, *d_out = nullptr;  // host path staging
-    size_t d_in_items = 0, d_out_items = 0;
+    DevBuf ws;                        // generic route: transformed frames of one piece
+    DevBuf d_in, d_out;               // host path staging
     std::mutex lock;
 };
 
@@ -283,17 +281,6 @@ int syn_upload(mi355_synth *h, const float *taps, int K)
     return MI355_OK;
 }
 
-int syn_ensure(void **p, size_t *have, size_t want)
-{
-    if (*have >= want) return MI355_OK;
-    if (*p) MI355_HIP(hipFree(*p));
-    *p = nullptr;
-    *have = 0;
-    MI355_HIP(hipMalloc(p, want * 8));
-    *have = want;
-    return MI355_OK;
-}
-
 // caller holds h->lock and has set the device
 int syn_launch(mi355_synth *h, long long nframes, const void *in, void *out, hipStream_t st)
 {
@@ -340,7 +327,7 @@ int syn_launch(mi355_synth *h, long long nframes, const void *in, void *out, hip
     long long piece = kSynWsItems / M - (T - 1);
     if (piece < 1) piece = 1;
     if (piece > nframes) piece = nframes;
-    const int rc = syn_ensure(&h->d_ws, &h->ws_items, (size_t)(T - 1 + piece) * M);
+    const int rc = h->ws.reserve((size_t)(T - 1 + piece) * M * 8);
     if (rc) return rc;
     for (long long l0 = 0; l0 < nframes; l0 += piece) {
         const long long n = nframes - l0 < piece ? nframes - l0 : piece;
@@ -348,9 +335,9 @@ int syn_launch(mi355_synth *h, long long nframes, const void *in, void *out, hip
         long long g1 = (tv + 255) / 256, g2 = (to + 255) / 256;
         if (g1 > (long long)cus * 32) g1 = (long long)cus * 32;
         if (g2 > (long long)cus * 32) g2 = (long long)cus * 32;
-        hipLaunchKernelGGL(k_synth_dft, dim3((unsigned)g1), dim3(256), 0, st, (const c32 *)in, (c32 *)h->d_ws, (const c32 *)h->d_tw, map, h->nmap, M, l0,
+        hipLaunchKernelGGL(k_synth_dft, dim3((unsigned)g1), dim3(256), 0, st, (const c32 *)in, (c32 *)h->ws.get(), (const c32 *)h->d_tw, map, h->nmap, M, l0,
                            tv);
-        hipLaunchKernelGGL(k_synth_fir, dim3((unsigned)g2), dim3(256), 0, st, (const c32 *)h->d_ws, (c32 *)out + l0 * M, d_taps, M, T, to);
+        hipLaunchKernelGGL(k_synth_fir, dim3((unsigned)g2), dim3(256), 0, st, (const c32 *)h->ws.get(), (c32 *)out + l0 * M, d_taps, M, T, to);
     }
     MI355_HIP(hipGetLastError());
     return MI355_OK;
@@ -466,9 +453,7 @@ extern "C" int mi355_synth_destroy(mi355_synth *h)
     if (h->d_tw) (void)hipFree(h->d_tw);
     if (h->d_map) (void)hipFree(h->d_map);
     if (h->plan.d_tw) (void)hipFree(h->plan.d_tw);
-    if (h->d_ws) (void)hipFree(h->d_ws);
-    if (h->d_in) (void)hipFree(h->d_in);
-    if (h->d_out) (void)hipFree(h->d_out);
+    for (DevBuf *b : {&h->ws, &h->d_in, &h->d_out}) b->release();
     delete h;
     return MI355_OK;
 }
@@ -522,21 +507,15 @@ extern "C" int mi355_synth_work(mi355_synth *h, long long nframes, const void *i
                   "clPolyphaseSynthesizer does not work in place: in and out overlap");
     MI355_HIP(hipSetDevice(h->ctx->device));
     // pieces of about kSynHostChunk outputs; each piece re-sends its T - 1 frames of history
-    long long piece = kSynHostChunk / h->M;
-    if (piece < 1) piece = 1;
-    if (piece > nframes) piece = nframes;
-    rc = syn_ensure(&h->d_in, &h->d_in_items, (size_t)(h->T - 1 + piece) * h->nmap);
-    if (rc) return rc;
-    rc = syn_ensure(&h->d_out, &h->d_out_items, (size_t)piece * h->M);
-    if (rc) return rc;
-    hipStream_t st = h->ctx->stream[0];
-    for (long long l0 = 0; l0 < nframes; l0 += piece) {
-        const long long n = nframes - l0 < piece ? nframes - l0 : piece;
-        MI355_HIP(hipMemcpyAsync(h->d_in, (const char *)in_with_history + l0 * h->nmap * 8, (size_t)(h->T - 1 + n) * h->nmap * 8, hipMemcpyHostToDevice, st));
-        rc = syn_launch(h, n, h->d_in, h->d_out, st);
-        if (rc) return rc;
-        MI355_HIP(hipMemcpyAsync((char *)out + l0 * h->M * 8, h->d_out, (size_t)n * h->M * 8, hipMemcpyDeviceToHost, st));
-        MI355_HIP(hipStreamSynchronize(st));
-    }
-    return MI355_OK;
+    const long long piece = mi355_piece_units(kSynHostChunk / h->M, nframes);
+    if ((rc = h->d_in.reserve((size_t)(h->T - 1 + piece) * h->nmap * 8))) return rc;
+    if ((rc = h->d_out.reserve((size_t)piece * h->M * 8))) return rc;
+    return mi355_pageable_run(h->ctx, nframes, piece, [&](long long l0, long long n, hipStream_t st) -> int {
+        MI355_HIP(hipMemcpyAsync(h->d_in.get(), (const char *)in_with_history + l0 * h->nmap * 8, (size_t)(h->T - 1 + n) * h->nmap * 8,
+                                 hipMemcpyHostToDevice, st));
+        const int lrc = syn_launch(h, n, h->d_in.get(), h->d_out.get(), st);
+        if (lrc) return lrc;
+        MI355_HIP(hipMemcpyAsync((char *)out + l0 * h->M * 8, h->d_out.get(), (size_t)n * h->M * 8, hipMemcpyDeviceToHost, st));
+        return MI355_OK;
+    });
 }

@@ -187,8 +187,7 @@ struct mi355_xcorr_fft {
     int n, num_inputs, time_series;
     void *d_twf = nullptr, *d_twi = nullptr;
     // device staging for the host-pointer path (grow only)
-    void *d_in = nullptr, *d_out = nullptr;
-    size_t cap_frames = 0;
+    DevBuf d_in, d_out;
     // every other even size clFFT plans (8192, 16384, ... and lengths that are not a power of two): the steps of the reference's work()
     // one after the other over clFFT handles -- forward transforms, X0 conj(Xs), backward transform, |.| with the half swap
     bool composed = false;
@@ -362,8 +361,8 @@ extern "C" int mi355_xcorr_fft_destroy(mi355_xcorr_fft *h)
     (void)hipSetDevice(h->ctx->device);
     if (h->d_twf) (void)hipFree(h->d_twf);
     if (h->d_twi) (void)hipFree(h->d_twi);
-    if (h->d_in) (void)hipFree(h->d_in);
-    if (h->d_out) (void)hipFree(h->d_out);
+    h->d_in.release();
+    h->d_out.release();
     if (h->fwd) (void)mi355_fft_destroy(h->fwd);
     if (h->inv) (void)mi355_fft_destroy(h->inv);
     for (void *w : h->d_ws)
@@ -397,39 +396,30 @@ extern "C" int mi355_xcorr_fft_work(mi355_xcorr_fft *h, int nframes, const void 
     MI355_REQUIRE(h != nullptr, "handle is NULL");
     if (nframes <= 0) return MI355_OK;
     MI355_REQUIRE(inputs && outputs, "NULL pointer arrays");
+    for (int s = 0; s < h->num_inputs; s++) {
+        MI355_REQUIRE(inputs[s] != nullptr, "NULL input buffer");
+        MI355_REQUIRE(s == 0 || outputs[s - 1] != nullptr, "NULL output buffer");
+    }
     std::lock_guard<std::mutex> g(h->ctx->lock);
     MI355_HIP(hipSetDevice(h->ctx->device));
     const size_t in_frame = 8 * (size_t)h->n, out_frame = 4 * (size_t)h->n;
     // chunks of frames so the staging stays bounded (64 MiB of input per chunk at most)
-    size_t chunk = (64u << 20) / (in_frame * (size_t)h->num_inputs);
-    if (chunk < 1) chunk = 1;
-    if (chunk > (size_t)nframes) chunk = (size_t)nframes;
-    if (chunk > h->cap_frames) {
-        if (h->d_in) (void)hipFree(h->d_in);
-        if (h->d_out) (void)hipFree(h->d_out);
-        h->d_in = h->d_out = nullptr; h->cap_frames = 0;
-        MI355_HIP(hipMalloc(&h->d_in, chunk * in_frame * (size_t)h->num_inputs));
-        MI355_HIP(hipMalloc(&h->d_out, chunk * out_frame * (size_t)(h->num_inputs - 1)));
-        h->cap_frames = chunk;
-    }
-    hipStream_t st = h->ctx->stream[0];
-    for (size_t f0 = 0; f0 < (size_t)nframes; f0 += chunk) {
-        const size_t nf = (size_t)nframes - f0 < chunk ? (size_t)nframes - f0 : chunk;
+    const size_t chunk = mi355_piece_units(((size_t)64 << 20) / (in_frame * (size_t)h->num_inputs), (size_t)nframes);
+    int rc;
+    if ((rc = h->d_in.reserve(chunk * in_frame * (size_t)h->num_inputs))) return rc;
+    if ((rc = h->d_out.reserve(chunk * out_frame * (size_t)(h->num_inputs - 1)))) return rc;
+    return mi355_pageable_run(h->ctx, (size_t)nframes, chunk, [&](size_t f0, size_t nf, hipStream_t st) -> int {
         XcArgs a{};
         for (int s = 0; s < h->num_inputs; s++) {
-            MI355_REQUIRE(inputs[s] != nullptr, "NULL input buffer");
-            char *d = (char *)h->d_in + (size_t)s * chunk * in_frame;
+            char *d = (char *)h->d_in.get() + (size_t)s * chunk * in_frame;
             MI355_HIP(hipMemcpyAsync(d, (const char *)inputs[s] + f0 * in_frame, nf * in_frame, hipMemcpyHostToDevice, st));
             a.in[s] = (const c32 *)d;
-            if (s >= 1) a.out[s] = (float *)((char *)h->d_out + (size_t)(s - 1) * chunk * out_frame);
+            if (s >= 1) a.out[s] = (float *)((char *)h->d_out.get() + (size_t)(s - 1) * chunk * out_frame);
         }
-        int rc = launch_xcorr(h, a, (int)nf, st);
-        if (rc) return rc;
-        for (int s = 1; s < h->num_inputs; s++) {
-            MI355_REQUIRE(outputs[s - 1] != nullptr, "NULL output buffer");
+        const int lrc = launch_xcorr(h, a, (int)nf, st);
+        if (lrc) return lrc;
+        for (int s = 1; s < h->num_inputs; s++)
             MI355_HIP(hipMemcpyAsync((char *)outputs[s - 1] + f0 * out_frame, a.out[s], nf * out_frame, hipMemcpyDeviceToHost, st));
-        }
-        MI355_HIP(hipStreamSynchronize(st));
-    }
-    return MI355_OK;
+        return MI355_OK;
+    });
 }

@@ -1,5 +1,6 @@
-// Stand-alone program around HostPipe (csrc/common.h, csrc/hostpipe.hip) for tests/test_hostpipe_host.py: the staging pipeline that
-// drives every block's host-pointer work(), over SYNCHRONOUS HOST STUBS of the dozen HIP runtime calls it makes, no device.  "Device"
+// Stand-alone program around HostPipe, mi355_pageable_run and DevBuf (csrc/common.h, csrc/hostpipe.hip) for
+// tests/test_hostpipe_host.py: the two drivers behind every block's host-pointer work(), the staging pipeline first and the piece
+// loop of the pageable paths after it, over SYNCHRONOUS HOST STUBS of the dozen HIP runtime calls they make, no device.  "Device"
 // and pinned buffers are heap blocks of exactly the size ensure() asked for and the caller's buffers are heap blocks of exactly the
 // size describe() names, so under -fsanitize=address,undefined a copy of one byte too many is caught.  The "kernel" is a host
 // function: output byte j of chunk ci = input byte j (xor the second input's) xor key(ci).  Every stubbed call is logged, and the
@@ -10,11 +11,13 @@
 #include <string>
 
 // ---- the log -------------------------------------------------------------------------------------------------------------------
-enum Kind { EV_RECORD, EV_SYNC, COPY_IN, COPY_OUT, H2D, D2H, STREAM_SYNC, DIRECT_SYNC, LAUNCH, DELIVER, FAIL };
+enum Kind { EV_RECORD, EV_SYNC, COPY_IN, COPY_OUT, H2D, D2H, STREAM_SYNC, DIRECT_SYNC, LAUNCH, DELIVER, FAIL, DEV_MALLOC, DEV_FREE };
 struct Entry { Kind kind; int slot; size_t arg; };
 static std::vector<Entry> g_log;
-static HostPipe *g_pipe = nullptr;
+static HostPipe *g_pipe = nullptr;  // nullptr: the pageable driver and DevBuf are under test, and hipMalloc / hipFree are logged too
 static int g_memcpy_calls = 0, g_memcpy_fail_at = -1;  // the g_memcpy_fail_at-th hipMemcpyAsync fails, once
+static int g_malloc_calls = 0, g_malloc_fail_at = -1;  // the same for hipMalloc
+static int g_sync_calls = 0, g_sync_fail_at = -1;      // and for hipStreamSynchronize
 static std::string g_err;
 
 static int slot_of_event(hipEvent_t e)
@@ -72,8 +75,24 @@ extern "C" {
 hipError_t hipSetDevice(int) { return hipSuccess; }
 hipError_t hipGetLastError(void) { return hipSuccess; }
 const char *hipGetErrorString(hipError_t e) { return e == hipSuccess ? "no error" : "stub error"; }
-hipError_t hipMalloc(void **p, size_t bytes) { *p = malloc(bytes); g_live_allocs++; return *p ? hipSuccess : hipErrorOutOfMemory; }
-hipError_t hipFree(void *p) { if (p) g_live_allocs--; free(p); return hipSuccess; }
+hipError_t hipMalloc(void **p, size_t bytes)
+{
+    if (g_malloc_calls++ == g_malloc_fail_at) {
+        g_log.push_back({FAIL, -1, bytes});
+        return hipErrorOutOfMemory;
+    }
+    if (!g_pipe) g_log.push_back({DEV_MALLOC, -1, bytes});
+    *p = malloc(bytes);
+    g_live_allocs++;
+    return *p ? hipSuccess : hipErrorOutOfMemory;
+}
+hipError_t hipFree(void *p)
+{
+    if (!g_pipe) g_log.push_back({DEV_FREE, -1, 0});
+    if (p) g_live_allocs--;
+    free(p);
+    return hipSuccess;
+}
 hipError_t hipHostMalloc(void **p, size_t bytes, unsigned int) { return hipMalloc(p, bytes); }
 hipError_t hipHostFree(void *p) { return hipFree(p); }
 hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned) { *e = (hipEvent_t)malloc(1); g_live_events++; return hipSuccess; }
@@ -91,7 +110,7 @@ hipError_t hipEventSynchronize(hipEvent_t e)
 hipError_t hipStreamSynchronize(hipStream_t st)
 {
     g_log.push_back({STREAM_SYNC, -1, (size_t)st});
-    return hipSuccess;
+    return g_sync_calls++ == g_sync_fail_at ? hipErrorUnknown : hipSuccess;
 }
 hipError_t hipMemcpyAsync(void *dst, const void *src, size_t bytes, hipMemcpyKind kind, hipStream_t st)
 {
@@ -100,7 +119,7 @@ hipError_t hipMemcpyAsync(void *dst, const void *src, size_t bytes, hipMemcpyKin
         return hipErrorInvalidValue;
     }
     const bool in = kind == hipMemcpyHostToDevice;
-    g_log.push_back({in ? H2D : D2H, slot_of(g_pipe->d_in, g_pipe->d_out, in ? dst : src), (size_t)st});
+    g_log.push_back({in ? H2D : D2H, g_pipe ? slot_of(g_pipe->d_in, g_pipe->d_out, in ? dst : src) : -1, (size_t)st});
     memcpy(dst, src, bytes);
     return hipSuccess;
 }
@@ -241,6 +260,207 @@ static int check_order()
     return 0;
 }
 
+// ---- one call through the piece loop of the pageable paths --------------------------------------------------------------------
+// A unit is kUnit bytes of each input and of output 0 and kUnit / 2 bytes of output 1.  Input a carries kHist bytes of history in
+// front, which every piece sends again (as the synthesizer and clFEngine do); input b carries none.  The "kernel":
+//   out0[j] = a[j] ^ a[j + kHist] ^ b[j],   out1[j] = b[2 j] ^ 0x5A   -- no piece number in it: any split gives the same bytes.
+// The caller's arrays and the DevBufs are heap blocks of exactly the size needed, so ASan sees a copy of one byte too many.
+static const size_t kUnit = 100, kHist = 30;
+
+struct PCall {
+    long long total = 1, want = 1;
+    long fail_launch_at = -1;  // the launch of this piece returns MI355_ERR_UNSUPPORTED
+    // results
+    int rc = 0;
+    long long per = 0;         // units per piece as clamped
+    std::vector<long long> firsts, counts;
+    std::vector<unsigned char> out0, out1, want0, want1;
+};
+
+static int run_pcall(mi355_ctx *ctx, PCall &c)
+{
+    g_log.clear();
+    g_memcpy_calls = g_sync_calls = 0;
+    const size_t total = (size_t)c.total;
+    unsigned char *a = (unsigned char *)malloc(total * kUnit + kHist), *b = (unsigned char *)malloc(total * kUnit);
+    for (size_t j = 0; j < total * kUnit + kHist; j++) a[j] = (unsigned char)(j * 7 + 3);
+    for (size_t j = 0; j < total * kUnit; j++) b[j] = (unsigned char)(j * 13 + 5);
+    unsigned char *o0 = (unsigned char *)malloc(total * kUnit), *o1 = (unsigned char *)malloc(total * kUnit / 2);
+    memset(o0, 0xEE, total * kUnit);
+    memset(o1, 0xEE, total * kUnit / 2);
+    c.per = mi355_piece_units(c.want, c.total);
+    DevBuf da, db, d0, d1;
+    const size_t per = (size_t)c.per;
+    CHECK(da.reserve(per * kUnit + kHist) == MI355_OK && db.reserve(per * kUnit) == MI355_OK);
+    CHECK(d0.reserve(per * kUnit) == MI355_OK && d1.reserve(per * kUnit / 2) == MI355_OK);
+    g_log.clear();
+    long npiece = 0;
+    c.rc = mi355_pageable_run(ctx, c.total, c.want, [&](long long first, long long n, hipStream_t st) -> int {
+        c.firsts.push_back(first);
+        c.counts.push_back(n);
+        const size_t f = (size_t)first * kUnit, bytes = (size_t)n * kUnit;
+        MI355_HIP(hipMemcpyAsync(da.get(), a + f, bytes + kHist, hipMemcpyHostToDevice, st));
+        MI355_HIP(hipMemcpyAsync(db.get(), b + f, bytes, hipMemcpyHostToDevice, st));
+        if (npiece++ == c.fail_launch_at) {
+            g_log.push_back({FAIL, -1, (size_t)first});
+            return MI355_ERR_UNSUPPORTED;
+        }
+        g_log.push_back({LAUNCH, -1, (size_t)st});
+        const unsigned char *x = (const unsigned char *)da.get(), *y = (const unsigned char *)db.get();
+        for (size_t j = 0; j < bytes; j++) ((unsigned char *)d0.get())[j] = x[j] ^ x[j + kHist] ^ y[j];
+        for (size_t j = 0; j < bytes / 2; j++) ((unsigned char *)d1.get())[j] = y[2 * j] ^ 0x5A;
+        MI355_HIP(hipMemcpyAsync(o0 + f, d0.get(), bytes, hipMemcpyDeviceToHost, st));
+        MI355_HIP(hipMemcpyAsync(o1 + f / 2, d1.get(), bytes / 2, hipMemcpyDeviceToHost, st));
+        return MI355_OK;
+    });
+    c.out0.assign(o0, o0 + total * kUnit);
+    c.out1.assign(o1, o1 + total * kUnit / 2);
+    c.want0.resize(total * kUnit);
+    c.want1.resize(total * kUnit / 2);
+    for (size_t j = 0; j < total * kUnit; j++) c.want0[j] = a[j] ^ a[j + kHist] ^ b[j];
+    for (size_t j = 0; j < total * kUnit / 2; j++) c.want1[j] = b[2 * j] ^ 0x5A;
+    const std::vector<Entry> log = g_log;  // of the run alone
+    for (DevBuf *d : {&da, &db, &d0, &d1}) d->release();
+    g_log = log;
+    for (unsigned char *p : {a, b, o0, o1}) free(p);
+    return 0;
+}
+
+// units [u0, u1) of output `which` hold the kernel's result / still hold the fill they had before the call
+static bool p_done(const PCall &c, int which, long long u0, long long u1)
+{
+    const size_t w = which ? kUnit / 2 : kUnit;
+    return memcmp((which ? c.out1 : c.out0).data() + u0 * w, (which ? c.want1 : c.want0).data() + u0 * w, (size_t)(u1 - u0) * w) == 0;
+}
+static bool p_untouched(const PCall &c, int which, long long u0, long long u1)
+{
+    const size_t w = which ? kUnit / 2 : kUnit;
+    for (size_t j = (size_t)u0 * w; j < (size_t)u1 * w; j++)
+        if ((which ? c.out1 : c.out0)[j] != 0xEE) return false;
+    return true;
+}
+static bool log_is(std::initializer_list<Kind> kinds, size_t from)
+{
+    size_t i = from;
+    for (Kind k : kinds)
+        if (i >= g_log.size() || g_log[i++].kind != k) return false;
+    return true;
+}
+
+static int pageable_cases(mi355_ctx *ctx)
+{
+    const long long kPer = 4, kLast = 3;  // units of a full piece and of the ragged last one
+    // 1 to 5 pieces: every output byte, and per piece H2D H2D LAUNCH D2H D2H STREAM_SYNC on ctx->stream[0], nothing else
+    for (long long np = 1; np <= 5; np++) {
+        PCall c;
+        c.total = (np - 1) * kPer + kLast;
+        c.want = kPer;
+        CHECK(run_pcall(ctx, c) == 0);
+        CHECK(c.rc == MI355_OK && c.out0 == c.want0 && c.out1 == c.want1);
+        CHECK((long long)c.firsts.size() == np && g_log.size() == (size_t)np * 6);
+        for (long long i = 0; i < np; i++) {
+            CHECK(c.firsts[i] == i * c.per && c.counts[i] == (i + 1 == np ? kLast : kPer));
+            CHECK(log_is({H2D, H2D, LAUNCH, D2H, D2H, STREAM_SYNC}, (size_t)i * 6));
+        }
+        for (const Entry &e : g_log) CHECK(e.kind == LAUNCH || e.kind == H2D || e.kind == D2H || e.kind == STREAM_SYNC);
+        for (const Entry &e : g_log) CHECK((hipStream_t)e.arg == ctx->stream[0]);
+    }
+    // a total smaller than the wanted piece is one piece of `total` units; a wanted piece of 0 is held to one unit, so it is one piece
+    // of `total` units for total = 1 and `total` pieces of one unit otherwise (min(max(want, 1), total))
+    {
+        PCall c;
+        c.total = 3;
+        c.want = 1000;
+        CHECK(run_pcall(ctx, c) == 0);
+        CHECK(c.rc == MI355_OK && c.per == 3 && c.firsts.size() == 1 && c.counts[0] == 3 && c.out0 == c.want0 && c.out1 == c.want1);
+        for (long long total : {1ll, 3ll})
+            for (long long want : {0ll, -5ll}) {
+                PCall z;
+                z.total = total;
+                z.want = want;
+                CHECK(run_pcall(ctx, z) == 0);
+                CHECK(z.rc == MI355_OK && z.per == 1 && (long long)z.firsts.size() == total && z.out0 == z.want0 && z.out1 == z.want1);
+                for (long long n : z.counts) CHECK(n == 1);
+            }
+        CHECK(mi355_piece_units((size_t)0, (size_t)7) == 1 && mi355_piece_units((size_t)9, (size_t)7) == 7 && mi355_piece_units(5, 7) == 5);
+    }
+    // a launch that fails in piece k of 4: its code comes back, the stream is waited for behind the failure, nothing follows that wait,
+    // and no output byte of a piece >= k is touched
+    for (long k = 0; k < 4; k++) {
+        PCall c;
+        c.total = 3 * kPer + kLast;
+        c.want = kPer;
+        c.fail_launch_at = k;
+        CHECK(run_pcall(ctx, c) == 0);
+        CHECK(c.rc == MI355_ERR_UNSUPPORTED && (long)c.firsts.size() == k + 1);
+        CHECK(g_log.size() == (size_t)k * 6 + 4 && log_is({H2D, H2D, FAIL, STREAM_SYNC}, (size_t)k * 6));
+        for (int which = 0; which <= 1; which++) CHECK(p_done(c, which, 0, k * kPer) && p_untouched(c, which, k * kPer, c.total));
+    }
+    // the n-th hipMemcpyAsync failing, every n of a four-piece call (four copies per piece): MI355_ERR_HIP and the same drain.  The
+    // outputs of the pieces behind the failed one are untouched, and so is every output of the failed piece that was not queued
+    // before the failure (output 0 was when the copy of output 1 fails).
+    for (int n = 0; n < 16; n++) {
+        PCall c;
+        c.total = 3 * kPer + kLast;
+        c.want = kPer;
+        g_memcpy_fail_at = n;
+        CHECK(run_pcall(ctx, c) == 0);
+        g_memcpy_fail_at = -1;
+        const long long k = n / 4, u0 = k * kPer, u1 = k == 3 ? c.total : u0 + kPer;
+        CHECK(c.rc == MI355_ERR_HIP && g_err.find("hipMemcpyAsync") != std::string::npos && (long long)c.firsts.size() == k + 1);
+        CHECK(count(FAIL) == 1 && g_log.size() >= 2 && g_log[g_log.size() - 2].kind == FAIL && g_log.back().kind == STREAM_SYNC);
+        CHECK(g_log.size() == (size_t)k * 6 + (n % 4 < 2 ? n % 4 : n % 4 + 1) + 2);
+        for (int which = 0; which <= 1; which++) CHECK(p_done(c, which, 0, u0) && p_untouched(c, which, u1, c.total));
+        CHECK(n % 4 == 3 ? p_done(c, 0, u0, u1) : p_untouched(c, 0, u0, u1));
+        CHECK(p_untouched(c, 1, u0, u1));
+    }
+    // the wait behind piece 1 failing: one more wait, MI355_ERR_HIP, no third piece
+    {
+        PCall c;
+        c.total = 3 * kPer + kLast;
+        c.want = kPer;
+        g_sync_fail_at = 1;
+        CHECK(run_pcall(ctx, c) == 0);
+        g_sync_fail_at = -1;
+        CHECK(c.rc == MI355_ERR_HIP && g_err.find("hipStreamSynchronize") != std::string::npos && c.firsts.size() == 2);
+        CHECK(g_log.size() == 13 && log_is({H2D, H2D, LAUNCH, D2H, D2H, STREAM_SYNC, STREAM_SYNC}, 6));
+        for (int which = 0; which <= 1; which++) CHECK(p_untouched(c, which, 2 * kPer, c.total));
+    }
+    return 0;
+}
+
+static int devbuf_cases()
+{
+    DevBuf d;
+    CHECK(d.get() == nullptr && d.bytes() == 0);
+    g_log.clear();
+    CHECK(d.reserve(0) == MI355_OK && d.get() == nullptr && g_log.empty());
+    CHECK(d.reserve(100) == MI355_OK && d.get() != nullptr && d.bytes() == 100);
+    CHECK(g_log.size() == 1 && g_log[0].kind == DEV_MALLOC && g_log[0].arg == 100);
+    memset(d.get(), 1, 100);  // exactly that many bytes are there
+    // a smaller or equal reserve keeps the block
+    void *const p = d.get();
+    CHECK(d.reserve(100) == MI355_OK && d.reserve(7) == MI355_OK && d.get() == p && d.bytes() == 100 && g_log.size() == 1);
+    // a larger one frees first, then allocates
+    CHECK(d.reserve(101) == MI355_OK && d.bytes() == 101 && g_live_allocs == 1);
+    CHECK(g_log.size() == 3 && g_log[1].kind == DEV_FREE && g_log[2].kind == DEV_MALLOC && g_log[2].arg == 101);
+    memset(d.get(), 2, 101);
+    // a failed allocation leaves the buffer empty (the old block is gone), and the next reserve works
+    g_malloc_fail_at = g_malloc_calls;
+    CHECK(d.reserve(500) == MI355_ERR_HIP && d.get() == nullptr && d.bytes() == 0 && g_live_allocs == 0);
+    CHECK(g_err.find("hipMalloc") != std::string::npos);
+    g_malloc_fail_at = -1;
+    CHECK(d.reserve(50) == MI355_OK && d.get() != nullptr && d.bytes() == 50 && g_live_allocs == 1);
+    memset(d.get(), 3, 50);
+    d.release();
+    CHECK(d.get() == nullptr && d.bytes() == 0 && g_live_allocs == 0);
+    d.release();  // twice is harmless
+    CHECK(d.reserve(10) == MI355_OK && d.bytes() == 10);
+    d.release();
+    CHECK(g_live_allocs == 0);
+    return 0;
+}
+
 int main()
 {
     mi355_ctx ctx;
@@ -346,6 +566,10 @@ int main()
             }
 
     CHECK(g_live_allocs == 0 && g_live_events == 0);
+
+    CHECK(pageable_cases(&ctx) == 0);
+    CHECK(devbuf_cases() == 0);
+    CHECK(g_live_allocs == 0);
     printf("hostpipe host ok\n");
     return 0;
 }

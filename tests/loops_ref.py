@@ -188,6 +188,25 @@ def costas_long_expected():
     return _cache["longref"]
 
 
+# (order, streams, items per stream) of the smallest host call that runs three pieces: a piece of the host path is 2^21 items over all
+# streams, here 32768 per stream, so two full pieces and one of three items
+COSTAS_PIECES = (4, 64, 2 * 32768 + 3)
+
+
+def costas_pieces_input():
+    if "pieces" not in _cache:
+        order, streams, n = COSTAS_PIECES
+        _cache["pieces"] = psk(np.random.default_rng(78), order, n, streams)
+    return _cache["pieces"]
+
+
+def costas_pieces_expected():
+    if "piecesref" not in _cache:
+        order, streams, _ = COSTAS_PIECES
+        _cache["piecesref"] = costas(costas_pieces_input()[0], order, LOOP_BW, streams)
+    return _cache["piecesref"]
+
+
 SIG_N = (1, 7, 64, 1000, 4099, 1 << 20)
 SIG_RATIOS = (0.01234, -0.37, 0.5, 1e-7)      # freq / samp_rate
 SIG_AMPS = (1.0, 1000.5)

@@ -335,6 +335,33 @@ def test_host_work_equals_device_work(gpu, pkg, S, npol, F, P, T):
         blk.work(T + 1, xs, [np.zeros((T + 1) * blk.frame_bytes(), np.int8)])
 
 
+def test_host_work_in_two_pieces(gpu, pkg):
+    """A piece of the host path is 64 MiB of input over all inputs.  2 stations of 2 polarisations, 16 channels, P = 4 and
+    64 MiB / (8 * 16 * 4) + 3 frames: one full piece and one of three frames, which sends the three frames of history it shares with
+    the first again.  The bytes and the clip counts of ONE work_device call on either route, and the float64 reference."""
+    S, npol, F, P = 2, 2, 16, 4
+    R = S * npol
+    T = (64 << 20) // (8 * F * R) + 3
+    rng = np.random.default_rng(4242)
+    items = (T + P - 1) * F
+    xs = [(rng.standard_normal(items) + 1j * rng.standard_normal(items)).astype(np.complex64) for _ in range(R)]
+    h = ref.sinc_taps(F, P)
+    # unit-variance components through the bank and the transform come out with variance sum h^2: 30 rms per output component, with
+    # the ripple of _case, so that some components clip
+    g = (30.0 / np.sqrt((h.astype(np.float64) ** 2).sum()) * (1.0 + 0.1 * np.cos(2 * np.pi * np.arange(F) / F + np.arange(R)[:, None]))).astype(np.float32)
+    res = ref.fengine(xs, h, g, S, npol, F, P, True, T)
+    dev, blk = (pkg.clFEngine(*GPU_ARGS, npol, S, F, h, P, True, g) for _ in range(2))
+    for _ in zip(_routes(dev, F, P), _routes(blk, F, P)):
+        want = _run(dev, xs, T)
+        y = np.full(T * blk.frame_bytes(), -128, np.int8)
+        assert blk.work(T, xs, [y]) == T
+        y = y.reshape(T, S, F, npol, 2)
+        assert np.array_equal(y, want), blk.route()
+        clips = blk.clips(reset=True)
+        assert np.array_equal(clips, dev.clips(reset=True)) and clips.any(), blk.route()
+        _compare(y, res, "two pieces, %s" % blk.route())
+
+
 # ---- 7. the chain ---------------------------------------------------------------------------------------------------------------
 def test_frames_feed_the_xengine_and_the_beamformer(gpu, pkg):
     """the device's own frames go to clXEngine (BYTE) and to clBeamformer (VOLTAGE) without leaving the device; both are compared with

@@ -4,7 +4,13 @@ bookkeeping runs on the CPU over synchronous host stubs of the HIP runtime calls
 (tests/hostpipe_host_main.cc): a program of its own, nothing loaded into python.  Placement on exact-size buffers over 1 .. 9 chunks
 and 1, 2 and 4 slots, the wait before a slot is refilled, zero-byte outputs, the drain after a failed launch or runtime call, and
 custom delivery.  The blocks themselves run through it on the GPU (tests/test_device_bounds_gpu.py HOST_CASES and each block's
-multi-chunk host test)."""
+multi-chunk host test).
+
+The same program then drives mi355_pageable_run, the piece loop of the seven blocks that copy from pageable memory, and DevBuf,
+their device scratch: 1 .. 5 pieces with a ragged last one over two inputs (one with a history overlap) and two outputs on
+exact-size buffers, the order H2D.. LAUNCH D2H.. STREAM_SYNC per piece, the clamp of the piece size, the wait behind a failed
+launch, a failed copy (every one of a call's sixteen) and a failed wait, with nothing logged after it and no output byte of a later
+piece touched; and DevBuf's keep / free-then-allocate / failed-allocation / release behaviour against the live-allocation count."""
 import os
 import subprocess
 

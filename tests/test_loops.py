@@ -114,6 +114,15 @@ def test_the_start_state_case_is_stable():
     assert np.abs(noisy[1] - clean[1]).max() <= 0.1 * COSTAS_TOL
 
 
+def test_the_three_piece_case_is_stable():
+    order, streams, _ = ref.COSTAS_PIECES
+    x, _ = ref.costas_pieces_input()
+    clean = ref.costas_pieces_expected()
+    noisy = ref.costas(x, order, ref.LOOP_BW, streams, trig_noise=1e-9, rng=np.random.default_rng(8))
+    assert np.abs(noisy[0] - clean[0]).max() <= 0.1 * COSTAS_TOL * float(np.abs(x).max())
+    assert np.abs(noisy[1] - clean[1]).max() <= 0.1 * COSTAS_TOL
+
+
 def test_the_long_case_is_stable_and_locks():
     x, off = ref.costas_long_input()
     clean = ref.costas_long_expected()

@@ -1,5 +1,5 @@
 """clSignalSource and clCostasLoop on the device against the float64 restatement (tests/loops_ref.py): single calls, consecutive
-calls, chunking, streams, guard bands, short tensors, a source -> multiply -> loop chain, the pybind blocks and the CLI.
+calls, chunking, streams, guard bands, host calls of more than one piece, short tensors, a source -> multiply -> loop chain, the pybind blocks and the CLI.
 
 Tolerances (derived, not fitted):
   signal source, complex / float   |got - ref| <= 2^-22 |A|: the result is the float rounding of a double (half a float ulp at
@@ -120,6 +120,30 @@ def test_signal_source_consecutive_calls_setters_and_host_path(gpu, kind):
     assert blk.work(n, [], [host]) == n
     _check_sig(host, want, amp)
     assert blk.get_state()[0] == pos
+
+
+HOST_PIECE = 1 << 21   # items of a piece of either block's host path, over all streams (csrc/loops.hip kHostChunkItems)
+
+
+@pytest.mark.parametrize("kind", ["complex", "float-sin"])
+def test_signal_source_host_path_in_two_pieces(gpu, kind):
+    """work(2^21 + 5): one full piece and one of five items, whose first item is item 2^21 of the call.  The bits of one
+    work_device call from the same phase, the same state afterwards, and the restatement.  (The frequency keeps the largest
+    argument, 1.6e5 rad, below the 2^22 rad of the tolerance's derivation.)"""
+    dtype, wave, npdt = KINDS[kind]
+    ratio, amp, n = 0.01234, 1000.5, HOST_PIECE + 5
+    inc = ref.sig_inc(ratio * ref.SIG_SAMP_RATE, ref.SIG_SAMP_RATE)
+    dev, blk = _source(gpu, dtype, wave, ratio, amp), _source(gpu, dtype, wave, ratio, amp)
+    dev.set_phase(1.25)
+    blk.set_phase(1.25)
+    one = _gen(dev, n, npdt)
+    host = np.full(n, np.nan, npdt)
+    assert blk.work(n, [], [host]) == n
+    assert np.array_equal(host.view(np.uint32), one.view(np.uint32))
+    assert blk.get_state() == dev.get_state()
+    want, pos = ref.sig_call(1.25, inc, n, amp, kind.split("-")[0], wave)
+    _check_sig(host, want, amp)
+    assert blk.get_state() == (pos, inc)
 
 
 @pytest.mark.parametrize("kind,offset", [("complex", 0), ("complex", 1), ("float-sin", 0), ("float-sin", 1), ("float-sin", 3),
@@ -248,6 +272,27 @@ def test_costas_chunks_repeats_and_streams_are_bit_identical(gpu, order, streams
     host, host_f = np.empty(n * streams, np.complex64), np.empty(n * streams, np.float32)
     assert blk.work(n, [x], [host, host_f]) == n
     assert np.array_equal(host.view(np.uint32), one.view(np.uint32)) and np.array_equal(host_f.view(np.uint32), one_f.view(np.uint32))
+
+
+def test_costas_host_path_in_three_pieces(gpu):
+    """64 streams, 2 * 32768 + 3 items each: the host path runs two pieces of 2^21 / 64 items per stream and one of three.  With the
+    frequency output: output, frequency output and final state are the bits of ONE work_device call, and the whole array is held to
+    the restatement (2.8 s of CPU, once)."""
+    order, streams, n = ref.COSTAS_PIECES
+    assert (HOST_PIECE // streams) * 2 + 3 == n
+    x, _ = ref.costas_pieces_input()
+    dev = _loop(gpu, order, streams)
+    one, one_f = _run_loop(dev, x, n)
+    blk = _loop(gpu, order, streams)
+    host, host_f = np.full(n * streams, np.nan, np.complex64), np.full(n * streams, np.nan, np.float32)
+    assert blk.work(n, [x], [host, host_f]) == n
+    assert np.array_equal(host.view(np.uint32), one.view(np.uint32)) and np.array_equal(host_f.view(np.uint32), one_f.view(np.uint32))
+    state = blk.get_state()
+    for a, b in zip(state, dev.get_state()):
+        assert np.array_equal(a, b)
+    want, want_f, want_state = ref.costas_pieces_expected()
+    _check_costas(host, host_f, want, want_f, x)
+    _close_state(state, want_state)
 
 
 @pytest.mark.parametrize("order", ref.COSTAS_ORDERS)
