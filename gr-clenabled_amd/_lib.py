@@ -262,6 +262,18 @@ def lib():
         "mi355_dedisp_work": (i, [vp, ll, vp, vp, ll]),
         "mi355_dedisp_work_dev": (i, [vp, ll, vp, vp, ll, vp]),
         "mi355_dedisp_delays": (i, [d, d, i, d, vp, i, vp, C.POINTER(i)]),
+        "mi355_psearch_plan": (i, [i, i, i, i, i, llp, llp, llp]),
+        "mi355_psearch_create": (i, [vp, i, i, i, i, i, vp, vp, pp]),
+        "mi355_psearch_destroy": (i, [vp]),
+        "mi355_psearch_set_stats": (i, [vp, vp, vp]),
+        "mi355_psearch_get_stats": (i, [vp, vp, vp, ll]),
+        "mi355_psearch_set_threshold": (i, [vp, f]),
+        "mi355_psearch_history": (ll, [vp]),
+        "mi355_psearch_set_generic": (i, [vp, i]),
+        "mi355_psearch_route": (C.c_char_p, [vp]),
+        "mi355_psearch_work": (i, [vp, ll, vp, ll, vp, vp, ll, vp]),
+        "mi355_psearch_work_dev": (i, [vp, ll, vp, ll, vp, vp, ll, vp, vp]),
+        "mi355_psearch_measure": (i, [vp, ll, vp, ll, i, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)  # AttributeError here = header/library mismatch: fail loudly

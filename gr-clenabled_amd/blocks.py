@@ -1631,3 +1631,165 @@ class clDedisperser(_Block):
                                             _dp(output_items[0], need * 4, "output"), pitch, _torch_stream(self.device)),
               "mi355_dedisp_work_dev")
         return n
+
+
+PSEARCH_TRIAL_MAJOR, PSEARCH_TIME_MAJOR = 0, 1
+PSEARCH_PEAK = np.dtype([("snr", np.float32), ("loc", np.uint32)])
+PSEARCH_CAND = np.dtype([("snr", np.float32), ("loc", np.uint32), ("series", np.uint32), ("block", np.uint32)])
+
+
+class clPulseSearch(_Block):
+    """Exact boxcar single-pulse search behind clDedisperser (beyond the reference module; the contract is in
+    include/mi355_clenabled.h): per series K boxcars of widths 2^0 .. 2^(K-1) summed as a fixed dyadic tree of binary32 additions,
+    snr_k[t] = (b_k[t] - mean 2^k) (inv_sigma c_k), and per (block of block_len outputs, series) the record {snr, loc = (k << 24) | t}
+    of the largest one (ties: smallest k, then smallest t; NaN never takes part).  A call for `nblocks` blocks reads
+    nblocks block_len + history() samples per series: TIME_MAJOR x[t][r][d], or TRIAL_MAJOR x[(r D + d) in_pitch + t].  With
+    max_cands > 0 every peak at or above the threshold (set_threshold, +Inf at first) is also listed: candidates().  Bit-exact on
+    either route, for any split into calls and any alignment."""
+    _destroy = "mi355_psearch_destroy"
+
+    def __init__(self, openCLPlatformType, devSelector, platformId, devId, num_rows, num_trials, num_widths, block_len,
+                 order=PSEARCH_TIME_MAJOR, mean=None, inv_sigma=None, max_cands=0, setDebug=0):
+        self.num_rows, self.num_trials, self.num_widths = int(num_rows), int(num_trials), int(num_widths)
+        self.block_len, self.order, self.max_cands = int(block_len), int(order), int(max_cands)
+        L = lib()
+        fi, hi, pb = C.c_longlong(), C.c_longlong(), C.c_longlong()
+        # argument errors before a context exists
+        check(L.mi355_psearch_plan(self.num_rows, self.num_trials, self.num_widths, self.block_len, self.order, C.byref(fi), C.byref(hi),
+                                   C.byref(pb)), "mi355_psearch_plan")
+        if self.max_cands < 0:
+            raise ValueError("max_cands is negative")
+        self.num_series, self._history = fi.value, hi.value
+        m = None if mean is None else self._per_series(mean, "mean")
+        g = None if inv_sigma is None else self._per_series(inv_sigma, "inv_sigma")
+        super().__init__(openCLPlatformType, devSelector, platformId, devId, setDebug)
+        check(self._L.mi355_psearch_create(self._ctx, self.num_rows, self.num_trials, self.num_widths, self.block_len, self.order,
+                                           None if m is None else _hp(m), None if g is None else _hp(g), C.byref(self._h)),
+              "mi355_psearch_create")
+        self._cands = self._counts = None  # the candidate buffers of the last call: numpy (work) or CUDA tensors (work_device)
+
+    def _per_series(self, a, name):
+        a = np.ascontiguousarray(a)
+        if a.dtype != np.float32:
+            raise TypeError("%s is float32" % name)
+        if a.size != self.num_series:
+            raise ValueError("%s holds %d entries, the geometry has %d series" % (name, a.size, self.num_series))
+        return a
+
+    def history(self):
+        """samples of look-ahead behind a call's last output: 2^(K-1) - 1 (the GR block's history() is this plus one)"""
+        return self._history
+
+    def in_floats(self, nblocks, in_pitch=None):
+        """floats from the first to one past the last a call for nblocks blocks reads"""
+        if nblocks == 0:
+            return 0
+        rows = int(nblocks) * self.block_len + self._history
+        if self.order == PSEARCH_TIME_MAJOR:
+            return rows * self.num_series
+        return (self.num_series - 1) * (rows if in_pitch is None else int(in_pitch)) + rows
+
+    def route(self):
+        return self._L.mi355_psearch_route(self._h).decode()
+
+    def set_generic(self, on):
+        check(self._L.mi355_psearch_set_generic(self._h, 1 if on else 0), "mi355_psearch_set_generic")
+
+    def set_threshold(self, threshold):
+        check(self._L.mi355_psearch_set_threshold(self._h, float(threshold)), "mi355_psearch_set_threshold")
+
+    def set_stats(self, mean, inv_sigma):
+        check(self._L.mi355_psearch_set_stats(self._h, _hp(self._per_series(mean, "mean")), _hp(self._per_series(inv_sigma, "inv_sigma"))),
+              "mi355_psearch_set_stats")
+
+    def stats(self):
+        m, g = np.empty(self.num_series, np.float32), np.empty(self.num_series, np.float32)
+        check(self._L.mi355_psearch_get_stats(self._h, _hp(m), _hp(g), self.num_series), "mi355_psearch_get_stats")
+        return m, g
+
+    def measure(self, x, n, in_pitch=None):
+        """(mean, inv_sigma) of n samples per series of `x` (numpy, or a CUDA tensor) in the block's order, computed in float64; the
+        values are not installed: pass them to set_stats()"""
+        n = int(n)
+        pitch = 0 if self.order == PSEARCH_TIME_MAJOR else (n if in_pitch is None else int(in_pitch))
+        need = n * self.num_series if self.order == PSEARCH_TIME_MAJOR else (self.num_series - 1) * pitch + n
+        m, g = np.empty(self.num_series, np.float32), np.empty(self.num_series, np.float32)
+        if isinstance(x, np.ndarray):
+            x = _host(x, np.float32)
+            _need("input", x, need)
+            p, dev = _hp(x), 0
+        else:
+            p, dev = _dp(x, need * 4, "input"), 1
+        check(self._L.mi355_psearch_measure(self._h, n, p, pitch, dev, _hp(m), _hp(g)), "mi355_psearch_measure")
+        return m, g
+
+    def _pitch(self, nblocks, in_pitch):
+        if self.order == PSEARCH_TIME_MAJOR:
+            return 0 if in_pitch is None else int(in_pitch)
+        return nblocks * self.block_len + self._history if in_pitch is None else int(in_pitch)
+
+    def work(self, noutput_items, input_items, output_items, in_pitch=None):
+        """host buffers: input_items[0] float32; output_items[0] a PSEARCH_PEAK array of noutput_items (blocks) x R x D records"""
+        nb = int(noutput_items)
+        if nb == 0:
+            return 0
+        x = _host(input_items[0], np.float32)
+        pitch = self._pitch(nb, in_pitch)
+        if self.order == PSEARCH_TIME_MAJOR or pitch >= nb * self.block_len + self._history:
+            _need("input", x, self.in_floats(nb, pitch))
+        y = _host(output_items[0], PSEARCH_PEAK, writable=True)
+        _need("output", y, nb * self.num_series)
+        cands = counts = None
+        if self.max_cands:
+            cands, counts = np.zeros(self.max_cands, PSEARCH_CAND), np.zeros(2, np.uint32)
+        check(self._L.mi355_psearch_work(self._h, nb * self.block_len, _hp(x), pitch, _hp(y), None if cands is None else _hp(cands),
+                                         self.max_cands, None if counts is None else _hp(counts)), "mi355_psearch_work")
+        self._cands, self._counts = cands, counts
+        return nb
+
+    def work_device(self, noutput_items, input_items, output_items, in_pitch=None):
+        """CUDA tensors: output_items[0] holds 8 bytes per record (torch.int64, say; see peaks_of); output_items[1:3], if given, are
+        the candidate buffer (16 max_cands bytes) and the two 32-bit counters, otherwise the block keeps its own"""
+        nb = int(noutput_items)
+        if nb == 0:
+            return 0
+        pitch = self._pitch(nb, in_pitch)
+        ok = self.order == PSEARCH_TIME_MAJOR or pitch >= nb * self.block_len + self._history
+        xin = _dp(input_items[0], self.in_floats(nb, pitch) * 4 if ok else None, "input")
+        cands = counts = None
+        if self.max_cands:
+            if len(output_items) >= 3:
+                cands, counts = output_items[1], output_items[2]
+            else:
+                import torch
+                cands = torch.empty(self.max_cands * 4, dtype=torch.int32, device=input_items[0].device)
+                counts = torch.empty(2, dtype=torch.int32, device=input_items[0].device)
+        check(self._L.mi355_psearch_work_dev(self._h, nb * self.block_len, xin, pitch, _dp(output_items[0], nb * self.num_series * 8, "output"),
+                                             None if cands is None else _dp(cands, self.max_cands * 16, "candidates"), self.max_cands,
+                                             None if counts is None else _dp(counts, 8, "counts"), _torch_stream(self.device)),
+              "mi355_psearch_work_dev")
+        self._cands, self._counts = cands, counts
+        return nb
+
+    def search(self, x, nblocks, in_pitch=None):
+        """work() on a numpy input: the peaks as a PSEARCH_PEAK array [nblocks][R][D]"""
+        y = np.empty((int(nblocks), self.num_rows, self.num_trials), PSEARCH_PEAK)
+        self.work(nblocks, [x], [y], in_pitch)
+        return y
+
+    @staticmethod
+    def peaks_of(t):
+        """the records of a work_device output tensor as a flat PSEARCH_PEAK array on the host (waits for the tensor's device)"""
+        return np.ascontiguousarray(t.detach().cpu().numpy()).reshape(-1).view(np.uint8).view(PSEARCH_PEAK)
+
+    def candidates(self):
+        """(records, found) of the last work() / work_device() call: a PSEARCH_CAND array of the min(found, max_cands) stored records in
+        no particular order, and the number found; waits for the device after a work_device() call"""
+        if self._cands is None:
+            return np.zeros(0, PSEARCH_CAND), 0
+        if isinstance(self._cands, np.ndarray):
+            cands, counts = self._cands, self._counts
+        else:
+            counts = self._counts.detach().cpu().numpy().reshape(-1).view(np.uint8).view(np.uint32)
+            cands = np.ascontiguousarray(self._cands.detach().cpu().numpy()).reshape(-1).view(np.uint8).view(PSEARCH_CAND)
+        return cands[:int(counts[1])].copy(), int(counts[0])

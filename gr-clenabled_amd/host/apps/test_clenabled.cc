@@ -977,11 +977,59 @@ static int dedisp_test(size_t n)
     return g_fail ? 1 : 0;
 }
 
+// --psearch-only: clPulseSearch at (R, D, K, Tb) = (2, 5, 4, 32), 3 blocks, on samples from the 32-bit linear congruential generator
+// of --beamform-only (the top byte of each state as int8, as float: every boxcar sum is an exact integer), mean 0 and inv_sigma 1.
+// Prints a "checksum" line that tests/test_psearch_gpu.py compares with the numpy reference: sum_i (i % 7 + 1) (loc_i + bits of
+// snr_i) modulo 2^64 over the peak records in memory order; then one timing row.
+static int psearch_test(size_t n)
+{
+    const int R = 2, D = 5, K = 4, Tb = 32, NB = 3, Hs = (1 << (K - 1)) - 1;
+    uint32_t state = 12345u;
+    auto next = [&]() { state = state * 1664525u + 1013904223u; return (float)(int8_t)(state >> 24); };
+    std::vector<float> x((size_t)(NB * Tb + Hs) * R * D);
+    for (auto &v : x) v = next();
+    {
+        auto ps = clPulseSearch::make(OCLTYPE_GPU, OCLDEVICESELECTOR_SPECIFIC, 0, g_dev, R, D, K, Tb);
+        bool ok = (int)ps->history() == Hs + 1 && ps->lookahead() == Hs && (int)ps->decimation() == Tb && ps->route().compare(0, 10, "tiled time") == 0 &&
+                  ps->mean() == std::vector<float>((size_t)R * D, 0.0f) && ps->inv_sigma() == std::vector<float>((size_t)R * D, 1.0f);
+        std::vector<clPulseSearch::peak> y((size_t)NB * R * D, clPulseSearch::peak{-1e30f, 0u});
+        gr_vector_const_void_star in = {x.data()};
+        gr_vector_void_star out = {y.data()};
+        auto t0 = std::chrono::steady_clock::now();
+        ok = ok && ps->work(NB, in, out) == NB;
+        std::chrono::duration<double> dt = std::chrono::steady_clock::now() - t0;
+        unsigned long long sum = 0;
+        for (size_t i = 0; i < y.size(); i++) {
+            uint32_t bits;
+            memcpy(&bits, &y[i].snr, 4);
+            ok = ok && y[i].snr != -1e30f && (y[i].loc >> 24) < (uint32_t)K && (y[i].loc & 0xFFFFFFu) < (uint32_t)Tb;
+            sum += (unsigned long long)(i % 7 + 1) * ((unsigned long long)y[i].loc + bits);
+        }
+        printf("clPulseSearch checksum %llu\n", sum);
+        report("clPulseSearch (2 rows, 5 trials, 4 widths, blocks of 32)", (size_t)NB, dt.count(), ok);
+    }
+    {
+        const int Rt = 4, Dt = 64, Kt = 8, Tbt = 256, Ht = (1 << (Kt - 1)) - 1, nb = (int)std::max<size_t>(n / 1024, 2);
+        std::vector<float> xt((size_t)(nb * Tbt + Ht) * Rt * Dt, 0.5f);
+        auto ps = clPulseSearch::make(OCLTYPE_GPU, OCLDEVICESELECTOR_SPECIFIC, 0, g_dev, Rt, Dt, Kt, Tbt);
+        std::vector<clPulseSearch::peak> y((size_t)nb * Rt * Dt, clPulseSearch::peak{-1.0f, 0u});
+        gr_vector_const_void_star in = {xt.data()};
+        gr_vector_void_star out = {y.data()};
+        int got = 0;
+        const double t = time_calls([&] { got = ps->work(nb, in, out); });
+        // a constant 1/2: snr_k = 2^(k/2) / 2 grows with k, so every peak is the widest boxcar at the block's first sample
+        const uint32_t want = 7u << 24;
+        report("clPulseSearch (4 x 64 series, 8 widths, timing)", (size_t)nb, t,
+               got == nb && y[0].loc == want && y[y.size() / 2].loc == want && y.back().loc == want && y.back().snr > 5.6f && y.back().snr < 5.7f);
+    }
+    return g_fail ? 1 : 0;
+}
+
 int main(int argc, char **argv)
 {
     size_t n = 8192;  // the reference's default block size
     int fft_size = 4096, ntaps = 65;
-    bool only_fft = false, only_xcorrelate = false, xc_complex = false, only_loops = false, only_resampler = false, only_synth = false, only_pspec = false, only_xlate = false, only_beamform = false, only_fengine = false, only_dedisp = false;
+    bool only_fft = false, only_xcorrelate = false, xc_complex = false, only_loops = false, only_resampler = false, only_synth = false, only_pspec = false, only_xlate = false, only_beamform = false, only_fengine = false, only_dedisp = false, only_psearch = false;
     int xc_inputs = 2, xc_maxsearch = 512;
     for (int i = 1; i < argc; i++) {
         if (!strncmp(argv[i], "--device=", 9)) g_dev = atoi(argv[i] + 9);
@@ -999,6 +1047,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--beamform-only")) only_beamform = true;
         else if (!strcmp(argv[i], "--fengine-only")) only_fengine = true;
         else if (!strcmp(argv[i], "--dedisp-only")) only_dedisp = true;
+        else if (!strcmp(argv[i], "--psearch-only")) only_psearch = true;
         else if (!strncmp(argv[i], "--num_inputs=", 13)) xc_inputs = atoi(argv[i] + 13);
         else if (!strncmp(argv[i], "--maxsearch=", 12)) xc_maxsearch = atoi(argv[i] + 12);
         else if (!strcmp(argv[i], "--input_complex")) xc_complex = true;
@@ -1024,8 +1073,9 @@ int main(int argc, char **argv)
                    "       %s --xlate-only [--iterations N] [block size]\n"
                    "       %s --beamform-only [--iterations N] [block size]\n"
                    "       %s --fengine-only [--iterations N] [block size]\n"
-                   "       %s --dedisp-only [--iterations N] [block size]\n",
-                   argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
+                   "       %s --dedisp-only [--iterations N] [block size]\n"
+                   "       %s --psearch-only [--iterations N] [block size]\n",
+                   argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
             return 0;
         } else n = strtoull(argv[i], nullptr, 10);
     }
@@ -1059,6 +1109,10 @@ int main(int argc, char **argv)
     }
     if (only_dedisp) {
         try { return dedisp_test(n); }
+        catch (const std::exception &e) { std::cerr << "error: " << e.what() << std::endl; return 2; }
+    }
+    if (only_psearch) {
+        try { return psearch_test(n); }
         catch (const std::exception &e) { std::cerr << "error: " << e.what() << std::endl; return 2; }
     }
     if (only_xcorrelate) {

@@ -221,5 +221,31 @@ public:
     virtual std::string route() const = 0;  // may change with set_delays()
 };
 
+// gr::clenabled::clPulseSearch -- exact boxcar single-pulse search behind clDedisperser: per series num_widths boxcars of widths
+// 2^0 .. 2^(num_widths - 1) summed as a fixed dyadic tree of binary32 additions, normalised to S/N with a mean and an inverse sigma per
+// series, reduced to one peak per (block of block_len samples, series).  Beyond the reference module; the contract is in
+// mi355_clenabled.h.  A sync_decimator by block_len: one input stream whose item is a time sample of num_rows num_trials floats
+// ([row][trial], the item clDedisperser writes), one output stream whose item is num_rows num_trials peak records of 8 bytes
+// ({float snr; uint32 loc = (k << 24) | t_in_block}), history 2^(num_widths - 1).  mean / inv_sigma: num_rows num_trials floats each;
+// empty vectors at make() are mean 0 and inv_sigma 1.  Candidates are not exposed at this layer (no message port).
+// (No per-block header of this name is installed by this build yet.)
+class CLENABLED_API clPulseSearch : virtual public gr::sync_decimator {
+public:
+    typedef std::shared_ptr<clPulseSearch> sptr;
+    struct peak {
+        float snr;
+        uint32_t loc;
+    };
+    static sptr make(int openCLPlatformType, int devSelector, int platformId, int devId, int num_rows, int num_trials, int num_widths,
+                     int block_len, const std::vector<float> &mean = std::vector<float>(), const std::vector<float> &inv_sigma = std::vector<float>(),
+                     int setDebug = 0);
+    virtual void set_stats(const std::vector<float> &mean, const std::vector<float> &inv_sigma) = 0;  // num_rows num_trials entries each, anything else throws
+    virtual std::vector<float> mean() const = 0;
+    virtual std::vector<float> inv_sigma() const = 0;
+    virtual int lookahead() const = 0;      // 2^(num_widths - 1) - 1
+    virtual void set_generic(bool on) = 0;  // the generic route for every later call
+    virtual std::string route() const = 0;
+};
+
 }  // namespace clenabled
 }  // namespace gr

@@ -474,4 +474,40 @@ PYBIND11_MODULE(clenabled_python, m)
         .def("route", &clDedisperser::route)
         .def("history", [](clDedisperser &b) { return b.history(); })
         .def("work", &call_work<clDedisperser>, py::arg("noutput_items"), py::arg("input_items"), py::arg("output_items"));
+
+    // pulse search (lib/clPulseSearch_impl.cc): input items are time samples of R D floats with 2^(K-1) - 1 samples of look-ahead behind
+    // the call's last block, output items the R D peak records of 8 bytes of one block; the statistics go in and out as float arrays
+    using f32array = py::array_t<float, py::array::c_style | py::array::forcecast>;
+    py::class_<clPulseSearch DECIM_BASES, std::shared_ptr<clPulseSearch>>(m, "clPulseSearch")
+        .def(py::init([](int openCLPlatformType, int devSelector, int platformId, int devId, int num_rows, int num_trials, int num_widths,
+                         int block_len, const f32array &mean, const f32array &inv_sigma, int setDebug) {
+                 return clPulseSearch::make(openCLPlatformType, devSelector, platformId, devId, num_rows, num_trials, num_widths, block_len,
+                                            std::vector<float>(mean.data(), mean.data() + mean.size()),
+                                            std::vector<float>(inv_sigma.data(), inv_sigma.data() + inv_sigma.size()), setDebug);
+             }),
+             py::arg("openCLPlatformType"), py::arg("devSelector"), py::arg("platformId"), py::arg("devId"), py::arg("num_rows"),
+             py::arg("num_trials"), py::arg("num_widths"), py::arg("block_len"), py::arg("mean") = f32array(0),
+             py::arg("inv_sigma") = f32array(0), py::arg("setDebug") = 0)
+        .def("set_stats",
+             [](clPulseSearch &b, const f32array &mean, const f32array &inv_sigma) {
+                 b.set_stats(std::vector<float>(mean.data(), mean.data() + mean.size()),
+                             std::vector<float>(inv_sigma.data(), inv_sigma.data() + inv_sigma.size()));
+             },
+             py::arg("mean"), py::arg("inv_sigma"))
+        .def("mean",
+             [](clPulseSearch &b) {
+                 const std::vector<float> t = b.mean();
+                 return f32array(t.size(), t.data());
+             })
+        .def("inv_sigma",
+             [](clPulseSearch &b) {
+                 const std::vector<float> t = b.inv_sigma();
+                 return f32array(t.size(), t.data());
+             })
+        .def("lookahead", &clPulseSearch::lookahead)
+        .def("set_generic", &clPulseSearch::set_generic, py::arg("on"))
+        .def("route", &clPulseSearch::route)
+        .def("decimation", [](clPulseSearch &b) { return b.decimation(); })
+        .def("history", [](clPulseSearch &b) { return b.history(); })
+        .def("work", &call_work<clPulseSearch>, py::arg("noutput_items"), py::arg("input_items"), py::arg("output_items"));
 }

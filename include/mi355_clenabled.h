@@ -915,6 +915,92 @@ int mi355_dedisp_work_dev(mi355_dedisp *h, long long n, const void *in, void *ou
 int mi355_dedisp_delays(double f0_mhz, double df_mhz, int num_channels, double tsamp_s, const double *dm, int num_trials, int32_t *out,
                         int *max_delay);
 
+/* ------------------------------------------------------------------------------------------------
+ * Pulse search: clPulseSearch, an exact boxcar single-pulse search over the R D dedispersed time series that clDedisperser delivers:
+ * a bank of K boxcar matched filters of widths 2^0 .. 2^(K-1) per series, normalised to S/N, reduced to one peak per (block of Tb
+ * outputs, series) and, optionally, to a list of the peaks at or above a threshold.  Beyond the reference module, which has no such
+ * block (this comment is the contract).  The arithmetic is pinned, so there is no tolerance anywhere except in _measure.
+ *     R = num_rows 1 .. 4096;  D = num_trials 1 .. 4096;  S = R D series, s = r D + d;  K = num_widths 1 .. 13;
+ *     history (look-ahead) Hs = 2^(K-1) - 1;  Tb = block_len 16 .. 2^24 - 1, any integer;
+ *     order = MI355_PSEARCH_TRIAL_MAJOR (0) or MI355_PSEARCH_TIME_MAJOR (1): the two output orders of clDedisperser, same values.
+ * Input: float32.  TRIAL_MAJOR x[s in_pitch + t] with in_pitch >= n + Hs in floats; the floats between n + Hs and in_pitch are never
+ * read.  TIME_MAJOR x[t][r][d], in_pitch must be 0.  A call for n outputs per series reads the n + Hs samples per series that start
+ * at `in` and nothing beyond; n must be a multiple of Tb; n == 0 is a no-op.  Between calls the caller advances `in` by n samples.
+ * Boxcar sums are a dyadic tree, and the tree is the contract:
+ *     b_0[t] = x[t];     b_k[t] = b_(k-1)[t] + b_(k-1)[t + 2^(k-1)]
+ * each one IEEE binary32 addition, round to nearest even, one rounding.  Every b_k[t] is a fixed balanced tree over x[t .. t + 2^k):
+ * a function of those inputs alone, whatever the tiling.  (A left-to-right or prefix-sum evaluation gives other bits and does not
+ * conform.)
+ * Normalisation: two float32 per series, mean[s] and inv_sigma[s], set at _create (NULL: mean 0, inv_sigma 1) and by _set_stats.
+ *     m_k = mean[s] 2^k;   g_k = inv_sigma[s] c_k,  c_k = (k odd ? 0x3F3504F3 : 1.0f) 2^(-floor(k/2)): the binary32 nearest 2^(-k/2)
+ *     snr_k[t] = (b_k[t] - m_k) g_k           one subtraction and one multiplication, each rounded once
+ * Subnormal operands or results are unspecified, as in clDedisperser.
+ * Peaks: one 8-byte record {float snr; uint32 loc} per (block, series), peaks[b][r][d], loc = (k << 24) | t_in_block: the maximum of
+ * snr_k[t] over k < K and the block's Tb output times.  The order is that of a 64-bit key: high word the order-preserving map of the
+ * float's bits (all bits flipped if the sign bit is set, else the sign bit set), low word ~loc; the largest key wins.  So the greatest
+ * S/N wins, +0 is above -0, then the smallest k, then the smallest t.  A NaN snr_k[t] never takes part; a block without a non-NaN
+ * value yields {-Inf, 0xFFFFFFFF}.  +Inf inputs give +Inf peaks where the formula puts them.  A NaN at input sample t0 removes exactly
+ * the snr_k[t] with t0 - 2^k < t <= t0 and nothing else.  The key maximum does not depend on the order of the reduction, so every
+ * reduction shape, 64-bit integer atomicMax across workgroups included, gives the same bits.  There are no float atomics.  (While a
+ * call runs, `peaks` holds its keys: the buffer is initialised, reduced into and decoded in place, all in the call's stream.)
+ * Candidates (cands == NULL skips them): every peak record with snr >= threshold becomes a 16-byte record {float snr; uint32 loc;
+ * uint32 series; uint32 block}, block counted from the call's first block.  threshold: _set_threshold, +Inf by default, NaN refused.
+ * counts[0] = the number found, counted in full; counts[1] = the number stored = min(found, max_cands); records past the capacity are
+ * dropped.  The order of the list is unspecified (an integer atomic counter, zeroed in the stream by the call).  The stored records
+ * are a subset of the true set, and the whole set when found <= max_cands.
+ * Invariance: either route, any split of a stream into calls at block boundaries, any legal alignment (`in` 4-byte; peaks, cands and
+ * counts 8-byte) and any in_pitch give identical peak bits and an identical candidate set.
+ * Routes, fixed at _create by (order, K) and named by _route():
+ *   "tiled trial R=64 D=1024 K=10 Tb=1024 ns=1 w=4096 tt=3585" -- TRIAL_MAJOR, K <= 12: a workgroup stages w = 2048 (K <= 9), 4096
+ *       (K <= 11) or 8192 (K = 12) samples of one series in LDS, builds the levels in place there with its own values in registers
+ *       and delivers tt = w - Hs outputs;
+ *   "tiled time R=64 D=1024 K=10 Tb=1024 ns=32 w=1024 tt=513" -- TIME_MAJOR, K <= 10: the same on ns = 32 series at once, whose
+ *       128-byte runs per time sample are transposed into LDS rows (32 x 1025 floats and the tile's keys: 145 KiB of the 160);
+ *   "generic trial R=1 D=3 K=13 Tb=16" -- TRIAL_MAJOR K = 13, TIME_MAJOR K >= 11 and every handle under _set_generic(h, 1): one thread
+ *       per output walks the tree of its widest boxcar.
+ * Both fused routes hold for every Tb and S.  The route is forced by _set_generic only; there is no environment switch.
+ * Statistics updates: a call enqueued before _set_stats returns uses the old version entirely, a later call the new one entirely
+ * (versioned device buffers; an old version is released behind the event of its last launch; nothing on the work path waits for the
+ * device).  A refused update changes nothing.
+ * Errors (nothing launched): NULL `in` or `peaks`, cands without counts, a misaligned buffer, `in` overlapping an output or two
+ * outputs overlapping, in_pitch < n + Hs (TRIAL_MAJOR) or != 0 (TIME_MAJOR), n < 0 or n % Tb != 0, max_cands < 0, a parameter outside
+ * the ranges above, a NaN threshold: MI355_ERR_INVALID_ARG.  More than 2^40 bytes per buffer and call, or 2^32 blocks and more in
+ * one call: MI355_ERR_UNSUPPORTED.
+ *   _plan           in_floats_per_sample = R D, history = Hs, peaks_per_block = R D; no device; any output pointer may be NULL
+ *   _create         everything that can be told without a device is checked before ctx is touched; mean / inv_sigma: S floats or NULL
+ *   _set_stats      replaces both arrays whole (S floats each, neither NULL);  _get_stats copies them, cap_entries is the size of each
+ *   _set_threshold  the candidate threshold of every later call
+ *   _history        Hs
+ *   _set_generic    on != 0: the generic route for every later call of the handle; 0: back
+ *   _route          valid until the next _set_generic / _destroy of the handle; "" for NULL
+ *   _work           host pointers, blocking: pieces of whole blocks, each sent with its Hs samples of look-ahead; `block` of the
+ *                   candidate records counts from the call's first block, as in _work_dev
+ *   _work_dev       device pointers, enqueue only
+ * mi355_psearch_measure: blocking and off the work path.  `in` (host, or device with in_is_device != 0) holds n >= 1 samples per
+ * series in the handle's order (TRIAL_MAJOR in_pitch >= n, TIME_MAJOR 0); mean[s] and inv_sigma[s] = 1 / sqrt(population variance)
+ * (host arrays of S floats) are computed on the device in float64, two passes, and rounded to float32 once; a variance of 0 gives
+ * inv_sigma 0.  The values are not installed: the caller passes them to _set_stats.  The one entry that is not bit-exact.
+ * ------------------------------------------------------------------------------------------------ */
+#define MI355_PSEARCH_TRIAL_MAJOR 0
+#define MI355_PSEARCH_TIME_MAJOR 1
+typedef struct mi355_psearch mi355_psearch;
+int mi355_psearch_plan(int num_rows, int num_trials, int num_widths, int block_len, int order, long long *in_floats_per_sample,
+                       long long *history, long long *peaks_per_block);
+int mi355_psearch_create(mi355_ctx *ctx, int num_rows, int num_trials, int num_widths, int block_len, int order, const float *mean,
+                         const float *inv_sigma, mi355_psearch **out);
+int mi355_psearch_destroy(mi355_psearch *h);
+int mi355_psearch_set_stats(mi355_psearch *h, const float *mean, const float *inv_sigma);
+int mi355_psearch_get_stats(const mi355_psearch *h, float *mean, float *inv_sigma, long long cap_entries);
+int mi355_psearch_set_threshold(mi355_psearch *h, float threshold);
+long long mi355_psearch_history(const mi355_psearch *h);
+int mi355_psearch_set_generic(mi355_psearch *h, int on);
+const char *mi355_psearch_route(const mi355_psearch *h);
+int mi355_psearch_work(mi355_psearch *h, long long n, const void *in, long long in_pitch, void *peaks, void *cands, long long max_cands,
+                       void *counts);
+int mi355_psearch_work_dev(mi355_psearch *h, long long n, const void *in, long long in_pitch, void *peaks, void *cands, long long max_cands,
+                           void *counts, void *stream);
+int mi355_psearch_measure(mi355_psearch *h, long long n, const void *in, long long in_pitch, int in_is_device, float *mean, float *inv_sigma);
+
 #ifdef __cplusplus
 }
 #endif
