@@ -420,6 +420,12 @@ int mi355_elem_work_dev(mi355_elem *h, size_t n, const void *in0, const void *in
  * fft_size: powers of two 16..4096 run as ONE fused kernel; every other even size up to 4194304 (the reference hands fftSize to
  * clFFT, lib/clxcorrelate_fft_vcf_impl.cc:711-737) runs the reference's steps one after the other over the clFFT transforms of
  * this library; an odd size is refused (the reference would leave the last output of every vector unwritten).  num_inputs 2..32.
+ * Reach: frame f of output s-1 depends on frame f of input 0 and frame f of input s alone -- not on the other frames of the call (however
+ * many frames share a workgroup, wherever the frame sits in the call, whether its group is full or ragged), not on the other signals, and
+ * not on how many signals the call has: a two-input call of (input 0, input s) gives the same bits.  A non-finite item in frame f of input
+ * s >= 1 makes every lag of frame f of output s-1 non-finite; one in frame f of input 0 does that to frame f of every output; every other
+ * frame of every output keeps its bits.  A frame in which either operand is all zero (spectra: also operands whose supports do not meet)
+ * comes out as exact zeros.  work() gives the bits of work_device() (tests/test_xcorr_bounds_gpu.py).
  * ------------------------------------------------------------------------------------------------ */
 int mi355_xcorr_fft_create(mi355_ctx *ctx, int fft_size, int num_inputs, int input_type, mi355_xcorr_fft **out);
 int mi355_xcorr_fft_destroy(mi355_xcorr_fft *h);

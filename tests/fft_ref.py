@@ -1,8 +1,9 @@
 """Numpy float64 yardsticks of clFFT and clxcorrelate_fft_vcf for the sizes the oracle's O(N^2) DFT cannot run, and the per-frame error bounds
-of clFFT (fft_frames64, fft_bound_check, the input kinds they are held on; DESIGN.md, 'Tolerances').  Plain module (no fixtures), shared by
-tests/test_fft_gpu.py, tests/test_fft_bounds_gpu.py, tests/test_xcorr_gpu.py and tests/switch_cases.py (whose child processes import no test
-module); the transforms are tied to the oracle at small lengths in tests/test_fft_gpu.py and tests/test_xcorr_gpu.py, the multiples of the
-bounds are fixed by tests/test_fft_ref.py."""
+of clFFT (fft_frames64, fft_bound_check, the input kinds they are held on; DESIGN.md, 'Tolerances') and the per-frame, per-lag ones of the
+correlator (xcorr_frames64, xcorr_bound_check).  Plain module (no fixtures), shared by tests/test_fft_gpu.py, tests/test_fft_bounds_gpu.py,
+tests/test_xcorr_gpu.py, tests/test_xcorr_bounds_gpu.py and tests/switch_cases.py (whose child processes import no test module); the
+transforms are tied to the oracle at small lengths in tests/test_fft_gpu.py and tests/test_xcorr_gpu.py, the multiples of the bounds are
+fixed by tests/test_fft_ref.py and tests/test_xcorr_ref.py."""
 import numpy as np
 
 
@@ -186,13 +187,90 @@ def tone_bins(n, frames):
     return _edge_then_seeded(n, frames, (1, n // 2, n - 1, 0), 2000 + n)
 
 
-def np_xcorr(n, itype, ins):
-    """The block's definition on numpy's float64 pocketfft (the oracle's O(N^2) DFT cannot run lengths that are not a power of two
-    at these sizes); tied to the oracle at a small length in the test below."""
-    x = [v.astype(np.complex128).reshape(-1, n) for v in ins]
+def xcorr_frames64(n, itype, ins):
+    """clxcorrelate_fft_vcf's definition on numpy's float64 pocketfft, NOT rounded to float.  ins: the complex64 items the block was given
+    (input 0 the reference).  For every signal s >= 1: (|r| with the two halves of every vector exchanged, float64, shape (frames, n);
+    (T, S)), r = ifft(X0 conj(Xs)) n, X = the input (itype 1, spectra) or its forward transform (itype 2, time series), and the per-frame
+    scales of xcorr_bound_check: T_f = ||P_f||_2 of P = X0 conj(Xs), plus sqrt(n) ||x0_f||_2 ||xs_f||_2 for time series; S_f = max_m |r_f[m]|."""
+    x = [np.asarray(v).astype(np.complex128).reshape(-1, n) for v in ins]
     spec = x if itype == 1 else [np.fft.fft(v, axis=1) for v in x]
+    e = [np.sqrt((v.real * v.real + v.imag * v.imag).sum(axis=1)) for v in x]
     outs = []
-    for sp in spec[1:]:
-        r = np.abs(np.fft.ifft(spec[0] * np.conj(sp), axis=1) * n)
-        outs.append(np.concatenate([r[:, n // 2:], r[:, :n // 2]], axis=1).reshape(-1).astype(np.float32))
+    for s in range(1, len(x)):
+        P = spec[0] * np.conj(spec[s])
+        r = np.abs(np.fft.ifft(P, axis=1) * n)
+        T = np.sqrt((P.real * P.real + P.imag * P.imag).sum(axis=1))
+        if itype != 1:
+            T = T + np.sqrt(float(n)) * e[0] * e[s]
+        outs.append((np.concatenate([r[:, n // 2:], r[:, :n // 2]], axis=1), (T, r.max(axis=1))))
     return outs
+
+
+def np_xcorr(n, itype, ins):
+    """xcorr_frames64 flattened and rounded to float (the oracle's O(N^2) DFT cannot run lengths that are not a power of two at these
+    sizes); tied to the oracle at a small length in tests/test_xcorr_gpu.py."""
+    return [mag.reshape(-1).astype(np.float32) for mag, _ in xcorr_frames64(n, itype, ins)]
+
+
+# ---- per-frame, per-lag error bounds of clxcorrelate_fft_vcf (DESIGN.md, 'Tolerances'; the multiples are fixed by tests/test_xcorr_ref.py,
+# never by a GPU result).  (a, b): per lag  |d| <= a unit (T_f + S_f);  per frame  ||d_f||_2 <= b unit sqrt(n) T_f.  Keyed by the clFFT
+# route kind of the transforms underneath (fft_bound_kind): `direct` is the fused kernel and the composed route over power-of-two transforms ----
+# Each is the smallest integer at or above twice the largest figure of the CPU evaluations of that structure: 1.34 / 1.81 units (radix 2 and
+# pocketfft), 2.20 / 1.92 (chirp-z), 2.92 / 3.02 (mixed radix, one pass: the twiddle products), 2.74 / 1.93 (two passes).
+XCORR_MULT = {"direct": (3.0, 4.0), "chirpz": (5.0, 4.0), "mixed_radix": (6.0, 7.0), "mixed_radix_two_passes": (6.0, 4.0)}
+
+
+def xcorr_unit(n, itype):
+    """u sqrt(L) for spectra (one transform), u sqrt(2 L) for time series (two transforms in series), L = ceil(log2 n)"""
+    L = float(int(n - 1).bit_length())
+    return U32 * np.sqrt(L if itype == 1 else 2.0 * L)
+
+
+def xcorr_bound_check(got, ref, scales, n, itype, kind="direct", check=True, what=""):
+    """Every frame f of one output of the correlator (float32 items, any shape) against xcorr_frames64's (|r|, (T, S)) of that signal:
+        per lag      |got - |r||         <= a unit (T_f + S_f)
+        per frame    ||got_f - |r_f|||_2 <= b unit sqrt(n) T_f
+        zero frame   T_f == 0 (either operand's frame all zero; for spectra also disjoint supports): got is exactly zero there
+        non-finite   a non-finite got fails
+    unit = xcorr_unit(n, itype), (a, b) = XCORR_MULT[kind].  T_f is the size of what the inverse transform is given (its rounding error is
+    unit T_f per lag whatever the result sums to) and, for time series, of what the forward transforms' error leaves in the product (which
+    does not shrink when P cancels, as for orthogonal tones); S_f covers the coherent peak, whose own rounding (the magnitude, the last
+    butterflies) is relative to it.  Returns the largest used fraction of each bound (lag, frame); check = True asserts both <= 1 and the
+    zero frames; check = False only measures and returns inf for both when a zero frame did not come out as zeros."""
+    a, b = XCORR_MULT[kind]
+    ref = np.asarray(ref).reshape(-1, n)
+    assert ref.dtype == np.float64, "the reference is the float64 one, not a rounded result"
+    got = np.asarray(got).reshape(-1, n).astype(np.float64)
+    assert got.shape == ref.shape, (got.shape, ref.shape)
+    T, S = (np.asarray(v, np.float64) for v in scales)
+    unit = xcorr_unit(n, itype)
+    d = np.abs(got - ref)  # a non-finite got gives a non-finite d, which fails every comparison below
+    dlag = d.max(axis=1)
+    drss = np.sqrt((d * d).sum(axis=1))
+    zero = T == 0
+    zero_ok = bool(np.all(got[zero] == 0))
+    live = ~zero
+    with np.errstate(invalid="ignore", divide="ignore"):
+        fl = dlag[live] / (a * unit * (T[live] + S[live]))
+        fr = drss[live] / (b * unit * np.sqrt(float(n)) * T[live])
+    fl = np.where(np.isfinite(fl), fl, np.inf)
+    fr = np.where(np.isfinite(fr), fr, np.inf)
+    frac_lag = float(fl.max()) if fl.size else 0.0
+    frac_rss = float(fr.max()) if fr.size else 0.0
+    if not zero_ok and not check:
+        return float("inf"), float("inf")
+    if check:
+        live_idx = np.flatnonzero(live)
+        assert zero_ok, "%s: a zero frame did not come out as zeros (frames %s)" % (what, np.flatnonzero(zero & ~((got == 0).all(axis=1)))[:8])
+        assert frac_lag <= 1.0, "%s: per-lag bound used %.3g times over (frame %d, n %d, %s)" % (what, frac_lag, live_idx[int(fl.argmax())], n, kind)
+        assert frac_rss <= 1.0, "%s: per-frame bound used %.3g times over (frame %d, n %d, %s)" % (what, frac_rss, live_idx[int(fr.argmax())], n, kind)
+    return frac_lag, frac_rss
+
+
+def xcorr_held(outs, n, itype, ins, kind="direct", what=""):
+    """xcorr_bound_check of every output of a call against the float64 definition of its inputs: for the call sites that hold a relerr
+    comparison.  Returns the largest used fractions (lag, frame) over the outputs."""
+    used = [xcorr_bound_check(o, mag, sc, n, itype, kind, what="%s output %d" % (what, k))
+            for k, (o, (mag, sc)) in enumerate(zip(outs, xcorr_frames64(n, itype, ins)))]
+    return max(u[0] for u in used), max(u[1] for u in used)
+

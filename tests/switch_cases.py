@@ -683,12 +683,37 @@ add("math_wg_per_cu", _math_grid, {"MI355_MATH_WG_PER_CU": "1"}, taken=None)
 
 # -------------------------------------------------------------------------------------------- clxcorrelate_fft_vcf: its pieces
 
+def xcorr_route_kind(pkg, n):
+    """the multiples (fft_ref.XCORR_MULT) a correlator of n points is held to: `direct` for the fused kernel (powers of two 16 ... 4096); for the
+    composed route the kind of the clFFT route its transforms take -- a clFFT of that length, one frame, last_route().  Returns (kind, route)."""
+    import torch
+    from fft_ref import fft_bound_kind
+    if 16 <= n <= 4096 and n & (n - 1) == 0:
+        return "direct", "k_xcorr<%d>" % n
+    blk = pkg.clFFT(n, pkg.CLFFT_FORWARD, [], pkg.DTYPE_COMPLEX, *GPU_ARGS, 0, 1, False)
+    x = torch.zeros((n, 2), device="cuda")
+    x[0, 0] = 1.0
+    blk.work_device(1, [x], [torch.empty((n, 2), device="cuda")])
+    torch.cuda.synchronize()
+    route = blk.last_route()
+    return fft_bound_kind(route), route
+
+
+def xcorr_used(got, n, itype, ins, kind):
+    """the largest used fraction of the per-lag and per-frame bounds of tests/fft_ref.py (bound 1.0) of ONE output against the float64
+    definition of (reference, signal); a zero frame that did not come out as zeros counts as inf"""
+    from fft_ref import xcorr_bound_check, xcorr_frames64
+    (mag, sc), = xcorr_frames64(n, itype, ins)
+    return max(xcorr_bound_check(got, mag, sc, n, itype, kind, check=False))
+
+
 def _xcorr_device_pieces(pkg, oracle):
     """65536 points, two inputs, 2 x 256 + 3 frames through work_device: three pieces of the 128 MiB work buffers"""
     import torch
     from fft_ref import np_xcorr as _np_xcorr
     n, frames = 65536, 2 * 256 + 3
     ocl, sel, plat, dev = GPU_ARGS
+    kind, route = xcorr_route_kind(pkg, n)
     blk = pkg.clxcorrelate_fft_vcf(n, 2, ocl, sel, plat, dev, 2)
     g = torch.Generator(device="cuda").manual_seed(21)
     ins = [torch.randn(frames * n * 2, device="cuda", generator=g) for _ in range(2)]
@@ -698,20 +723,33 @@ def _xcorr_device_pieces(pkg, oracle):
     checks = []
     for f in six(frames):
         xs = [t[f * n * 2:(f + 1) * n * 2].cpu().numpy().view(np.complex64) for t in ins]
-        checks.append(("frame %d" % f, relerr(out[f * n:(f + 1) * n].cpu().numpy(), _np_xcorr(n, 2, xs)[0]), TOL))
-    return result(None, "", checks)
+        got = out[f * n:(f + 1) * n].cpu().numpy()
+        checks.append(("frame %d" % f, relerr(got, _np_xcorr(n, 2, xs)[0]), TOL))
+        checks.append(("frame %d: per-lag / per-frame bounds used (%s)" % (f, kind), xcorr_used(got, n, 2, xs, kind), 1.0))
+    return result(None, route, checks)
 
 
 def _xcorr_host_pieces(pkg, oracle):
-    """256 points, two inputs, 2 x 16384 + 5 frames through work(): three staging pieces of 64 MiB of input"""
+    """256 points, two inputs, 2 x 16384 + 5 frames through work(): three staging pieces of 64 MiB of input (16384 frames each); the first
+    frame, the last one and the first of the second piece also bit for bit what work_device gives for that frame alone"""
+    import torch
     from fft_ref import np_xcorr as _np_xcorr
     n, frames = 256, 2 * 16384 + 5
     rng = np.random.default_rng(22)
     ins = [rng.standard_normal(frames * n * 2, dtype=np.float32).view(np.complex64) for _ in range(2)]
     out = np.full(frames * n, np.nan, np.float32)
     ocl, sel, plat, dev = GPU_ARGS
-    pkg.clxcorrelate_fft_vcf(n, 2, ocl, sel, plat, dev, 2).work(frames, ins, [out])
-    return result(None, "", [("every frame", relerr(out, _np_xcorr(n, 2, ins)[0]), TOL)])
+    blk = pkg.clxcorrelate_fft_vcf(n, 2, ocl, sel, plat, dev, 2)
+    blk.work(frames, ins, [out])
+    checks = [("every frame", relerr(out, _np_xcorr(n, 2, ins)[0]), TOL),
+              ("every frame: per-lag / per-frame bounds used", xcorr_used(out, n, 2, ins, "direct"), 1.0)]
+    for f in (0, 16384, frames - 1):
+        d_in = [torch.from_numpy(x[f * n:(f + 1) * n].view(np.float32).copy()).cuda() for x in ins]
+        d_out = torch.full((n,), float("nan"), device="cuda")
+        blk.work_device(1, d_in, [d_out])
+        torch.cuda.synchronize()
+        checks.append(("frame %d: work() against work_device, bits" % f, bits_differ(out[f * n:(f + 1) * n], d_out.cpu().numpy()), 0.0))
+    return result(None, "", checks)
 
 
 add("xcorr_fft_device_pieces", _xcorr_device_pieces, switches=[], taken=None)

@@ -1,4 +1,5 @@
 """GPU parity: clxcorrelate_fft_vcf through the C ABI vs the oracle and vs the float64 definition.
+Every comparison also holds the per-lag / per-frame bounds of tests/fft_ref.py (xcorr_held; tests/test_xcorr_bounds_gpu.py is their own file).
 The reference holds no vectors for this block (parity unpinned); the anchors are the oracle's restatement of
 lib/clxcorrelate_fft_vcf_impl.cc:886-935,1058-1143 and the circular cross-correlation definition."""
 import numpy as np
@@ -6,6 +7,8 @@ import pytest
 
 from conftest import GPU_ARGS, crandn, golden, relerr
 from fft_ref import np_xcorr as _np_xcorr
+from fft_ref import xcorr_held
+from switch_cases import xcorr_route_kind
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
@@ -28,6 +31,7 @@ def test_vs_oracle_all_sizes(gpu, oracle, n, itype):
     ref = oracle.xcorr_fft(n, itype, ins, use_f64=True)
     for o, r in zip(outs, ref):
         assert relerr(o, r) <= TOL
+    print("USED k_xcorr<%d> itype %d: lag %.3f frame %.3f" % ((n, itype) + xcorr_held(outs, n, itype, ins, what="n %d" % n)))
 
 
 def test_definition_and_peak_location(gpu):
@@ -43,6 +47,7 @@ def test_definition_and_peak_location(gpu):
     a, b = x0.astype(np.complex128), x1.astype(np.complex128)
     r = np.array([np.sum(np.roll(a, -m) * np.conj(b)) for m in range(n)]) * n
     assert relerr(out, np.fft.fftshift(np.abs(r)).astype(np.float32)) <= TOL
+    xcorr_held([out], n, 2, [x0, x1], what="delayed copy")
 
 
 def test_many_inputs_and_device_path(gpu, oracle):
@@ -58,6 +63,7 @@ def test_many_inputs_and_device_path(gpu, oracle):
     ref = oracle.xcorr_fft(n, 2, ins, use_f64=True)
     for o, r in zip(d_out, ref):
         assert relerr(o.cpu().numpy(), r) <= TOL
+    xcorr_held([o.cpu().numpy() for o in d_out], n, 2, ins, what="6 inputs")
 
 
 # sizes outside the fused kernel's (powers of two 16 ... 4096): the reference's steps over the clFFT transforms -- powers of two below 16
@@ -73,17 +79,20 @@ def test_other_even_sizes(gpu, oracle, n, itype):
     if n == 1000:  # the numpy reference against the oracle where the oracle can run
         for r, o in zip(_np_xcorr(n, itype, ins), oracle.xcorr_fft(n, itype, ins, use_f64=True)):
             assert relerr(r, o) <= 1e-6
+    kind, route = xcorr_route_kind(gpu, n)
     blk = _blk(gpu, n, nin, itype)
     assert blk.work(nframes, ins, outs) == nframes
     ref = _np_xcorr(n, itype, ins)
     for o, r in zip(outs, ref):
         assert relerr(o, r) <= TOL
+    print("USED composed | %s | n %d itype %d: lag %.3f frame %.3f" % ((route, n, itype) + xcorr_held(outs, n, itype, ins, kind, what=route)))
     d_in = [torch.from_numpy(x.view(np.float32).reshape(-1, 2)).cuda() for x in ins]
     d_out = [torch.empty(nframes * n, device="cuda") for _ in range(nin - 1)]
     blk.work_device(nframes, d_in, d_out)
     torch.cuda.synchronize()
     for o, r in zip(d_out, ref):
         assert relerr(o.cpu().numpy(), r) <= TOL
+    xcorr_held([o.cpu().numpy() for o in d_out], n, itype, ins, kind, what=route + " (device path)")
 
 
 def test_errors(gpu):
@@ -109,3 +118,4 @@ def test_independent_scipy_case(gpu):
     assert _blk(gpu, 256, 3, 2).work(ins[0].size // 256, ins, outs) == ins[0].size // 256
     for o, s_ in zip(outs, (1, 2)):
         assert relerr(o, g["xc_out%d" % s_]) <= TOL
+    xcorr_held(outs, 256, 2, ins, what="scipy case")
