@@ -333,7 +333,7 @@ int bf_launch_mfma(mi355_beamform *h, const BfArgs &a, dim3 grid, hipStream_t st
 // caller holds the lock and has set the device
 int bf_launch(mi355_beamform *h, long long nunits, const void *in, void *out, hipStream_t st)
 {
-    const int cus = h->ctx->num_cus > 0 ? h->ctx->num_cus : 256;
+    const int cus = mi355_cus(h->ctx);
     const long long T = nunits * h->Ti;
     const signed char *d_raw = (const signed char *)h->tab.current();
     int rc = MI355_OK;

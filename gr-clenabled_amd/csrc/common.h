@@ -116,13 +116,23 @@ static inline size_t mi355_dtype_size(int dtype)
 // default (null) stream, which is also torch's default stream.
 static inline hipStream_t mi355_pick_stream(mi355_ctx *, void *stream) { return (hipStream_t)stream; }
 
+// compute units of the context's device (256, the MI355X's, where the query gave nothing)
+static inline int mi355_cus(const mi355_ctx *ctx) { return ctx->num_cus > 0 ? ctx->num_cus : 256; }
+
+// grid of a grid-stride kernel of 256-thread workgroups over `total` items: one workgroup per 256 items, at most per_cu per CU
+static inline unsigned mi355_grid_256(const mi355_ctx *ctx, long long total, int per_cu)
+{
+    const long long g = (total + 255) / 256, cap = (long long)mi355_cus(ctx) * per_cu;
+    return (unsigned)(g > cap ? cap : g < 1 ? 1 : g);
+}
+
 // Persistent-kernel grid: k workgroups per CU, k in [kmin, kmax] (all resident).  More resident
 // workgroups hide latency better, so kmax is the default; a smaller k is taken only when it divides
 // the work units more evenly by more than `tol` (a ragged last round costs up to 1/rounds of the
 // run time; latency-bound kernels pass a large tol, the bandwidth-bound FFT a small one).  MI355_WG_PER_CU overrides (tuning aid).
 static inline int mi355_balanced_grid(const mi355_ctx *ctx, long long units, int kmin, int kmax, double tol = 0.08)
 {
-    const int cus = ctx->num_cus > 0 ? ctx->num_cus : 256;
+    const int cus = mi355_cus(ctx);
     if (const char *e = getenv("MI355_WG_PER_CU")) {
         const int k = atoi(e);
         if (k > 0) return units < (long long)cus * k ? (units < 1 ? 1 : (int)units) : cus * k;
@@ -319,6 +329,31 @@ struct DevBuf {
 private:
     void *p = nullptr;
     size_t n = 0;
+};
+
+// The one device workspace of a handle whose work_dev calls may come on different streams (clFFT's multi-pass and unfused chirp-z
+// routes, clPowerSpectrum, clFEngine's generic route): a DevBuf, an event behind its last user and that user's stream.  The caller
+// holds the handle's lock from acquire() to release() and has set the device.
+struct DevWorkspace {
+    // `st` is the next user and needs `bytes`: if the last user was another stream, st waits for it (on the same stream order is
+    // given already); if the buffer has to grow while it has been used, the host waits for that user first, since its kernels may
+    // still work on the block that is freed.  A failed allocation leaves the buffer empty (DevBuf::reserve).
+    int acquire(size_t bytes, hipStream_t st);
+    // after the call's last launch.  Nothing is recorded while st is being captured: a graph orders its own nodes, and an event
+    // recorded in a capture is no event for an eager call to wait on.
+    int release(hipStream_t st);
+    // the host waits for the last user (before something its kernels read is freed); no user yet: nothing to wait for
+    int wait();
+    void destroy();
+    void *get() const { return buf.get(); }
+    size_t bytes() const { return buf.bytes(); }
+    hipStream_t last_stream() const { return last; }
+
+private:
+    DevBuf buf;
+    hipEvent_t done = nullptr;  // made by the first acquire
+    hipStream_t last = nullptr;
+    bool used = false;
 };
 
 // units in a piece of a call of `total` >= 1 units that would like `want` per piece

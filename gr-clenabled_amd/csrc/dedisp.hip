@@ -259,7 +259,7 @@ int dd_upload(mi355_dedisp *h, const int *tab)
 // caller holds the lock and has set the device
 int dd_launch(mi355_dedisp *h, long long n, const void *in, void *out, long long pitch, hipStream_t st)
 {
-    const int cus = h->ctx->num_cus > 0 ? h->ctx->num_cus : 256;
+    const int cus = mi355_cus(h->ctx);
     const char *d_tab = (const char *)h->dtab.current();
     const int *d_raw = (const int *)d_tab;
     if (h->tiled && h->fits32 && !h->generic) {

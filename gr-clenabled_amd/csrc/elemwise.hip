@@ -131,7 +131,7 @@ namespace {
 
 int launch_elem(mi355_elem *h, size_t n, const void *i0, const void *i1, void *o0, void *o1, hipStream_t st)
 {
-    int cus = h->ctx->num_cus > 0 ? h->ctx->num_cus : 256;
+    int cus = mi355_cus(h->ctx);
     auto al16 = [](const void *p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
     const int vec_ok = al16(i0) && al16(i1) && al16(o0) && al16(o1);
     size_t blocks = ((vec_ok ? (n + 3) / 4 : n) + kT - 1) / kT;

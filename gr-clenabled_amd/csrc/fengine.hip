@@ -369,10 +369,7 @@ struct mi355_fengine {
     unsigned long long *d_clips = nullptr;
     mi355_fft *fft = nullptr;             // generic route, made when first needed
     // generic route: one workspace per handle; calls on different streams are ordered on it
-    DevBuf ws;
-    hipEvent_t ws_done = nullptr;
-    hipStream_t ws_stream = nullptr;
-    bool ws_used = false;
+    DevWorkspace ws;
     DevBuf d_in, d_out;  // host path staging
     std::string route;
     std::mutex lock;
@@ -412,20 +409,12 @@ int fe_upload(mi355_fengine *h)
     return h->gtab.publish(h->ctx, h->gains.data(), h->gains.size() * sizeof(float), "mi355_fengine: gain");
 }
 
-unsigned fe_grid(const mi355_ctx *ctx, long long total)
-{
-    const long long cus = ctx->num_cus > 0 ? ctx->num_cus : 256;
-    long long g = (total + 255) / 256;
-    if (g > cus * 32) g = cus * 32;
-    return (unsigned)(g < 1 ? 1 : g);
-}
-
 #define FE_SIZES(X) X(16) X(32) X(64) X(128) X(256) X(512) X(1024) X(2048) X(4096)
 
 int fe_launch_fused(mi355_fengine *h, long long n, const void *const *in, void *out, hipStream_t st)
 {
     const int N = h->N, FG = kFePts / N;
-    const long long cus = h->ctx->num_cus > 0 ? h->ctx->num_cus : 256;
+    const long long cus = mi355_cus(h->ctx);
     const long long ngroups = (n + FG - 1) / FG;
     FeArgs a = {};
     a.taps = h->d_taps;
@@ -480,9 +469,7 @@ int fe_launch_generic(mi355_fengine *h, long long n, const void *const *in, void
     fe_gen_batch(h, &Sb, &nb);
     if (nb > n) nb = n;
     const size_t half = (size_t)Sb * npol * nb * N * 8;
-    if (h->ws_used && h->ws_stream != st) MI355_HIP(hipStreamWaitEvent(st, h->ws_done, 0));
-    if (2 * half > h->ws.bytes() && h->ws_used) MI355_HIP(hipEventSynchronize(h->ws_done));  // kernels of an earlier call still use the old one
-    int rc = h->ws.reserve(2 * half);
+    int rc = h->ws.acquire(2 * half, st);
     if (rc) return rc;
     c32 *d_z = (c32 *)h->ws.get(), *d_x = (c32 *)((char *)h->ws.get() + half);
     FeGenArgs g = {};
@@ -497,21 +484,16 @@ int fe_launch_generic(mi355_fengine *h, long long n, const void *const *in, void
             for (int i = 0; i < nr; i++) g.in[i] = (const f2v *)in[s0 * npol + i] + t0 * N;
             g.m = (int)m;
             g.total = (long long)nr * m * N;
-            hipLaunchKernelGGL(k_fe_woa, dim3(fe_grid(h->ctx, g.total)), dim3(256), 0, st, g);
+            hipLaunchKernelGGL(k_fe_woa, dim3(mi355_grid_256(h->ctx, g.total, 32)), dim3(256), 0, st, g);
             rc = mi355_fft_work_dev(h->fft, (int)(nr * m), d_z, d_x, (void *)st);
             if (rc) return rc;
-            hipLaunchKernelGGL(k_fe_quant, dim3(fe_grid(h->ctx, g.total)), dim3(256), 0, st, (const c32 *)d_x,
+            hipLaunchKernelGGL(k_fe_quant, dim3(mi355_grid_256(h->ctx, g.total, 32)), dim3(256), 0, st, (const c32 *)d_x,
                                (const float *)h->gtab.current() + (long long)s0 * npol * N, h->d_clips + (long long)s0 * npol,
                                (unsigned short *)((char *)out + t0 * h->frame_bytes), N, npol, h->S, s0, ns, (int)m, h->shift ? N / 2 : 0, g.total);
         }
     }
     MI355_HIP(hipGetLastError());
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return MI355_OK;  // a graph orders its own nodes
-    MI355_HIP(hipEventRecord(h->ws_done, st));
-    h->ws_stream = st;
-    h->ws_used = true;
-    return MI355_OK;
+    return h->ws.release(st);
 }
 
 // caller holds h->lock and has set the device
@@ -591,7 +573,6 @@ extern "C" int mi355_fengine_create(mi355_ctx *ctx, int num_inputs, int npol, in
         mi355_set_error("mi355_fengine_create: hipSetDevice failed");
         return fail(MI355_ERR_HIP);
     }
-    if (hipEventCreateWithFlags(&h->ws_done, hipEventDisableTiming) != hipSuccess) return fail(MI355_ERR_HIP);
     {
         const std::vector<float> ones(taps ? 0 : nt, 1.0f);
         if (hipMalloc((void **)&h->d_taps, nt * sizeof(float)) != hipSuccess) return fail(MI355_ERR_NOMEM);
@@ -621,12 +602,12 @@ extern "C" int mi355_fengine_destroy(mi355_fengine *h)
     if (!h) return MI355_OK;
     (void)hipSetDevice(h->ctx->device);
     h->gtab.release();
-    if (h->ws_used) (void)hipEventSynchronize(h->ws_done);
+    (void)h->ws.wait();
     if (h->fft) (void)mi355_fft_destroy(h->fft);
     for (void *p : {(void *)h->d_taps, h->d_tw, (void *)h->d_clips})
         if (p) (void)hipFree(p);
-    for (DevBuf *b : {&h->ws, &h->d_in, &h->d_out}) b->release();
-    if (h->ws_done) (void)hipEventDestroy(h->ws_done);
+    h->ws.destroy();
+    for (DevBuf *b : {&h->d_in, &h->d_out}) b->release();
     delete h;
     return MI355_OK;
 }

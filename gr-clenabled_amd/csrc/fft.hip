@@ -613,6 +613,89 @@ inline void set_route(FftRoute *rt, int kind, int a = 0, int b = 0, int c = 0, i
     rt->kind = kind; rt->a = a; rt->b = b; rt->c = c; rt->d = d; rt->wave = wave;
 }
 
+// The route of a length, decided once (fft_plan) and read by create, the launch dispatch, the host path's stream choice, the INFO
+// line and mi355_fft_plan_text.
+enum FftKind {
+    kPlanOnePass,  // powers of two up to 32768: k_fft / k_fft_s / k_fft_32k
+    kPlanTile,     // 65536 .. 1048576: two tile passes n1 x n2
+    kPlanSub,      // 4096-point sub-transforms and `levels` - 1 combine passes (above 2^20, and what the switches send here)
+    kPlanMr,       // 2^a 3^b 5^c 7^d ... that a workgroup holds (fft_mr.hip)
+    kPlanMrTile,   // the same lengths above 15360 points: two passes over sixteen-column tiles
+    kPlanChirpz    // every other length: chirp-z over power-of-two transforms of m points
+};
+struct FftPlan {
+    FftKind kind = kPlanOnePass;
+    int n1 = 0, n2 = 0;  // kPlanTile
+    int levels = 0;      // kPlanSub: 2 (S = n / 4096 <= 16), 3 (S = 16 x 2 .. 16) or 4 (S = 16 x 16 x 2 .. 16)
+    int m = 0;           // kPlanChirpz
+    MrPlan mr;           // kPlanMr
+    MrTilePlan mrt;      // kPlanMrTile
+};
+
+// the "plan" of create's INFO line, by FftKind
+const char *const kPlanInfo[] = {"one pass", "two passes over 16-column tiles", "multi-pass", "mixed radix, one pass",
+                                 "mixed radix, two passes over sixteen-column tiles", "chirp-z over a power-of-two transform"};
+const char kFftRange[] = "powers of two 2..16777216, any other size 3..8388608";
+bool fft_pow2(int n) { return n >= 2 && (n & (n - 1)) == 0; }
+bool fft_in_range(int n) { return n >= 2 && n <= (fft_pow2(n) ? 16777216 : 8388608); }
+// rows of the first tile pass.  131072 = 256 x 512: the 256-row pass first (its window values stay in registers); 2^19 = 1024 x 512
+// measured 3 % faster than 512 x 1024
+int fft_tile_rows(int n)
+{
+    int lg = 0;
+    while ((1 << lg) < n) lg++;
+    return lg == 17 ? 256 : 1 << ((lg + 1) / 2);
+}
+// size of the chirp-z convolution; at least 256, the fused kernel's smallest instantiation (more zero padding is harmless)
+int fft_chirpz_m(int n)
+{
+    int m = 256;
+    while (m < 2 * n - 1) m <<= 1;
+    return m;
+}
+bool fft_chirpz_fused_size(int m) { return m <= 16384; }
+
+// false: n is out of range.  `honour`: the create-time switches (MI355_FFT_32768_TWO_KERNELS, MI355_FFT_NO_TILE, MI355_FFT_TILE_N1,
+// MI355_FFT_NO_MR) are read; without it this is the default plan, which mi355_fft_plan_text describes.  tw_a / tw_b receive the host
+// twiddle runs of the mixed-radix plans (kPlanMr: tw_a; kPlanMrTile: both passes').
+bool fft_plan(int n, int sign, bool honour, FftPlan *p, std::vector<float> *tw_a, std::vector<float> *tw_b)
+{
+    *p = FftPlan();
+    if (!fft_in_range(n)) return false;
+    if (fft_pow2(n)) {
+        if (n < 32768 || (n == 32768 && !(honour && getenv("MI355_FFT_32768_TWO_KERNELS")))) return true;
+        if (n >= 65536 && n <= 1048576 && !(honour && getenv("MI355_FFT_NO_TILE"))) {
+            p->kind = kPlanTile;
+            p->n1 = fft_tile_rows(n);
+            if (const char *e = honour ? getenv("MI355_FFT_TILE_N1") : nullptr) {  // (tuning switch)
+                const int v = atoi(e);
+                if ((v == 256 || v == 512 || v == 1024) && n / v >= 256 && n / v <= 1024) p->n1 = v;
+            }
+            p->n2 = n / p->n1;
+            return true;
+        }
+        p->kind = kPlanSub;
+        p->levels = n / 4096 > 256 ? 4 : n / 4096 > 16 ? 3 : 2;
+        return true;
+    }
+    const bool no_mr = honour && getenv("MI355_FFT_NO_MR");
+    if (!no_mr && mi355_fft_mr_plan(n, sign, 0, &p->mr, tw_a)) p->kind = kPlanMr;
+    else if (p->mr = MrPlan(); !no_mr && mi355_fft_mr_tile_plan(n, sign, &p->mrt, tw_a, tw_b)) p->kind = kPlanMrTile;
+    else {
+        p->mrt = MrTilePlan();
+        p->kind = kPlanChirpz;
+        p->m = fft_chirpz_m(n);
+    }
+    return true;
+}
+
+// A run-time sign or flag as a template argument: f is a generic lambda and is called with a std::integral_constant, so that a launch
+// site is one hipLaunchKernelGGL inside nested lambdas; an `if constexpr` there keeps a combination that must not exist from being
+// instantiated.
+template <int V> using int_c = std::integral_constant<int, V>;
+template <class F> inline auto with_sign(int sign, F &&f) { return sign < 0 ? f(int_c<-1>{}) : f(int_c<1>{}); }
+template <class F> inline auto with_bool(bool b, F &&f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+
 template <int N>
 int launch_s(mi355_ctx *ctx, int sign, const void *in, void *out, const float *window, const void *tw, int nframes, int shift,
              int real_in, hipStream_t st, FftRoute *rt)
@@ -625,20 +708,24 @@ int launch_s(mi355_ctx *ctx, int sign, const void *in, void *out, const float *w
                                   : mi355_balanced_grid(ctx, nframes, 4, 4);
     if constexpr (N == 32768) {
         if (!getenv("MI355_FFT_32768_IN_REGISTERS")) {
-#define LAUNCH_32K(SG, RL) hipLaunchKernelGGL((k_fft_32k<SG, RL>), dim3(grid), dim3(512), 0, st, in, (c32 *)out, window, (const c32 *)tw, nframes, shift)
-            if (sign < 0) { if (real_in) LAUNCH_32K(-1, true); else LAUNCH_32K(-1, false); }
-            else          { if (real_in) LAUNCH_32K(1, true);  else LAUNCH_32K(1, false); }
-#undef LAUNCH_32K
+            with_sign(sign, [&](auto sg) {
+                with_bool(real_in != 0, [&](auto rl) {
+                    hipLaunchKernelGGL((k_fft_32k<decltype(sg)::value, decltype(rl)::value>), dim3(grid), dim3(512), 0, st, in, (c32 *)out, window,
+                                       (const c32 *)tw, nframes, shift);
+                });
+            });
             set_route(rt, kRtFft32k);
             MI355_HIP(hipGetLastError());
             return MI355_OK;
         }
     }
     if constexpr (N == 32768) MI355_SWITCH_NOTE(ctx, "MI355_FFT_32768_IN_REGISTERS", "k_fft_s<32768> instead of k_fft_32k");
-#define LAUNCH_S(SG, RL) hipLaunchKernelGGL((k_fft_s<N, SG, RL>), dim3(grid), dim3(256), 0, st, in, (c32 *)out, window, (const c32 *)tw, nframes, shift)
-    if (sign < 0) { if (real_in) LAUNCH_S(-1, true); else LAUNCH_S(-1, false); }
-    else          { if (real_in) LAUNCH_S(1, true);  else LAUNCH_S(1, false); }
-#undef LAUNCH_S
+    with_sign(sign, [&](auto sg) {
+        with_bool(real_in != 0, [&](auto rl) {
+            hipLaunchKernelGGL((k_fft_s<N, decltype(sg)::value, decltype(rl)::value>), dim3(grid), dim3(256), 0, st, in, (c32 *)out, window,
+                               (const c32 *)tw, nframes, shift);
+        });
+    });
     set_route(rt, kRtFftS, N);
     MI355_HIP(hipGetLastError());
     return MI355_OK;
@@ -1101,7 +1188,7 @@ int launch_g(mi355_ctx *ctx, int sign, const void *in, void *out, const float *w
 {
     constexpr int F = G::F, TH = G::TH, WAVES = TH / 64;
     int ngroups = (nframes + F - 1) / F;
-    int cus = ctx->num_cus > 0 ? ctx->num_cus : 256;
+    int cus = mi355_cus(ctx);
     // MI355_FFT_PREFETCH=1 selects the register-prefetch variant (2 workgroups/CU); measured equal to the
     // plain variant at 3 workgroups/CU on MI355X, so it is off by default.
     int pf = getenv("MI355_FFT_PREFETCH") ? atoi(getenv("MI355_FFT_PREFETCH")) : -1;  // (per call: tuning switch)
@@ -1134,21 +1221,17 @@ int launch_g(mi355_ctx *ctx, int sign, const void *in, void *out, const float *w
         ts = stamps_buffer(grid);
         if (ts) MI355_HIP(hipMemsetAsync(ts, 0, (size_t)grid * kTsSlots * 8, st));
     }
-#define LAUNCH_FFT_K(...) hipLaunchKernelGGL((k_fft<__VA_ARGS__>), dim3(grid), dim3(TH), 0, st, in, (c32 *)out, window, (const c32 *)tw, \
-                                                nframes, ngroups, shift, claims, ts)
-#define LAUNCH_FFT(SG, RL)                                                                      \
-    do {                                                                                             \
-        if (pf == 2) LAUNCH_FFT_K(N, SG, RL, 2, G);                                                  \
-        else if (pf == 1 && sched == 1 && ts) LAUNCH_FFT_K(N, SG, RL, 1, G, true, true);             \
-        else if (pf == 1 && sched == 1) LAUNCH_FFT_K(N, SG, RL, 1, G, true);                         \
-        else if (pf == 1 && ts) LAUNCH_FFT_K(N, SG, RL, 1, G, false, true);                          \
-        else if (pf == 1) LAUNCH_FFT_K(N, SG, RL, 1, G);                                             \
-        else LAUNCH_FFT_K(N, SG, RL, 0, G);                                                          \
-    } while (0)
-    if (sign < 0) { if (real_in) LAUNCH_FFT(-1, true); else LAUNCH_FFT(-1, false); }
-    else          { if (real_in) LAUNCH_FFT(1, true);  else LAUNCH_FFT(1, false); }
-#undef LAUNCH_FFT
-#undef LAUNCH_FFT_K
+    auto launch = [&](auto pfc, auto dyn, auto stamps) {
+        with_sign(sign, [&](auto sg) {
+            with_bool(real_in != 0, [&](auto rl) {
+                hipLaunchKernelGGL((k_fft<N, decltype(sg)::value, decltype(rl)::value, decltype(pfc)::value, G, decltype(dyn)::value, decltype(stamps)::value>),
+                                   dim3(grid), dim3(TH), 0, st, in, (c32 *)out, window, (const c32 *)tw, nframes, ngroups, shift, claims, ts);
+            });
+        });
+    };
+    if (pf == 2) launch(int_c<2>{}, std::false_type{}, std::false_type{});
+    else if (pf == 1) with_bool(sched == 1, [&](auto dyn) { with_bool(ts != nullptr, [&](auto stamps) { launch(int_c<1>{}, dyn, stamps); }); });
+    else launch(int_c<0>{}, std::false_type{}, std::false_type{});
     set_route(rt, kRtFft, N, pf, sched, grid, TH == 64);
     MI355_HIP(hipGetLastError());
     if (ts) return dump_stamps(ts, N, sign, sched, grid, ngroups, st);
@@ -1197,25 +1280,17 @@ struct mi355_fft {
     float *d_window;  // n floats or NULL
     void *d_tw;       // n complex: exp(sign*2*pi*i*k/n), generated in double
     HostPipe pipe;
-    // lengths 2^a 3^b 5^c 7^d that a workgroup holds: the mixed-radix kernel (fft_mr.hip); mr.n == 0: not used
-    MrPlan mr;
-    MrTilePlan mrt;  // the same lengths above 15360 points: two passes (mrt.n == 0: not used); the workspace is d_wa
-    // every other size that is not a power of two: chirp-z (Bluestein) over power-of-two transforms of size m
-    int m = 0;
+    FftPlan plan;     // the route of this length and what it needs (kPlanMrTile: the workspace holds the frames between the passes)
+    // kPlanChirpz: the convolution over power-of-two transforms of size plan.m
     void *d_pre = nullptr, *d_post = nullptr, *d_bspec = nullptr;  // window*chirp (n), chirp (n), spectrum of the conjugate chirp / m (m)
     void *d_twm_f = nullptr, *d_twm_i = nullptr;                    // twiddle tables of the size-m forward / inverse transforms
     float *d_ones = nullptr;                                        // all-ones window of size m
     mi355_fft *sub_f = nullptr, *sub_i = nullptr;                   // m > 32768: the size-m transforms are handles of their own (multi-pass sizes)
-    void *d_wa = nullptr, *d_wb = nullptr;                          // work buffers, cap_frames * m complex each
-    size_t cap_frames = 0;
-    // The two-kernel sizes (> 16384 points) and the unfused chirp-z path go through ONE workspace per handle.  Calls on
-    // different streams / threads are serialised on it: the lock covers the enqueue, ws_done orders the streams (the next
-    // user's stream waits for the previous user's kernels) and guards the re-allocation.
-    bool two_kernel = false;  // workspace scheme (65536 points; 32768 only with MI355_FFT_32768_TWO_KERNELS)
-    int tile_n1 = 0, tile_n2 = 0;  // 65536 .. 1048576 points: the two-pass tile scheme N = n1 x n2 (k_fft_tile); 0 = not used
+    // The multi-pass sizes and the unfused chirp-z path go through ONE workspace per handle (two buffers of it: the two halves).
+    // Calls on different streams / threads are serialised on it: the lock covers the enqueue (work_dev has no other handle lock),
+    // the workspace orders the streams and guards its re-allocation.
     std::mutex ws_lock;
-    hipEvent_t ws_done = nullptr;
-    bool ws_used = false;
+    DevWorkspace ws;
     // Claim words of the dynamic persistent schedule (one pass, n <= 4096): kClaimSets word sets, zeroed at create; every launch
     // leaves its words at zero again.  A stream keeps the set it was given first, so two calls in flight at once never share
     // one.  Calls from further streams, and calls captured into a graph, take the static schedule (same results); see claim_words.
@@ -1359,42 +1434,33 @@ int launch_chirpz_m(mi355_fft *h, const void *in, void *out, int nframes, hipStr
     const int lo = (h->sign < 0 && h->shift) ? (h->n + 1) / 2 : 0;
     const int *src = (const int *)((const char *)h->d_post + (size_t)h->n * 8);
     constexpr int lds_bytes = Geo<M>::PTS * 8;
-    if (h->dtype == MI355_DTYPE_FLOAT) {
-        if (lds_bytes > 64 * 1024) MI355_HIP(hipFuncSetAttribute((const void *)k_chirpz<M, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-        hipLaunchKernelGGL((k_chirpz<M, true>), dim3(grid), dim3(TH), lds_bytes, st, in, (c32 *)out, (const c32 *)h->d_pre, src, (const c32 *)h->d_post,
+    const int rc = with_bool(h->dtype == MI355_DTYPE_FLOAT, [&](auto rl) -> int {
+        constexpr bool REAL = decltype(rl)::value;
+        if (lds_bytes > 64 * 1024) MI355_HIP(hipFuncSetAttribute((const void *)k_chirpz<M, REAL>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
+        hipLaunchKernelGGL((k_chirpz<M, REAL>), dim3(grid), dim3(TH), lds_bytes, st, in, (c32 *)out, (const c32 *)h->d_pre, src, (const c32 *)h->d_post,
                            (const c32 *)h->d_bspec, (const c32 *)h->d_twm_f, (const c32 *)h->d_twm_i, h->n, nframes, ngroups, lo);
-    } else {
-        if (lds_bytes > 64 * 1024) MI355_HIP(hipFuncSetAttribute((const void *)k_chirpz<M, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-        hipLaunchKernelGGL((k_chirpz<M, false>), dim3(grid), dim3(TH), lds_bytes, st, in, (c32 *)out, (const c32 *)h->d_pre, src, (const c32 *)h->d_post,
-                           (const c32 *)h->d_bspec, (const c32 *)h->d_twm_f, (const c32 *)h->d_twm_i, h->n, nframes, ngroups, lo);
-    }
+        return MI355_OK;
+    });
+    if (rc) return rc;
     set_route(&h->rt, kRtChirpz, M);
     MI355_HIP(hipGetLastError());
     return MI355_OK;
 }
 
-// workspace hand-over between streams: call with h->ws_lock held
-int ws_acquire(mi355_fft *h, hipStream_t st, bool realloc)
+// Prologue of the workspace routes, called with h->ws_lock held: *chunk = frames per piece (a buffer is bounded to `bound` bytes
+// and holds at least one frame), and the workspace of `nbuf` buffers of that many frames is handed over to st.  Buffer b starts
+// b * *chunk frames into it.  The caller ends with h->ws.release(st).
+int ws_frames(mi355_fft *h, size_t bound, size_t frame_bytes, int nbuf, int nframes, hipStream_t st, size_t *chunk)
 {
-    if (!h->ws_done) MI355_HIP(hipEventCreateWithFlags(&h->ws_done, hipEventDisableTiming));
-    if (h->ws_used) {
-        if (realloc) MI355_HIP(hipEventSynchronize(h->ws_done));  // nobody may still be reading the buffers that are freed
-        else MI355_HIP(hipStreamWaitEvent(st, h->ws_done, 0));
-    }
-    return MI355_OK;
-}
-int ws_release(mi355_fft *h, hipStream_t st)
-{
-    MI355_HIP(hipEventRecord(h->ws_done, st));
-    h->ws_used = true;
-    return MI355_OK;
+    *chunk = mi355_piece_units(bound / frame_bytes, (size_t)nframes);
+    return h->ws.acquire((size_t)nbuf * *chunk * frame_bytes, st);
 }
 
 int launch_handle(mi355_fft *h, const void *in, void *out, int nvec, hipStream_t st);
 
 int launch_bluestein(mi355_fft *h, const void *in, void *out, int nframes, hipStream_t st)
 {
-    const int N = h->n, M = h->m;
+    const int N = h->n, M = h->plan.m;
     static const bool fused = getenv("MI355_CHIRPZ_FUSED") ? atoi(getenv("MI355_CHIRPZ_FUSED")) != 0 : true;
     if (fused) {
         switch (M) {
@@ -1407,106 +1473,80 @@ int launch_bluestein(mi355_fft *h, const void *in, void *out, int nframes, hipSt
         case 16384: return launch_chirpz_m<16384>(h, in, out, nframes, st);
         }
     }
-    if (!fused && M >= 256 && M <= 16384) MI355_SWITCH_NOTE(h->ctx, "MI355_CHIRPZ_FUSED", "the five-launch chirp-z path instead of k_chirpz");
-    // bound the work buffers to 2 x 128 MiB
-    size_t chunk = (128u << 20) / ((size_t)M * 8);
-    if (chunk < 1) chunk = 1;
-    if (chunk > (size_t)nframes) chunk = (size_t)nframes;
+    if (!fused && fft_chirpz_fused_size(M)) MI355_SWITCH_NOTE(h->ctx, "MI355_CHIRPZ_FUSED", "the five-launch chirp-z path instead of k_chirpz");
     std::lock_guard<std::mutex> ws_guard(h->ws_lock);
-    {
-        const int rc = ws_acquire(h, st, chunk > h->cap_frames);
-        if (rc) return rc;
-    }
-    if (chunk > h->cap_frames) {
-        MI355_HIP(hipStreamSynchronize(st));
-        if (h->d_wa) (void)hipFree(h->d_wa);
-        if (h->d_wb) (void)hipFree(h->d_wb);
-        h->d_wa = h->d_wb = nullptr; h->cap_frames = 0;
-        MI355_HIP(hipMalloc(&h->d_wa, chunk * (size_t)M * 8));
-        MI355_HIP(hipMalloc(&h->d_wb, chunk * (size_t)M * 8));
-        h->cap_frames = chunk;
-    }
-    const int cus = h->ctx->num_cus > 0 ? h->ctx->num_cus : 256;
-    auto grid_for = [&](long long total) { long long b = (total + 255) / 256; return (unsigned)(b < (long long)cus * 16 ? b : (long long)cus * 16); };
+    size_t chunk;
+    if (const int rc = ws_frames(h, 128u << 20, (size_t)M * 8, 2, nframes, st, &chunk)) return rc;  // the work buffers bounded to 2 x 128 MiB
+    c32 *wa = (c32 *)h->ws.get(), *wb = wa + chunk * M;
     const size_t isz = h->dtype == MI355_DTYPE_FLOAT ? 4 : 8;
     const int len = (N + 1) / 2;
     for (size_t f0 = 0; f0 < (size_t)nframes; f0 += chunk) {
         const int nf = (int)((size_t)nframes - f0 < chunk ? (size_t)nframes - f0 : chunk);
         const long long tm = (long long)nf * M, tn = (long long)nf * N;
-        hipLaunchKernelGGL(k_blu_pre, dim3(grid_for(tm)), dim3(256), 0, st, (const char *)in + f0 * N * isz, (c32 *)h->d_wa,
+        hipLaunchKernelGGL(k_blu_pre, dim3(mi355_grid_256(h->ctx, tm, 16)), dim3(256), 0, st, (const char *)in + f0 * N * isz, wa,
                            (const c32 *)h->d_pre, (const int *)((const char *)h->d_post + (size_t)N * 8), N, M, tm,
                            h->dtype == MI355_DTYPE_FLOAT ? 1 : 0);
-        int rc = h->sub_f ? launch_handle(h->sub_f, h->d_wa, h->d_wb, nf, st) : launch_fft(h->ctx, M, -1, h->d_wa, h->d_wb, h->d_ones, h->d_twm_f, nf, 0, 0, st, nullptr, &h->rt_sub);
+        int rc = h->sub_f ? launch_handle(h->sub_f, wa, wb, nf, st) : launch_fft(h->ctx, M, -1, wa, wb, h->d_ones, h->d_twm_f, nf, 0, 0, st, nullptr, &h->rt_sub);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_blu_mul, dim3(grid_for(tm)), dim3(256), 0, st, (c32 *)h->d_wb, (const c32 *)h->d_bspec, M, tm);
-        rc = h->sub_i ? launch_handle(h->sub_i, h->d_wb, h->d_wa, nf, st) : launch_fft(h->ctx, M, 1, h->d_wb, h->d_wa, h->d_ones, h->d_twm_i, nf, 0, 0, st);
+        hipLaunchKernelGGL(k_blu_mul, dim3(mi355_grid_256(h->ctx, tm, 16)), dim3(256), 0, st, wb, (const c32 *)h->d_bspec, M, tm);
+        rc = h->sub_i ? launch_handle(h->sub_i, wb, wa, nf, st) : launch_fft(h->ctx, M, 1, wb, wa, h->d_ones, h->d_twm_i, nf, 0, 0, st);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_blu_post, dim3(grid_for(tn)), dim3(256), 0, st, (const c32 *)h->d_wa, (c32 *)out + f0 * N,
+        hipLaunchKernelGGL(k_blu_post, dim3(mi355_grid_256(h->ctx, tn, 16)), dim3(256), 0, st, (const c32 *)wa, (c32 *)out + f0 * N,
                            (const c32 *)h->d_post, N, M, tn, (h->sign < 0 && h->shift) ? len : 0);
         MI355_HIP(hipGetLastError());
     }
     set_route(&h->rt, kRtBluestein, M);
-    return ws_release(h, st);
+    return h->ws.release(st);
 }
 
+// One tile pass.  Pass B is never REAL (it reads the workspace), and WR, the window values of pass A in registers, exists only for
+// pass A with fewer than 1024 rows: the `if constexpr`s of the dispatch keep every other combination from being instantiated.
 template <int NR, bool PASS_B>
 int launch_tile(mi355_fft *h, const void *in, c32 *out, const c32 *twR, int ld, int nframes, int row_xor, bool real_in, hipStream_t st)
 {
     constexpr int lds_bytes = 16 * (NR + 1) * 8;
-    const int cus = h->ctx->num_cus > 0 ? h->ctx->num_cus : 256;
     const long long items = (long long)nframes * (ld / 16);
     const int per_cu = (160 * 1024) / lds_bytes;
-    long long grid = (long long)cus * (per_cu < 1 ? 1 : per_cu);
+    long long grid = (long long)mi355_cus(h->ctx) * (per_cu < 1 ? 1 : per_cu);
     if (grid > items) grid = items;
     if (grid > ld / 16) grid -= grid % (ld / 16);  // a workgroup then meets the same tile of every frame (its window values stay in registers)
     const int nmask = h->n - 1;
     constexpr bool WRD = !PASS_B && NR == 256;  // window values of pass A in registers
     const bool wr = !PASS_B && NR < 1024 && (getenv("MI355_FFT_TILE_WREG") ? atoi(getenv("MI355_FFT_TILE_WREG")) != 0 : WRD);
-#define TILE1(SG, RL, WR)                                                                                                       \
-    do {                                                                                                                        \
-        MI355_HIP(hipFuncSetAttribute((const void *)k_fft_tile<NR, SG, PASS_B, RL, WR>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes)); \
-        hipLaunchKernelGGL((k_fft_tile<NR, SG, PASS_B, RL, WR>), dim3((unsigned)grid), dim3(NR), lds_bytes, st, in, out, h->d_window, (const c32 *)h->d_tw, \
-                           twR, ld, nmask, items, row_xor);                                                                     \
-    } while (0)
-#define TILE(SG, RL)                                                                                                            \
-    do {                                                                                                                        \
-        if constexpr (!PASS_B && NR < 1024) { if (wr) TILE1(SG, RL, true); else TILE1(SG, RL, false); }                         \
-        else TILE1(SG, RL, false);                                                                                              \
-    } while (0)
+    bool half = false;
     if constexpr (NR == 1024) {
         // 1024 rows: half the threads, two transforms each, the next tile fetched under the transform (2^20 points 540 -> 517 us, 2^19 500 -> 485
         // on one box; the same form at 512 rows, where two workgroups share the CU anyway, measured 3 % slower and is not instantiated)
-        static const bool half = getenv("MI355_FFT_TILE_HALF") ? atoi(getenv("MI355_FFT_TILE_HALF")) != 0 : true;
-        if (!half) MI355_SWITCH_NOTE(h->ctx, "MI355_FFT_TILE_HALF", "k_fft_tile with one thread per sixteen values instead of k_fft_tile_h");
-        if (half) {
-#define TILEH(SG, RL)                                                                                                           \
-    do {                                                                                                                        \
-        MI355_HIP(hipFuncSetAttribute((const void *)k_fft_tile_h<NR, SG, PASS_B, RL>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes)); \
-        hipLaunchKernelGGL((k_fft_tile_h<NR, SG, PASS_B, RL>), dim3((unsigned)grid), dim3(NR / 2), lds_bytes, st, in, out, h->d_window, (const c32 *)h->d_tw, \
-                           twR, ld, nmask, items, row_xor);                                                                     \
-    } while (0)
-            if constexpr (PASS_B) {
-                if (h->sign < 0) TILEH(-1, false); else TILEH(1, false);
-            } else {
-                if (h->sign < 0) { if (real_in) TILEH(-1, true); else TILEH(-1, false); }
-                else             { if (real_in) TILEH(1, true);  else TILEH(1, false); }
+        static const bool on = getenv("MI355_FFT_TILE_HALF") ? atoi(getenv("MI355_FFT_TILE_HALF")) != 0 : true;
+        if (!on) MI355_SWITCH_NOTE(h->ctx, "MI355_FFT_TILE_HALF", "k_fft_tile with one thread per sixteen values instead of k_fft_tile_h");
+        half = on;
+    }
+    auto launch = [&](auto sg, auto rl, auto w) -> int {
+        constexpr int SG = decltype(sg)::value;
+        constexpr bool RL = decltype(rl)::value, WR = decltype(w)::value;
+        if constexpr (NR == 1024) {
+            if (half) {
+                MI355_HIP(hipFuncSetAttribute((const void *)k_fft_tile_h<NR, SG, PASS_B, RL>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
+                hipLaunchKernelGGL((k_fft_tile_h<NR, SG, PASS_B, RL>), dim3((unsigned)grid), dim3(NR / 2), lds_bytes, st, in, out, h->d_window,
+                                   (const c32 *)h->d_tw, twR, ld, nmask, items, row_xor);
+                MI355_HIP(hipGetLastError());
+                return MI355_OK;
             }
-#undef TILEH
-            MI355_HIP(hipGetLastError());
-            return MI355_OK;
         }
-    }
-    if constexpr (PASS_B) {
-        if (h->sign < 0) TILE(-1, false); else TILE(1, false);
-    } else {
-        if (h->sign < 0) { if (real_in) TILE(-1, true); else TILE(-1, false); }
-        else             { if (real_in) TILE(1, true);  else TILE(1, false); }
-    }
-#undef TILE
-#undef TILE1
-    (void)wr;
-    MI355_HIP(hipGetLastError());
-    return MI355_OK;
+        MI355_HIP(hipFuncSetAttribute((const void *)k_fft_tile<NR, SG, PASS_B, RL, WR>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
+        hipLaunchKernelGGL((k_fft_tile<NR, SG, PASS_B, RL, WR>), dim3((unsigned)grid), dim3(NR), lds_bytes, st, in, out, h->d_window,
+                           (const c32 *)h->d_tw, twR, ld, nmask, items, row_xor);
+        MI355_HIP(hipGetLastError());
+        return MI355_OK;
+    };
+    return with_sign(h->sign, [&](auto sg) {
+        if constexpr (PASS_B) return launch(sg, std::false_type{}, std::false_type{});
+        else
+            return with_bool(real_in, [&](auto rl) {
+                if constexpr (NR < 1024) return with_bool(wr, [&](auto w) { return launch(sg, rl, w); });
+                else return launch(sg, rl, std::false_type{});
+            });
+    });
 }
 
 template <bool PASS_B>
@@ -1519,153 +1559,110 @@ int launch_tile_nr(mi355_fft *h, int nr, const void *in, c32 *out, const c32 *tw
     }
 }
 
+// One k_fft_combine2 launch over the nf frames of a piece: the radix-`radix` combine of transforms of nsub points, src -> dst.  The
+// levels below the last run `sets` interleaved sets of radix-16 combines in one launch (blockIdx.y), and share the CUs among them.
+void launch_combine2(mi355_fft *h, int radix, const c32 *src, c32 *dst, int nf, int nsub, int sets, int m_xor, hipStream_t st)
+{
+    const long long total = (long long)nf * nsub, share = (long long)mi355_cus(h->ctx) * 16 / sets + 1;
+    const unsigned blocks = sets == 1 ? mi355_grid_256(h->ctx, total, 16) : (unsigned)std::min((total + 255) / 256, share);
+    auto launch = [&](auto ss) {
+        with_sign(h->sign, [&](auto sg) {
+            hipLaunchKernelGGL((k_fft_combine2<decltype(ss)::value, decltype(sg)::value>), dim3(blocks, (unsigned)sets), dim3(256), 0, st, src, dst,
+                               (const c32 *)h->d_tw, total, nsub, (long long)h->n, (long long)sets * nsub, sets > 1 ? (long long)nsub : 0LL,
+                               sets > 1 ? 16LL * nsub : 0LL, sets, h->n - 1, m_xor);
+        });
+    };
+    switch (radix) {
+    case 2: return launch(int_c<2>{});
+    case 4: return launch(int_c<4>{});
+    case 8: return launch(int_c<8>{});
+    default: return launch(int_c<16>{});
+    }
+}
+
 int launch_big(mi355_fft *h, const void *in, void *out, int nframes, hipStream_t st)
 {
-    const int N = h->n, S = N / 4096;
+    const int N = h->n, S = N / 4096, levels = h->plan.levels;
+    const bool tile = h->plan.kind == kPlanTile, real_in = h->dtype == MI355_DTYPE_FLOAT, fwd_shift = h->sign < 0 && h->shift;
     static const size_t ws_mb = getenv("MI355_FFT_WS_MB") ? (size_t)atoi(getenv("MI355_FFT_WS_MB")) : 256;
     if (ws_mb != 256) MI355_SWITCH_NOTE(h->ctx, "MI355_FFT_WS_MB", "another workspace bound for the multi-pass sizes");
-    size_t chunk = (ws_mb << 20) / ((size_t)N * 8);  // workspace bounded to 256 MiB
-    if (chunk < 1) chunk = 1;
-    if (chunk > (size_t)nframes) chunk = (size_t)nframes;
     std::lock_guard<std::mutex> ws_guard(h->ws_lock);
-    {
-        const int rc = ws_acquire(h, st, chunk > h->cap_frames);
-        if (rc) return rc;
-    }
-    const bool three_pass = S > 16 && !h->tile_n1;  // 131072 points and more (decimation-in-time scheme): a second workspace for the intermediate transforms
-    const bool four_pass = S > 256;  // 2^21 .. 2^24 points = 4096 x 16 x 16 x S3: one more combine level
-    if (chunk > h->cap_frames) {
-        MI355_HIP(hipStreamSynchronize(st));
-        if (h->d_wa) (void)hipFree(h->d_wa);
-        if (h->d_wb) (void)hipFree(h->d_wb);
-        h->d_wa = h->d_wb = nullptr; h->cap_frames = 0;
-        MI355_HIP(hipMalloc(&h->d_wa, chunk * (size_t)N * 8));
-        if (three_pass) MI355_HIP(hipMalloc(&h->d_wb, chunk * (size_t)N * 8));
-        h->cap_frames = chunk;
-    }
-    const int cus = h->ctx->num_cus > 0 ? h->ctx->num_cus : 256;
-    const size_t isz = h->dtype == MI355_DTYPE_FLOAT ? 4 : 8;
-    const int in_xor = (h->sign > 0 && h->shift) ? 8 : 0, m_xor = (h->sign < 0 && h->shift) ? S / 2 : 0;
+    // a buffer bounded to 256 MiB; three and four levels (131072 points and more, decimation in time) keep the intermediate transforms in a second one
+    size_t chunk;
+    if (const int rc = ws_frames(h, ws_mb << 20, (size_t)N * 8, !tile && levels > 2 ? 2 : 1, nframes, st, &chunk)) return rc;
+    c32 *wa = (c32 *)h->ws.get(), *wb = wa + chunk * N;
+    const size_t isz = real_in ? 4 : 8;
+    const int in_xor = (h->sign > 0 && h->shift) ? 8 : 0, m_xor = fwd_shift ? S / 2 : 0;
     const c32 *tw4096 = (const c32 *)h->d_tw + N;
     for (size_t f0 = 0; f0 < (size_t)nframes; f0 += chunk) {
         const int nf = (int)((size_t)nframes - f0 < chunk ? (size_t)nframes - f0 : chunk);
-        const int nsub = nf * S / 4;  // quads of sub-frames
-        // whole octets: workgroup id % 8 = XCD (see k_fft_sub); one quad per workgroup (8 per CU) measures 465 us per 2^26 samples
-        // against 494 with the two resident workgroups per CU walking four quads each
-        const int grid = (mi355_balanced_grid(h->ctx, nsub, 8, 8) + 7) & ~7;
         const void *src = (const char *)in + f0 * N * isz;
-        if (h->tile_n1) {  // two passes over whole lines: x (n1 rows of n2) -> ws[n2][k1] -> out[k2][k1]
-            const int n1 = h->tile_n1, n2 = h->tile_n2;
+        c32 *dst = (c32 *)out + f0 * N;
+        if (tile) {  // two passes over whole lines: x (n1 rows of n2) -> ws[n2][k1] -> out[k2][k1]
+            const int n1 = h->plan.n1, n2 = h->plan.n2;
             const c32 *tw1 = (const c32 *)h->d_tw + N + 4096, *tw2 = tw1 + n1;
-            int rc = launch_tile_nr<false>(h, n1, src, (c32 *)h->d_wa, tw1, n2, nf, (h->sign > 0 && h->shift) ? n1 / 2 : 0, h->dtype == MI355_DTYPE_FLOAT, st);
+            int rc = launch_tile_nr<false>(h, n1, src, wa, tw1, n2, nf, (h->sign > 0 && h->shift) ? n1 / 2 : 0, real_in, st);
             if (rc) return rc;
-            rc = launch_tile_nr<true>(h, n2, h->d_wa, (c32 *)out + f0 * N, tw2, n1, nf, (h->sign < 0 && h->shift) ? n2 / 2 : 0, false, st);
+            rc = launch_tile_nr<true>(h, n2, wa, dst, tw2, n1, nf, fwd_shift ? n2 / 2 : 0, false, st);
             if (rc) return rc;
             set_route(&h->rt, kRtTile, n1, n2);
             continue;
         }
-        set_route(&h->rt, kRtSub, S, four_pass ? 4 : three_pass ? 3 : 2);
-#define SUB(SG, RL) hipLaunchKernelGGL((k_fft_sub<SG, RL>), dim3(grid), dim3(256), 0, st, src, (c32 *)h->d_wa, h->d_window, tw4096, S, nsub, in_xor)
-        if (h->sign < 0) { if (h->dtype == MI355_DTYPE_FLOAT) SUB(-1, true); else SUB(-1, false); }
-        else             { if (h->dtype == MI355_DTYPE_FLOAT) SUB(1, true);  else SUB(1, false); }
-#undef SUB
-        c32 *dst = (c32 *)out + f0 * N;
-#define COMB2(SS, SG, GY, ...) hipLaunchKernelGGL((k_fft_combine2<SS, SG>), dim3((unsigned)blocks, GY), dim3(256), 0, st, __VA_ARGS__)
-        if (four_pass) {
+        set_route(&h->rt, kRtSub, S, levels);
+        const int nsub = nf * S / 4;  // quads of sub-frames
+        // whole octets: workgroup id % 8 = XCD (see k_fft_sub); one quad per workgroup (8 per CU) measures 465 us per 2^26 samples
+        // against 494 with the two resident workgroups per CU walking four quads each
+        const int grid = (mi355_balanced_grid(h->ctx, nsub, 8, 8) + 7) & ~7;
+        with_sign(h->sign, [&](auto sg) {
+            with_bool(real_in, [&](auto rl) {
+                hipLaunchKernelGGL((k_fft_sub<decltype(sg)::value, decltype(rl)::value>), dim3(grid), dim3(256), 0, st, src, wa, h->d_window, tw4096, S,
+                                   nsub, in_xor);
+            });
+        });
+        if (levels == 4) {
             // sub-frame s = 16 S3 a + S3 b + c (a, b < 16, c < S3):
             //   H_(b,c) = radix-16 combine over a of E_s            (A -> B)   65536-point transforms of x[16 S3 m + S3 b + c]
             //   G_c     = radix-16 combine over b of H_(b,c)        (B -> A)   2^20-point transforms of x[S3 m + c]
             //   X       = radix-S3 combine over c of G_c            (A -> out)
-            const int S3 = S / 256, T2 = 16 * S3;  // T2 = number of 65536-point intermediate transforms
-            {
-                const long long total = (long long)nf * 4096;
-                long long blocks = (total + 255) / 256;
-                if (blocks > (long long)cus * 16 / T2 + 1) blocks = (long long)cus * 16 / T2 + 1;
-                if (h->sign < 0) COMB2(16, -1, T2, (const c32 *)h->d_wa, (c32 *)h->d_wb, (const c32 *)h->d_tw, total, 4096, (long long)N, (long long)T2 * 4096, 4096LL, 65536LL, T2, N - 1, 0);
-                else             COMB2(16, 1, T2, (const c32 *)h->d_wa, (c32 *)h->d_wb, (const c32 *)h->d_tw, total, 4096, (long long)N, (long long)T2 * 4096, 4096LL, 65536LL, T2, N - 1, 0);
-            }
-            {
-                const long long total = (long long)nf * 65536;
-                long long blocks = (total + 255) / 256;
-                if (blocks > (long long)cus * 16 / S3 + 1) blocks = (long long)cus * 16 / S3 + 1;
-                if (h->sign < 0) COMB2(16, -1, S3, (const c32 *)h->d_wb, (c32 *)h->d_wa, (const c32 *)h->d_tw, total, 65536, (long long)N, (long long)S3 * 65536, 65536LL, 1048576LL, S3, N - 1, 0);
-                else             COMB2(16, 1, S3, (const c32 *)h->d_wb, (c32 *)h->d_wa, (const c32 *)h->d_tw, total, 65536, (long long)N, (long long)S3 * 65536, 65536LL, 1048576LL, S3, N - 1, 0);
-            }
-            {
-                const long long total = (long long)nf * 1048576;
-                long long blocks = (total + 255) / 256;
-                if (blocks > (long long)cus * 16) blocks = (long long)cus * 16;
-                const int mx = (h->sign < 0 && h->shift) ? S3 / 2 : 0;
-#define COMB2G(SS) do { if (h->sign < 0) COMB2(SS, -1, 1, (const c32 *)h->d_wa, dst, (const c32 *)h->d_tw, total, 1048576, (long long)N, 1048576LL, 0LL, 0LL, 1, N - 1, mx); \
-                        else             COMB2(SS, 1, 1, (const c32 *)h->d_wa, dst, (const c32 *)h->d_tw, total, 1048576, (long long)N, 1048576LL, 0LL, 0LL, 1, N - 1, mx); } while (0)
-                if (S3 == 2) COMB2G(2); else if (S3 == 4) COMB2G(4); else if (S3 == 8) COMB2G(8); else COMB2G(16);
-#undef COMB2G
-            }
-            MI355_HIP(hipGetLastError());
-            continue;
-        }
-        if (three_pass) {
+            const int S3 = S / 256;  // 16 S3 = number of 65536-point intermediate transforms
+            launch_combine2(h, 16, wa, wb, nf, 4096, 16 * S3, 0, st);
+            launch_combine2(h, 16, wb, wa, nf, 65536, S3, 0, st);
+            launch_combine2(h, S3, wa, dst, nf, 1048576, 1, fwd_shift ? S3 / 2 : 0, st);
+        } else if (levels == 3) {
             const int S2 = S / 16;
-            {   // G_b = radix-16 combine of the sub-frames S2 a + b  (workspace A -> B), all b in one launch
-                const long long total = (long long)nf * 4096;
-                long long blocks = (total + 255) / 256;
-                if (blocks > (long long)cus * 16 / S2 + 1) blocks = (long long)cus * 16 / S2 + 1;
-                if (h->sign < 0) COMB2(16, -1, S2, (const c32 *)h->d_wa, (c32 *)h->d_wb, (const c32 *)h->d_tw, total, 4096, (long long)N, (long long)S2 * 4096, 4096LL, 65536LL, S2, N - 1, 0);
-                else             COMB2(16, 1, S2, (const c32 *)h->d_wa, (c32 *)h->d_wb, (const c32 *)h->d_tw, total, 4096, (long long)N, (long long)S2 * 4096, 4096LL, 65536LL, S2, N - 1, 0);
-            }
-            {   // X = radix-S2 combine of the G_b  (workspace B -> out)
-                const long long total = (long long)nf * 65536;
-                long long blocks = (total + 255) / 256;
-                if (blocks > (long long)cus * 16) blocks = (long long)cus * 16;
-                const int mx = (h->sign < 0 && h->shift) ? S2 / 2 : 0;
-#define COMB2F(SS) do { if (h->sign < 0) COMB2(SS, -1, 1, (const c32 *)h->d_wb, dst, (const c32 *)h->d_tw, total, 65536, (long long)N, 65536LL, 0LL, 0LL, 1, N - 1, mx); \
-                        else             COMB2(SS, 1, 1, (const c32 *)h->d_wb, dst, (const c32 *)h->d_tw, total, 65536, (long long)N, 65536LL, 0LL, 0LL, 1, N - 1, mx); } while (0)
-                if (S2 == 2) COMB2F(2); else if (S2 == 4) COMB2F(4); else if (S2 == 8) COMB2F(8); else COMB2F(16);
-#undef COMB2F
-            }
-            MI355_HIP(hipGetLastError());
-            continue;
+            launch_combine2(h, 16, wa, wb, nf, 4096, S2, 0, st);                      // G_b = radix-16 combine of the sub-frames S2 a + b, all b in one launch
+            launch_combine2(h, S2, wb, dst, nf, 65536, 1, fwd_shift ? S2 / 2 : 0, st);  // X = radix-S2 combine of the G_b
+        } else {
+            const long long total = (long long)nf * 4096;
+            auto combine = [&](auto ss) {
+                with_sign(h->sign, [&](auto sg) {
+                    hipLaunchKernelGGL((k_fft_combine<decltype(ss)::value, decltype(sg)::value>), dim3(mi355_grid_256(h->ctx, total, 16)), dim3(256), 0, st,
+                                       (const c32 *)wa, dst, (const c32 *)h->d_tw, total, m_xor);
+                });
+            };
+            if (S == 8) combine(int_c<8>{});
+            else combine(int_c<16>{});
         }
-#undef COMB2
-        const long long total = (long long)nf * 4096;
-        long long blocks = (total + 255) / 256;
-        if (blocks > (long long)cus * 16) blocks = (long long)cus * 16;
-#define COMB(SS, SG) hipLaunchKernelGGL((k_fft_combine<SS, SG>), dim3((unsigned)blocks), dim3(256), 0, st, (const c32 *)h->d_wa, dst, (const c32 *)h->d_tw, total, m_xor)
-        if (S == 8) { if (h->sign < 0) COMB(8, -1); else COMB(8, 1); }
-        else        { if (h->sign < 0) COMB(16, -1); else COMB(16, 1); }
-#undef COMB
         MI355_HIP(hipGetLastError());
     }
-    return ws_release(h, st);
+    return h->ws.release(st);
 }
 
 int launch_mr_tile(mi355_fft *h, const void *in, void *out, int nframes, hipStream_t st)
 {
     const size_t N = (size_t)h->n;
-    size_t chunk = ((size_t)256 << 20) / (N * 8);  // workspace bounded to 256 MiB
-    if (chunk < 1) chunk = 1;
-    if (chunk > (size_t)nframes) chunk = (size_t)nframes;
     std::lock_guard<std::mutex> ws_guard(h->ws_lock);
-    {
-        const int rc = ws_acquire(h, st, chunk > h->cap_frames);
-        if (rc) return rc;
-    }
-    if (chunk > h->cap_frames) {
-        MI355_HIP(hipStreamSynchronize(st));
-        if (h->d_wa) (void)hipFree(h->d_wa);
-        h->d_wa = nullptr; h->cap_frames = 0;
-        MI355_HIP(hipMalloc(&h->d_wa, chunk * N * 8));
-        h->cap_frames = chunk;
-    }
+    size_t chunk;
+    if (const int rc = ws_frames(h, (size_t)256 << 20, N * 8, 1, nframes, st, &chunk)) return rc;  // workspace bounded to 256 MiB
     const size_t isz = h->dtype == MI355_DTYPE_FLOAT ? 4 : 8;
     for (size_t f0 = 0; f0 < (size_t)nframes; f0 += chunk) {
         const int nf = (int)((size_t)nframes - f0 < chunk ? (size_t)nframes - f0 : chunk);
-        const int rc = mi355_fft_mr_tile_launch(h->mrt, h->ctx, h->sign, (const char *)in + f0 * N * isz, h->d_wa, (char *)out + f0 * N * 8, h->d_window, nf,
-                                                h->shift, h->dtype == MI355_DTYPE_FLOAT, st);
+        const int rc = mi355_fft_mr_tile_launch(h->plan.mrt, h->ctx, h->sign, (const char *)in + f0 * N * isz, h->ws.get(), (char *)out + f0 * N * 8, h->d_window,
+                                                nf, h->shift, h->dtype == MI355_DTYPE_FLOAT, st);
         if (rc) return rc;
     }
     set_route(&h->rt, kRtMrTile);
-    return ws_release(h, st);
+    return h->ws.release(st);
 }
 
 // The claim word set of calls on stream st (NULL: the static schedule, same results).  The table is keyed by the stream's
@@ -1693,15 +1690,18 @@ unsigned *claim_words(mi355_fft *h, hipStream_t st)
 
 int launch_handle(mi355_fft *h, const void *in, void *out, int nvec, hipStream_t st)
 {
-    if (h->mrt.n) return launch_mr_tile(h, in, out, nvec, st);
-    if (h->mr.n) {
+    const int real_in = h->dtype == MI355_DTYPE_FLOAT;
+    switch (h->plan.kind) {
+    case kPlanMrTile: return launch_mr_tile(h, in, out, nvec, st);
+    case kPlanMr:
         set_route(&h->rt, kRtMr);
-        return mi355_fft_mr_launch(h->mr, h->ctx, h->sign, in, out, h->d_window, nvec, h->shift, h->dtype == MI355_DTYPE_FLOAT, st);
+        return mi355_fft_mr_launch(h->plan.mr, h->ctx, h->sign, in, out, h->d_window, nvec, h->shift, real_in, st);
+    case kPlanChirpz: return launch_bluestein(h, in, out, nvec, st);
+    case kPlanTile:
+    case kPlanSub: return launch_big(h, in, out, nvec, st);
+    case kPlanOnePass: break;
     }
-    if (h->m) return launch_bluestein(h, in, out, nvec, st);
-    if (h->n > 32768 || (h->n == 32768 && h->two_kernel)) return launch_big(h, in, out, nvec, st);
-    return launch_fft(h->ctx, h->n, h->sign, in, out, h->d_window, h->d_tw, nvec, h->shift, h->dtype == MI355_DTYPE_FLOAT, st,
-                      claim_words(h, st), &h->rt);
+    return launch_fft(h->ctx, h->n, h->sign, in, out, h->d_window, h->d_tw, nvec, h->shift, real_in, st, claim_words(h, st), &h->rt);
 }
 
 // iterative radix-2 FFT in double (host side, used once per handle for the chirp spectrum)
@@ -1741,31 +1741,29 @@ int upload(mi355_ctx *ctx, void **d, const void *src, size_t bytes)
     return MI355_OK;
 }
 
-std::vector<float> twiddle_table(int n, int sign)
+// appends exp(sign 2 pi i k / n), k < n, generated in double
+void push_roots(std::vector<float> &tw, int n, int sign)
 {
-    std::vector<float> tw;
-    tw.reserve(2 * (size_t)n + 8192);
     for (int k = 0; k < n; k++) {
         const double a = sign * 2.0 * M_PI * (double)k / (double)n;
         tw.push_back((float)cos(a));
         tw.push_back((float)sin(a));
     }
-    if (n > 4096)  // the interleaved sub-transform kernel also needs the 4096-point table
-        for (int k = 0; k < 4096; k++) {
-            const double a = sign * 2.0 * M_PI * (double)k / 4096.0;
-            tw.push_back((float)cos(a));
-            tw.push_back((float)sin(a));
-        }
+}
+
+std::vector<float> twiddle_table(int n, int sign)
+{
+    std::vector<float> tw;
+    tw.reserve(2 * (size_t)n + 8192);
+    push_roots(tw, n, sign);
+    if (n > 4096) push_roots(tw, 4096, sign);  // the interleaved sub-transform kernel also needs the 4096-point table
     return tw;
 }
 
 // tables of the chirp-z path; window == nullptr means all ones
 int setup_bluestein(mi355_fft *h, const float *window)
 {
-    const int N = h->n;
-    int M = 256;  // at least 256: the fused kernel's smallest instantiation (more zero padding is harmless)
-    while (M < 2 * N - 1) M <<= 1;
-    h->m = M;
+    const int N = h->n, M = h->plan.m;
     // a[n] = exp(sign * i*pi*n^2/N); n^2 reduced mod 2N in integers keeps the phase exact
     std::vector<double> ar(N), ai(N);
     for (int n = 0; n < N; n++) {
@@ -1819,9 +1817,8 @@ extern "C" int mi355_fft_create(mi355_ctx *ctx, int fft_size, int direction, con
 {
     MI355_REQUIRE(ctx && out, "NULL argument");
     *out = nullptr;
-    const bool pow2 = fft_size >= 2 && (fft_size & (fft_size - 1)) == 0;
-    if (fft_size < 2 || (pow2 && fft_size > 16777216) || (!pow2 && fft_size > 8388608)) {
-        mi355_set_error("fft size %d unsupported (powers of two 2..16777216, any other size 3..8388608)", fft_size);
+    if (!fft_in_range(fft_size)) {
+        mi355_set_error("fft size %d unsupported (%s)", fft_size, kFftRange);
         return fft_size < 2 ? MI355_ERR_INVALID_ARG : MI355_ERR_UNSUPPORTED;
     }
     MI355_REQUIRE(window_len == 0 || window_len == fft_size, "window not the same length as fft_size");
@@ -1837,45 +1834,21 @@ extern "C" int mi355_fft_create(mi355_ctx *ctx, int fft_size, int direction, con
     h->d_window = nullptr; h->d_tw = nullptr;
     auto fail = [&](int rc) { mi355_fft_destroy(h); return rc; };
     if (hipSetDevice(ctx->device) != hipSuccess) return fail(MI355_ERR_HIP);
-    std::vector<float> tw(2 * (size_t)fft_size);
-    for (int k = 0; k < fft_size; k++) {
-        double a = h->sign * 2.0 * M_PI * (double)k / (double)fft_size;
-        tw[2 * k] = (float)cos(a);
-        tw[2 * k + 1] = (float)sin(a);
-    }
-    if (fft_size > 4096) {  // the interleaved sub-transform kernel also needs the 4096-point table
-        for (int k = 0; k < 4096; k++) {
-            double a = h->sign * 2.0 * M_PI * (double)k / 4096.0;
-            tw.push_back((float)cos(a));
-            tw.push_back((float)sin(a));
-        }
-    }
-    if (pow2 && fft_size >= 65536 && fft_size <= 1048576 && !getenv("MI355_FFT_NO_TILE")) {
-        // two-pass tile scheme: N = n1 x n2, both 256 .. 1024; their twiddle tables follow the 4096-point one
-        int lg = 0;
-        while ((1 << lg) < fft_size) lg++;
-        // 131072 = 256 x 512: the 256-row pass first (its window values stay in registers); 2^19 = 1024 x 512 measured 3 % faster than 512 x 1024
-        h->tile_n1 = lg == 17 ? 256 : 1 << ((lg + 1) / 2);
-        if (const char *e = getenv("MI355_FFT_TILE_N1")) {  // (tuning switch)
-            const int v = atoi(e);
-            if ((v == 256 || v == 512 || v == 1024) && fft_size / v >= 256 && fft_size / v <= 1024) h->tile_n1 = v;
-        }
-        h->tile_n2 = fft_size / h->tile_n1;
-        for (int nr : {h->tile_n1, h->tile_n2})
-            for (int k = 0; k < nr; k++) {
-                double a = h->sign * 2.0 * M_PI * (double)k / (double)nr;
-                tw.push_back((float)cos(a));
-                tw.push_back((float)sin(a));
-            }
+    std::vector<float> mtw, mtw_b;  // host twiddle runs of the mixed-radix plans
+    fft_plan(fft_size, h->sign, true, &h->plan, &mtw, &mtw_b);
+    const FftKind kind = h->plan.kind;
+    std::vector<float> tw = twiddle_table(fft_size, h->sign);
+    if (kind == kPlanTile) {  // both tile sizes are 256 .. 1024; their twiddle tables follow the 4096-point one
+        push_roots(tw, h->plan.n1, h->sign);
+        push_roots(tw, h->plan.n2, h->sign);
     }
     if (hipMalloc(&h->d_tw, tw.size() * sizeof(float)) != hipSuccess) return fail(MI355_ERR_NOMEM);
     if (mi355_upload(ctx, h->d_tw, tw.data(), tw.size() * sizeof(float)) != hipSuccess) return fail(MI355_ERR_HIP);
     {
         std::vector<float> w(fft_size, 1.0f);  // no window == all ones: the kernel has a single code path
         if (window_len) memcpy(w.data(), window, sizeof(float) * (size_t)fft_size);
-        h->two_kernel = pow2 && (fft_size > 32768 || (fft_size == 32768 && getenv("MI355_FFT_32768_TWO_KERNELS") != nullptr));
-        if (h->two_kernel && !h->tile_n1) {
-            // two-kernel sizes: k_fft_sub reads the window values of the sub-frames (s .. s+3) for every n -- stored
+        if (kind == kPlanSub) {
+            // k_fft_sub reads the window values of the sub-frames (s .. s+3) for every n -- stored
             // quad-major, [s/4][n][4], they are one contiguous 16-byte load per lane instead of 16 bytes out of every S*4
             const int S = fft_size / 4096;
             std::vector<float> p((size_t)fft_size);
@@ -1888,16 +1861,17 @@ extern "C" int mi355_fft_create(mi355_ctx *ctx, int fft_size, int direction, con
         if (mi355_upload(ctx, h->d_window, w.data(), sizeof(float) * (size_t)fft_size) != hipSuccess)
             return fail(MI355_ERR_HIP);
     }
-    if (pow2 && fft_size <= 4096) {
+    if (kind == kPlanOnePass && fft_size <= 4096) {
         const std::vector<unsigned> zero((size_t)kClaimSets * kClaimSetWords, 0u);
         if (hipMalloc(&h->d_claims, zero.size() * sizeof(unsigned)) != hipSuccess) return fail(MI355_ERR_NOMEM);
         if (mi355_upload(ctx, h->d_claims, zero.data(), zero.size() * sizeof(unsigned)) != hipSuccess) return fail(MI355_ERR_HIP);
     }
     int rc = h->pipe.init(ctx);
     if (rc) return fail(rc);
-    if (!pow2) {
-        std::vector<float> mtw;
-        if (!getenv("MI355_FFT_NO_MR") && mi355_fft_mr_plan(fft_size, h->sign, 0, &h->mr, &mtw)) {
+    {
+        MrPlan &mr = h->plan.mr;
+        MrTilePlan &mrt = h->plan.mrt;
+        if (kind == kPlanMr) {
             // Two factorisations (fewest passes / at least 14 values per thread), each with its workgroup size and frames per iteration
             // measured once per length and process (fft_mr.hip); the faster one stays.  ~20 ms at the first handle of a length.
             auto put = [&](MrPlan &pl, const std::vector<float> &t) {
@@ -1917,53 +1891,48 @@ extern "C" int mi355_fft_create(mi355_ctx *ctx, int fft_size, int direction, con
             if (const char *e = getenv("MI355_FFT_MR_VARIANT")) known = atoi(e) != 0 ? 1 : 0;
             MrPlan alt;
             std::vector<float> atw;
-            const bool have_alt = mi355_fft_mr_plan(fft_size, h->sign, 1, &alt, &atw) && (alt.npass != h->mr.npass || alt.per_thread != h->mr.per_thread);
+            const bool have_alt = mi355_fft_mr_plan(fft_size, h->sign, 1, &alt, &atw) && (alt.npass != mr.npass || alt.per_thread != mr.per_thread);
             if (known == 1 && have_alt) {
-                h->mr = alt;
+                mr = alt;
                 mtw.swap(atw);
             }
-            if ((rc = put(h->mr, mtw))) return fail(rc);
+            if ((rc = put(mr, mtw))) return fail(rc);
             float ms0 = -1.f, ms1 = -1.f;
-            if ((rc = mi355_fft_mr_tune(&h->mr, ctx, h->sign, h->d_window, &ms0))) return fail(rc);
+            if ((rc = mi355_fft_mr_tune(&mr, ctx, h->sign, h->d_window, &ms0))) return fail(rc);
             if (known < 0 && have_alt && ms0 > 0.f && getenv("MI355_FFT_MR_TIMED_VARIANT")) {
                 if ((rc = put(alt, atw))) { if (alt.d_tw) (void)hipFree(alt.d_tw); return fail(rc); }
                 rc = mi355_fft_mr_tune(&alt, ctx, h->sign, h->d_window, &ms1);
                 if (rc) { (void)hipFree(alt.d_tw); return fail(rc); }
                 if (ms1 > 0.f && ms1 < ms0 * 0.90f) {
-                    (void)hipFree(h->mr.d_tw);
-                    h->mr = alt;
+                    (void)hipFree(mr.d_tw);
+                    mr = alt;
                 } else {
                     (void)hipFree(alt.d_tw);
                 }
             }
             if (ms0 > 0.f) {
-                mi355_fft_mr_remember(h->mr);
+                mi355_fft_mr_remember(mr);
                 mi355_log(ctx, MI355_LOG_INFO, "clFFT %d points (mixed radix): %d passes, %d threads x %d frame(s) per workgroup measured fastest", fft_size,
-                          h->mr.npass, h->mr.threads, h->mr.frames);
+                          mr.npass, mr.threads, mr.frames);
             }
-        } else {
-            h->mr.n = 0;
-            std::vector<float> twa, twb;
-            if (!getenv("MI355_FFT_NO_MR") && mi355_fft_mr_tile_plan(fft_size, h->sign, &h->mrt, &twa, &twb)) {
-                // two passes with the mixed-radix passes inside (fft_mr.hip); W_N^k is the table this handle already has
-                h->mrt.a.d_tw = h->mrt.b.d_tw = nullptr;
-                if (hipMalloc(&h->mrt.a.d_tw, twa.size() * sizeof(float) + 8) != hipSuccess) return fail(MI355_ERR_NOMEM);
-                if (hipMalloc(&h->mrt.b.d_tw, twb.size() * sizeof(float) + 8) != hipSuccess) return fail(MI355_ERR_NOMEM);
-                if (!twa.empty() && mi355_upload(ctx, h->mrt.a.d_tw, twa.data(), twa.size() * sizeof(float)) != hipSuccess) return fail(MI355_ERR_HIP);
-                if (!twb.empty() && mi355_upload(ctx, h->mrt.b.d_tw, twb.data(), twb.size() * sizeof(float)) != hipSuccess) return fail(MI355_ERR_HIP);
-                h->mrt.d_twn = h->d_tw;
-            } else {
-                h->mrt.n = 0;
-                rc = setup_bluestein(h, window_len ? window : nullptr);
-                if (rc) return fail(rc);
+        } else if (kind == kPlanMrTile) {
+            // two passes with the mixed-radix passes inside (fft_mr.hip); W_N^k is the table this handle already has
+            mrt.a.d_tw = mrt.b.d_tw = nullptr;
+            for (auto [pl, t] : {std::pair<MrPlan *, const std::vector<float> *>{&mrt.a, &mtw}, {&mrt.b, &mtw_b}}) {
+                if (hipMalloc(&pl->d_tw, t->size() * sizeof(float) + 8) != hipSuccess) return fail(MI355_ERR_NOMEM);
+                if (!t->empty() && mi355_upload(ctx, pl->d_tw, t->data(), t->size() * sizeof(float)) != hipSuccess) return fail(MI355_ERR_HIP);
             }
+            mrt.d_twn = h->d_tw;
+        } else if (kind == kPlanChirpz) {
+            rc = setup_bluestein(h, window_len ? window : nullptr);
+            if (rc) return fail(rc);
         }
     }
     // (the table uploads ran on the context's upload stream and were waited for there: mi355_upload; no device-wide wait)
     mi355_log(ctx, MI355_LOG_INFO, "clFFT: %d points, %s, %s input, %d stream(s), shift %d, window %s: %s", fft_size,
               h->sign < 0 ? "forward" : "reverse", dtype == MI355_DTYPE_COMPLEX ? "complex" : "float", num_streams, h->shift,
               window_len ? "given" : "none",
-              h->mr.n ? "mixed radix, one pass" : h->mrt.n ? "mixed radix, two passes over sixteen-column tiles" : !pow2 ? "chirp-z over a power-of-two transform" : h->tile_n1 ? "two passes over 16-column tiles" : h->two_kernel ? "multi-pass" : "one pass");
+              kPlanInfo[kind]);
     *out = h;
     return MI355_OK;
 }
@@ -1971,37 +1940,25 @@ extern "C" int mi355_fft_create(mi355_ctx *ctx, int fft_size, int direction, con
 extern "C" int mi355_fft_plan_text(int fft_size, char *buf, int buf_len)
 {
     MI355_REQUIRE(buf && buf_len > 0, "NULL argument");
-    const bool pow2 = fft_size >= 2 && (fft_size & (fft_size - 1)) == 0;
-    if (fft_size < 2 || (pow2 && fft_size > 16777216) || (!pow2 && fft_size > 8388608)) {
-        snprintf(buf, (size_t)buf_len, "unsupported (powers of two 2..16777216, any other size 3..8388608)");
+    FftPlan p;  // the default plan: what a handle made with no switch set runs
+    std::vector<float> tw, twb;
+    if (!fft_plan(fft_size, -1, false, &p, &tw, &twb)) {
+        snprintf(buf, (size_t)buf_len, "unsupported (%s)", kFftRange);
         return MI355_ERR_UNSUPPORTED;
     }
-    if (pow2) {
-        if (fft_size <= 32768) snprintf(buf, (size_t)buf_len, "one pass");
-        else if (fft_size <= 1048576) {
-            int lg = 0;
-            while ((1 << lg) < fft_size) lg++;
-            const int n1 = lg == 17 ? 256 : 1 << ((lg + 1) / 2);
-            snprintf(buf, (size_t)buf_len, "two tile passes %d x %d", n1, fft_size / n1);
-        } else snprintf(buf, (size_t)buf_len, "four passes");
-        return MI355_OK;
+    static const char *const count[] = {"two", "three", "four"};
+    int at = 0;
+    switch (p.kind) {
+    case kPlanOnePass: snprintf(buf, (size_t)buf_len, "one pass"); break;
+    case kPlanTile: snprintf(buf, (size_t)buf_len, "two tile passes %d x %d", p.n1, p.n2); break;
+    case kPlanSub: snprintf(buf, (size_t)buf_len, "%s passes", count[p.levels - 2]); break;  // (by default only above 2^20 points: four)
+    case kPlanMr:
+        at = snprintf(buf, (size_t)buf_len, "mixed radix ");
+        for (int i = 0; i < p.mr.npass && at < buf_len; i++) at += snprintf(buf + at, (size_t)(buf_len - at), i ? " x %d" : "%d", p.mr.pass[i].radix);
+        break;
+    case kPlanMrTile: snprintf(buf, (size_t)buf_len, "mixed radix, two passes %d x %d", p.mrt.n1, p.mrt.n2); break;
+    case kPlanChirpz: snprintf(buf, (size_t)buf_len, "chirp-z, m = %d%s", p.m, fft_chirpz_fused_size(p.m) ? " (fused)" : ""); break;
     }
-    MrPlan mp;
-    std::vector<float> tw;
-    if (mi355_fft_mr_plan(fft_size, -1, 0, &mp, &tw)) {
-        int at = snprintf(buf, (size_t)buf_len, "mixed radix ");
-        for (int p = 0; p < mp.npass && at < buf_len; p++) at += snprintf(buf + at, (size_t)(buf_len - at), p ? " x %d" : "%d", mp.pass[p].radix);
-        return MI355_OK;
-    }
-    MrTilePlan tp;
-    std::vector<float> twb;
-    if (mi355_fft_mr_tile_plan(fft_size, -1, &tp, &tw, &twb)) {
-        snprintf(buf, (size_t)buf_len, "mixed radix, two passes %d x %d", tp.n1, tp.n2);
-        return MI355_OK;
-    }
-    int m = 256;
-    while (m < 2 * fft_size - 1) m <<= 1;
-    snprintf(buf, (size_t)buf_len, "chirp-z, m = %d%s", m, m <= 16384 ? " (fused)" : "");
     return MI355_OK;
 }
 
@@ -2035,14 +1992,14 @@ extern "C" const char *mi355_fft_last_route(mi355_fft *h)
         break;
     case kRtMr:
         at = snprintf(t, n, "k_fft_mr ");
-        for (int p = 0; p < h->mr.npass && at < (int)n; p++) at += snprintf(t + at, n - (size_t)at, p ? "x%d" : "%d", h->mr.pass[p].radix);
-        if (at < (int)n) snprintf(t + at, n - (size_t)at, " threads=%d frames=%d", h->mr.threads, h->mr.frames);
+        for (int p = 0; p < h->plan.mr.npass && at < (int)n; p++) at += snprintf(t + at, n - (size_t)at, p ? "x%d" : "%d", h->plan.mr.pass[p].radix);
+        if (at < (int)n) snprintf(t + at, n - (size_t)at, " threads=%d frames=%d", h->plan.mr.threads, h->plan.mr.frames);
         break;
     case kRtMrTile:
-        at = snprintf(t, n, "k_fft_mr_tile %d x %d (", h->mrt.n1, h->mrt.n2);
-        for (const MrPlan *pl : {&h->mrt.a, &h->mrt.b}) {
+        at = snprintf(t, n, "k_fft_mr_tile %d x %d (", h->plan.mrt.n1, h->plan.mrt.n2);
+        for (const MrPlan *pl : {&h->plan.mrt.a, &h->plan.mrt.b}) {
             for (int p = 0; p < pl->npass && at < (int)n; p++) at += snprintf(t + at, n - (size_t)at, p ? "x%d" : "%d", pl->pass[p].radix);
-            if (at < (int)n) at += snprintf(t + at, n - (size_t)at, pl == &h->mrt.a ? ", " : ")");
+            if (at < (int)n) at += snprintf(t + at, n - (size_t)at, pl == &h->plan.mrt.a ? ", " : ")");
         }
         break;
     case kRtChirpz: snprintf(t, n, "k_chirpz<%d>", r.a); break;
@@ -2058,9 +2015,9 @@ extern "C" const char *mi355_fft_last_route(mi355_fft *h)
 
 const MrPlan *mi355_fft_mr_plan_of(const mi355_fft *h, int *sign)
 {
-    if (!h || !h->mr.n) return nullptr;
+    if (!h || h->plan.kind != kPlanMr) return nullptr;
     if (sign) *sign = h->sign;
-    return &h->mr;
+    return &h->plan.mr;
 }
 
 extern "C" int mi355_fft_destroy(mi355_fft *h)
@@ -2070,12 +2027,12 @@ extern "C" int mi355_fft_destroy(mi355_fft *h)
     h->pipe.release();
     if (h->d_window) (void)hipFree(h->d_window);
     if (h->d_tw) (void)hipFree(h->d_tw);
-    if (h->mr.d_tw) (void)hipFree(h->mr.d_tw);
-    if (h->mrt.a.d_tw) (void)hipFree(h->mrt.a.d_tw);
-    if (h->mrt.b.d_tw) (void)hipFree(h->mrt.b.d_tw);
-    for (void *p : {h->d_pre, h->d_post, h->d_bspec, h->d_twm_f, h->d_twm_i, (void *)h->d_ones, h->d_wa, h->d_wb, (void *)h->d_claims})
+    if (h->plan.mr.d_tw) (void)hipFree(h->plan.mr.d_tw);
+    if (h->plan.mrt.a.d_tw) (void)hipFree(h->plan.mrt.a.d_tw);
+    if (h->plan.mrt.b.d_tw) (void)hipFree(h->plan.mrt.b.d_tw);
+    for (void *p : {h->d_pre, h->d_post, h->d_bspec, h->d_twm_f, h->d_twm_i, (void *)h->d_ones, (void *)h->d_claims})
         if (p) (void)hipFree(p);
-    if (h->ws_done) (void)hipEventDestroy(h->ws_done);
+    h->ws.destroy();
     if (h->sub_f) (void)mi355_fft_destroy(h->sub_f);
     if (h->sub_i) (void)mi355_fft_destroy(h->sub_i);
     delete h;
@@ -2090,7 +2047,7 @@ extern "C" int mi355_fft_work_dev(mi355_fft *h, int nvec, const void *in, void *
     MI355_REQUIRE((reinterpret_cast<uintptr_t>(in) & 7u) == 0 && (reinterpret_cast<uintptr_t>(out) & 7u) == 0,
                   "device buffers must be 8-byte aligned");
     // the 8192/16384-point kernel reads 16 bytes per lane
-    MI355_REQUIRE(h->m != 0 || h->n <= 4096 || (reinterpret_cast<uintptr_t>(in) & 15u) == 0,
+    MI355_REQUIRE(h->plan.kind == kPlanChirpz || h->n <= 4096 || (reinterpret_cast<uintptr_t>(in) & 15u) == 0,
                   "device input of an 8192/16384-point transform must be 16-byte aligned");
     MI355_HIP(hipSetDevice(h->ctx->device));
     return launch_handle(h, in, out, nvec, mi355_pick_stream(h->ctx, stream));
@@ -2115,7 +2072,7 @@ extern "C" int mi355_fft_work(mi355_fft *h, int nvec, const void *const *in_stre
     // all (stream, chunk) pairs run through the staging slots back to back; a small call is one chunk per stream on the direct path,
     // the kernels working on the pinned staging themselves (see common.h)
     const size_t nchunks = ((size_t)nvec + chunk_frames - 1) / chunk_frames;
-    const bool one_stream = h->m || h->mrt.n || h->n > 32768 || (h->n == 32768 && h->two_kernel);  // chirp-z / multi-pass sizes share work buffers: one stream
+    const bool one_stream = h->plan.kind != kPlanOnePass && h->plan.kind != kPlanMr;  // chirp-z / multi-pass sizes share work buffers: one stream
     const HostPipe::Plan plan{nslots, one_stream, (size_t)nvec <= chunk_frames && mi355_direct_ok((size_t)nvec * out_frame, h->ctx)};
     auto frames = [&](size_t i) { return HostPipe::part((size_t)nvec, chunk_frames, i % nchunks); };
     return h->pipe.run(

@@ -932,7 +932,7 @@ int launch_with(const MrPlan &plan, int threads, int frames, mi355_ctx *ctx, int
     static const int copy_nb = getenv("MI355_FFT_MR_COPY_IN_NB") ? atoi(getenv("MI355_FFT_MR_COPY_IN_NB")) : 16;
     if (copy_nb != 16) MI355_SWITCH_NOTE(ctx, "MI355_FFT_MR_COPY_IN_NB", "another run length below which k_fft_mr loads through LDS");
     a.copy_in = plan.pass[0].nb < copy_nb && !no_copy_out;
-    const int cus = ctx->num_cus > 0 ? ctx->num_cus : 256;
+    const int cus = mi355_cus(ctx);
     const int lds_bytes = lds_bytes_for(plan.n, frames);
     int per_cu = (160 * 1024) / lds_bytes;
     if (per_cu > 2048 / threads) per_cu = 2048 / threads;
@@ -990,7 +990,7 @@ int mi355_fft_mr_pfb_launch(const MrPlan &plan, mi355_ctx *ctx, const void *in, 
     if (th_env >= 64 && th_env <= 512 && th_env % 64 == 0 && ranges_of(th_env) >= 1) th = th_env;
     const int Q = ranges_of(th);
     if (Q < 1) return MI355_ERR_INVALID_ARG;
-    const int cus = ctx->num_cus > 0 ? ctx->num_cus : 256;
+    const int cus = mi355_cus(ctx);
     int ntw = 0;
     for (int p = 1; p < plan.npass; p++) ntw += plan.pass[p].ns;
     const int tw_lds = lds_bytes_for(M, Q * FS) / 8;
@@ -1089,7 +1089,7 @@ int mi355_fft_mr_synth_launch(const MrPlan &plan, const MrSynthGeo &g, mi355_ctx
 {
     if (nframes <= 0) return MI355_OK;
     const int M = plan.n, F = g.frames;
-    const int cus = ctx->num_cus > 0 ? ctx->num_cus : 256;
+    const int cus = mi355_cus(ctx);
     int per_cu = (160 * 1024) / g.lds_bytes;
     if (per_cu > 2048 / g.threads) per_cu = 2048 / g.threads;
     if (per_cu < 1) per_cu = 1;
@@ -1297,7 +1297,7 @@ int mi355_fft_mr_tile_launch(const MrTilePlan &tp, mi355_ctx *ctx, int sign, con
             lds_ok[which] = true;
         }
     }
-    const int cus = ctx->num_cus > 0 ? ctx->num_cus : 256;
+    const int cus = mi355_cus(ctx);
     for (int pass = 0; pass < 2; pass++) {
         const MrPlan &pl = pass ? tp.b : tp.a;
         TileArgs a;

@@ -1108,7 +1108,7 @@ int launch_ols_g(mi355_filter *h, size_t nout, const void *in, void *out, hipStr
             if (nblocks > 0x7fffffffLL) { mi355_set_error("work() call too large"); return MI355_ERR_INVALID_ARG; }
             // a run of consecutive blocks per workgroup (the P - 1 warm-up transforms of a run are the overhead): two
             // workgroups per CU when the call is large enough, one block per workgroup for scheduler-sized calls
-            const int cus = h->ctx->num_cus > 0 ? h->ctx->num_cus : 256;
+            const int cus = mi355_cus(h->ctx);
             int wgs = cus * 2;
             if (const char *e = getenv("MI355_OLS_UPS_WGS")) wgs = atoi(e) > 0 ? atoi(e) : wgs;
             const int run = (int)((nblocks + wgs - 1) / wgs);
@@ -1199,7 +1199,7 @@ int launch_filter(mi355_filter *h, size_t nout, const void *in, void *out, hipSt
         mi355_set_error("internal: no fast-convolution kernel for FFT size %d", h->nf);
         return MI355_ERR_STATE;
     }
-    int cus = h->ctx->num_cus > 0 ? h->ctx->num_cus : 256;
+    int cus = mi355_cus(h->ctx);
     static const bool mf_on = !getenv("MI355_FIR_MFMA") || atoi(getenv("MI355_FIR_MFMA")) != 0;
     // decimations 2-8 keep every decim-th output of the same product; that variant needs more registers (2 workgroups per CU)
     // and only pays from ~100 taps (129 taps, decimation 2: 137 -> 148 GS/s; 65 taps: equal)

@@ -1,5 +1,5 @@
-// HostPipe (common.h): the staging buffers and per-slot events of the host-pointer work() path, and DevBuf, the device scratch of
-// the pageable host paths.  This unit and the drivers, HostPipe::run and mi355_pageable_run in common.h, use the HIP runtime's host
+// HostPipe (common.h): the staging buffers and per-slot events of the host-pointer work() path, DevBuf, the device scratch of
+// the pageable host paths, and DevWorkspace, the stream-ordered workspace of a handle.  This unit and the drivers, HostPipe::run and mi355_pageable_run in common.h, use the HIP runtime's host
 // API only, so that tests/hostpipe_host_main.cc can compile them with a host compiler over stubs of those calls.
 #include "common.h"
 
@@ -26,6 +26,39 @@ void DevBuf::release()
     if (p) (void)hipFree(p);
     p = nullptr;
     n = 0;
+}
+
+int DevWorkspace::acquire(size_t bytes, hipStream_t st)
+{
+    if (!done) MI355_HIP(hipEventCreateWithFlags(&done, hipEventDisableTiming));
+    if (used && last != st) MI355_HIP(hipStreamWaitEvent(st, done, 0));
+    if (bytes > buf.bytes() && used) MI355_HIP(hipEventSynchronize(done));  // kernels of an earlier call still use the old one
+    return buf.reserve(bytes);
+}
+
+int DevWorkspace::release(hipStream_t st)
+{
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return MI355_OK;
+    MI355_HIP(hipEventRecord(done, st));
+    last = st;
+    used = true;
+    return MI355_OK;
+}
+
+int DevWorkspace::wait()
+{
+    if (used) MI355_HIP(hipEventSynchronize(done));
+    return MI355_OK;
+}
+
+void DevWorkspace::destroy()
+{
+    buf.release();
+    if (done) (void)hipEventDestroy(done);
+    done = nullptr;
+    last = nullptr;
+    used = false;
 }
 
 int HostPipe::init(mi355_ctx *c)

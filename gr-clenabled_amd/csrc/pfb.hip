@@ -853,7 +853,7 @@ template <int M, int PMAX>
 int launch_wave(mi355_pfb *h, const void *in, void *out, hipStream_t st, int nsteps, long long buf_items)
 {
     const int ngroups = (nsteps + 15) / 16;
-    const int cus = h->ctx->num_cus > 0 ? h->ctx->num_cus : 256;
+    const int cus = mi355_cus(h->ctx);
     // fewer 16-step groups than two per CU: one workgroup per group, its steps split over four sets of M threads (k_pfbq)
     const int small_on = getenv("MI355_PFB_SMALL") ? atoi(getenv("MI355_PFB_SMALL")) : 1;  // (read per call: a tuning / test switch)
     if constexpr (!(M == 256 && PMAX > 16) && M <= 256) {  // (1024 threads x 32 taps per arm would spill: that shape keeps the ring kernel; 512 channels too)
@@ -893,7 +893,7 @@ int launch_wave(mi355_pfb *h, const void *in, void *out, hipStream_t st, int nst
 template <int M, int PMAX>
 int launch_wave_over(mi355_pfb *h, const void *in, void *out, hipStream_t st, int nsteps)
 {
-    const int S = h->M / h->R, cus = h->ctx->num_cus > 0 ? h->ctx->num_cus : 256;
+    const int S = h->M / h->R, cus = mi355_cus(h->ctx);
     const long long n_in = (long long)nsteps * h->R - h->R + h->K;
     // (512 channels: one 8-wave workgroup per CU and a single round: 8 -> 133 us, 16 -> 142, 32 -> 157 per 2^25 items)
     const int wpc = getenv("MI355_PFB_WAVES_PER_CU") ? atoi(getenv("MI355_PFB_WAVES_PER_CU")) : (M >= 512 ? 8 : 16);
@@ -928,7 +928,7 @@ int launch_streams(mi355_pfb *h, const void *in, void *out, hipStream_t st, int 
 {
     constexpr int SEG = 64 / M;
     const int ngroups = (nsteps + 15) / 16;
-    const int cus = h->ctx->num_cus > 0 ? h->ctx->num_cus : 256;
+    const int cus = mi355_cus(h->ctx);
     long long streams = (long long)cus * 8 * SEG;  // 8 waves per CU, SEG streams per wave
     if (streams > ngroups) streams = ngroups;
     const int gps = (int)((ngroups + streams - 1) / streams);
@@ -1046,7 +1046,7 @@ int launch_pfb(mi355_pfb *h, const void *in, void *out, hipStream_t st, int nste
             set_route(h, kRtMr, P_mr <= 8 ? 8 : P_mr <= 16 ? 16 : 32, 0, h->whole_map ? kRt2None : kRt2Map);
             if (!h->whole_map) {
                 const long long tot = (long long)nsteps * h->nmap, blocks = (tot + 255) / 256;
-                const long long cu8 = (long long)(h->ctx->num_cus > 0 ? h->ctx->num_cus : 256) * 8;
+                const long long cu8 = (long long)mi355_cus(h->ctx) * 8;
                 hipLaunchKernelGGL(k_pfb_map, dim3((unsigned)(blocks < cu8 ? (blocks < 1 ? 1 : blocks) : cu8)), dim3(256), 0, st, (const c32 *)h->d_filt2,
                                    (c32 *)out, h->d_map, h->nmap, h->M, tot);
                 MI355_HIP(hipGetLastError());
@@ -1054,7 +1054,7 @@ int launch_pfb(mi355_pfb *h, const void *in, void *out, hipStream_t st, int nste
             return MI355_OK;
         }
     }
-    int cus = h->ctx->num_cus > 0 ? h->ctx->num_cus : 256;
+    int cus = mi355_cus(h->ctx);
     long long total = (long long)nsteps * h->M;
     long long blocks = (total + 255) / 256;
     long long grid = blocks < (long long)cus * 8 ? blocks : (long long)cus * 8;

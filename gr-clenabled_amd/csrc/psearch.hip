@@ -368,7 +368,7 @@ int psr_launch_tiled(const mi355_psearch *h, const PsArgs &a, int wg_per_cu, con
 {
     if (h->lds_bytes > (64 << 10))
         MI355_HIP(hipFuncSetAttribute((const void *)k_ps_tiled<ORDER, THREADS, NS, EP, CH>, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_bytes));
-    const int cus = h->ctx->num_cus > 0 ? h->ctx->num_cus : 256;
+    const int cus = mi355_cus(h->ctx);
     const long long cap = (long long)cus * wg_per_cu * 4;  // four rounds of the resident workgroups
     const dim3 grid((unsigned)(a.units < cap ? a.units : cap));
     hipLaunchKernelGGL((k_ps_tiled<ORDER, THREADS, NS, EP, CH>), grid, dim3(THREADS), (size_t)h->lds_bytes, st, in, stats, keys, a);
@@ -379,7 +379,7 @@ int psr_launch_tiled(const mi355_psearch *h, const PsArgs &a, int wg_per_cu, con
 int psr_launch(mi355_psearch *h, long long n, const void *in, long long in_pitch, void *peaks, void *cands, long long max_cands, void *counts,
                hipStream_t st)
 {
-    const int cus = h->ctx->num_cus > 0 ? h->ctx->num_cus : 256;
+    const int cus = mi355_cus(h->ctx);
     const float *d_stats = (const float *)h->stab.current();
     const long long nrec = n / h->Tb * h->S;
     auto small_grid = [&](long long items) {
@@ -670,7 +670,7 @@ extern "C" int mi355_psearch_measure(mi355_psearch *h, long long n, const void *
         x = (const float *)h->d_in.get();
         pitch = n;
     }
-    const int cus = h->ctx->num_cus > 0 ? h->ctx->num_cus : 256;
+    const int cus = mi355_cus(h->ctx);
     const dim3 grid((unsigned)(S < (long long)cus * 8 ? S : (long long)cus * 8));
     hipLaunchKernelGGL(k_ps_stats, grid, dim3(256), 0, st, x, n, time_major ? 1ll : pitch, time_major ? S : 1ll, (int)S, (float *)h->d_out.get());
     std::vector<float> res(2 * (size_t)S);

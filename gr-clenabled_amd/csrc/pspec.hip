@@ -300,10 +300,7 @@ struct mi355_pspec {
     std::string route_name;
     // one workspace per handle (fused K > C: partial sums; generic: gathered frames, transformed frames, carried sums); calls on different
     // streams are ordered on it: the later stream waits for the earlier call's kernels
-    DevBuf ws;
-    hipEvent_t ws_done = nullptr;
-    hipStream_t ws_stream = nullptr;
-    bool ws_used = false;
+    DevWorkspace ws;
     DevBuf d_in, d_out;  // host path staging
     std::mutex lock;
 };
@@ -334,31 +331,6 @@ int ps_ensure_fft(mi355_pspec *h)
                             1, h->shift, &h->fft);
 }
 
-int ps_ws_acquire(mi355_pspec *h, size_t bytes, hipStream_t st)
-{
-    if (h->ws_used && h->ws_stream != st) MI355_HIP(hipStreamWaitEvent(st, h->ws_done, 0));
-    if (bytes > h->ws.bytes() && h->ws_used) MI355_HIP(hipEventSynchronize(h->ws_done));  // kernels of an earlier call still use the old one
-    return h->ws.reserve(bytes);
-}
-
-int ps_ws_release(mi355_pspec *h, hipStream_t st)
-{
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return MI355_OK;  // a graph orders its own nodes
-    MI355_HIP(hipEventRecord(h->ws_done, st));
-    h->ws_stream = st;
-    h->ws_used = true;
-    return MI355_OK;
-}
-
-unsigned ps_grid(const mi355_ctx *ctx, long long total)
-{
-    const long long cus = ctx->num_cus > 0 ? ctx->num_cus : 256;
-    long long g = (total + 255) / 256;
-    if (g > cus * 32) g = cus * 32;
-    return (unsigned)(g < 1 ? 1 : g);
-}
-
 #define PS_SIZES(X) X(16) X(32) X(64) X(128) X(256) X(512) X(1024) X(2048) X(4096)
 
 int ps_launch_fused(mi355_pspec *h, long long S, const void *in, float *out, hipStream_t st)
@@ -387,7 +359,7 @@ int ps_launch_fused(mi355_pspec *h, long long S, const void *in, float *out, hip
     }
     if (per > S) per = S;
     if (nchunks > 1) {
-        const int rc = ps_ws_acquire(h, (size_t)per * nchunks * N * sizeof(float), st);
+        const int rc = h->ws.acquire((size_t)per * nchunks * N * sizeof(float), st);
         if (rc) return rc;
     }
     for (long long s0 = 0; s0 < S; s0 += per) {
@@ -399,11 +371,11 @@ int ps_launch_fused(mi355_pspec *h, long long S, const void *in, float *out, hip
         PS_SIZES(X)
 #undef X
         if (nchunks > 1)
-            hipLaunchKernelGGL(k_pspec_finish, dim3(ps_grid(h->ctx, n * N)), dim3(256), 0, st, (const float *)h->ws.get(), out + s0 * N, N, nchunks,
+            hipLaunchKernelGGL(k_pspec_finish, dim3(mi355_grid_256(h->ctx, n * N, 32)), dim3(256), 0, st, (const float *)h->ws.get(), out + s0 * N, N, nchunks,
                                h->shift ? N / 2 : 0, a.sk, h->log_output, n * N);
     }
     MI355_HIP(hipGetLastError());
-    return nchunks > 1 ? ps_ws_release(h, st) : MI355_OK;
+    return nchunks > 1 ? h->ws.release(st) : MI355_OK;
 }
 
 int ps_launch_generic(mi355_pspec *h, long long S, const void *in, float *out, hipStream_t st)
@@ -425,7 +397,7 @@ int ps_launch_generic(mi355_pspec *h, long long S, const void *in, float *out, h
     const long long nb = K <= B ? K * per : B;     // frames of the largest batch
     // [gathered frames][transformed frames][carried sums]
     const size_t frames_bytes = (size_t)nb * N * 8, acc_bytes = (size_t)N * sizeof(float);
-    rc = ps_ws_acquire(h, (gather ? 2 : 1) * frames_bytes + acc_bytes, st);
+    rc = h->ws.acquire((gather ? 2 : 1) * frames_bytes + acc_bytes, st);
     if (rc) return rc;
     char *ws = (char *)h->ws.get();
     f2v *d_g = (f2v *)ws;
@@ -434,7 +406,7 @@ int ps_launch_generic(mi355_pspec *h, long long S, const void *in, float *out, h
     auto transform = [&](const f2v *src, long long nfr) {
         const void *fin = src;
         if (H != N || (N > 4096 && (reinterpret_cast<uintptr_t>(src) & 15u) != 0)) {
-            hipLaunchKernelGGL(k_pspec_gather, dim3(ps_grid(h->ctx, nfr * N)), dim3(256), 0, st, src, d_g, N, H, nfr * N);
+            hipLaunchKernelGGL(k_pspec_gather, dim3(mi355_grid_256(h->ctx, nfr * N, 32)), dim3(256), 0, st, src, d_g, N, H, nfr * N);
             fin = d_g;
         }
         return mi355_fft_work_dev(h->fft, (int)nfr, fin, d_x, (void *)st);
@@ -444,7 +416,7 @@ int ps_launch_generic(mi355_pspec *h, long long S, const void *in, float *out, h
             const long long n = S - s0 < per ? S - s0 : per;
             rc = transform((const f2v *)in + s0 * K * H, n * K);
             if (rc) return rc;
-            hipLaunchKernelGGL(k_pspec_acc, dim3(ps_grid(h->ctx, n * N)), dim3(256), 0, st, (const c32 *)d_x, d_acc, out + s0 * N, N, K, 1, 1, sk,
+            hipLaunchKernelGGL(k_pspec_acc, dim3(mi355_grid_256(h->ctx, n * N, 32)), dim3(256), 0, st, (const c32 *)d_x, d_acc, out + s0 * N, N, K, 1, 1, sk,
                                h->log_output, n * N);
         }
     } else {
@@ -453,12 +425,12 @@ int ps_launch_generic(mi355_pspec *h, long long S, const void *in, float *out, h
                 const long long n = K - f0 < B ? K - f0 : B;
                 rc = transform((const f2v *)in + (s * K + f0) * H, n);
                 if (rc) return rc;
-                hipLaunchKernelGGL(k_pspec_acc, dim3(ps_grid(h->ctx, N)), dim3(256), 0, st, (const c32 *)d_x, d_acc, out + s * N, N, (int)n, f0 == 0,
+                hipLaunchKernelGGL(k_pspec_acc, dim3(mi355_grid_256(h->ctx, N, 32)), dim3(256), 0, st, (const c32 *)d_x, d_acc, out + s * N, N, (int)n, f0 == 0,
                                    f0 + n == K, sk, h->log_output, (long long)N);
             }
     }
     MI355_HIP(hipGetLastError());
-    return ps_ws_release(h, st);
+    return h->ws.release(st);
 }
 
 // caller holds h->lock and has set the device
@@ -536,7 +508,6 @@ extern "C" int mi355_pspec_create(mi355_ctx *ctx, int fft_size, const float *win
         mi355_set_error("mi355_pspec_create: hipSetDevice failed");
         return fail(MI355_ERR_HIP);
     }
-    if (hipEventCreateWithFlags(&h->ws_done, hipEventDisableTiming) != hipSuccess) return fail(MI355_ERR_HIP);
     if (ps_fused_size(N)) {
         std::vector<float> tw((size_t)2 * N);
         for (int k = 0; k < N; k++) {
@@ -563,8 +534,8 @@ extern "C" int mi355_pspec_destroy(mi355_pspec *h)
     if (h->fft) (void)mi355_fft_destroy(h->fft);
     h->win.release();
     if (h->d_tw) (void)hipFree(h->d_tw);
-    for (DevBuf *b : {&h->ws, &h->d_in, &h->d_out}) b->release();
-    if (h->ws_done) (void)hipEventDestroy(h->ws_done);
+    h->ws.destroy();
+    for (DevBuf *b : {&h->d_in, &h->d_out}) b->release();
     delete h;
     return MI355_OK;
 }
@@ -588,7 +559,7 @@ extern "C" int mi355_pspec_set_window(mi355_pspec *h, const float *window, int w
     h->win_host.assign((size_t)h->N, 1.0f);
     if (window_len) memcpy(h->win_host.data(), window, sizeof(float) * (size_t)h->N);
     if (h->fft) {  // the internal clFFT carries its window: a new one is made at the next generic call (its kernels in flight end first)
-        if (h->ws_used) MI355_HIP(hipEventSynchronize(h->ws_done));
+        if (const int rc = h->ws.wait()) return rc;
         (void)mi355_fft_destroy(h->fft);
         h->fft = nullptr;
     }

@@ -316,7 +316,7 @@ int rs_launch(mi355_resampler *h, long long n, int phase, const void *in, void *
     const c32 *x = (const c32 *)in;
     c32 *y = (c32 *)out;
     const float *d_rev = (const float *)h->rev.current();
-    const int cus = h->ctx->num_cus > 0 ? h->ctx->num_cus : 256;
+    const int cus = mi355_cus(h->ctx);
     if (h->interp) {
         const long long bcount = ((long long)phase + n - 1) / h->L + 1, tiles = (bcount + kRiTile - 1) / kRiTile, cap = (long long)cus * h->wg_per_cu;
         const dim3 grid((unsigned)(tiles < cap ? tiles : cap));

@@ -308,7 +308,7 @@ extern "C" int mi355_pack3d_dev(mi355_ctx *ctx, void *dst, const void *src, size
     const size_t vec = (all & 15u) == 0 ? 16 : (all & 3u) == 0 ? 4 : 1;
     const size_t wv = width_bytes / vec, total = nblocks * rows * wv;
     size_t blocks = (total + 255) / 256;
-    const size_t cap = (size_t)(ctx->num_cus > 0 ? ctx->num_cus : 256) * 32;
+    const size_t cap = (size_t)mi355_cus(ctx) * 32;
     if (blocks > cap) blocks = cap;
     typedef int v4i_t __attribute__((ext_vector_type(4)));
     if (vec == 16)

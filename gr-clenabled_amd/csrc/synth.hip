@@ -285,7 +285,7 @@ int syn_upload(mi355_synth *h, const float *taps, int K)
 int syn_launch(mi355_synth *h, long long nframes, const void *in, void *out, hipStream_t st)
 {
     const int M = h->M, T = h->T;
-    const int cus = h->ctx->num_cus > 0 ? h->ctx->num_cus : 256;
+    const int cus = mi355_cus(h->ctx);
     const int *map = h->ident ? nullptr : h->d_map;
     const float *d_taps = (const float *)h->taps.current();
     if (h->route == kRouteMr) return mi355_fft_mr_synth_launch(h->plan, h->mg, h->ctx, in, out, d_taps, map, h->nmap, T, nframes, st);

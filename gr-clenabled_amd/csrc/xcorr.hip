@@ -252,7 +252,7 @@ int launch_composed(mi355_xcorr_fft *h, const XcArgs &a, int nframes, hipStream_
         for (void *&w : h->d_ws) MI355_HIP(hipMalloc(&w, chunk * n * 8));
         h->ws_frames = chunk;
     }
-    const int cus = h->ctx->num_cus > 0 ? h->ctx->num_cus : 256;
+    const int cus = mi355_cus(h->ctx);
     for (size_t f0 = 0; f0 < (size_t)nframes; f0 += chunk) {
         const int nf = (int)((size_t)nframes - f0 < chunk ? (size_t)nframes - f0 : chunk);
         const long long total = (long long)nf * (long long)n;

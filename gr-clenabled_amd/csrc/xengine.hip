@@ -1185,7 +1185,7 @@ int launch_xe_body(mi355_xengine *h, const void *in, void *out, int accumulate, 
         if (ts_env <= 0 && g.T >= 64) {
             // few channels: more time ranges, so that (channel groups) x (ranges) still covers the CUs -- 64 antennas x 16 channels x 16384
             // frames ran as 4 workgroups (2.2 ms); the ranges keep at least two K blocks each and their partial matrices fit the workspace
-            const int cus = h->ctx->num_cus > 0 ? h->ctx->num_cus : 256, groups = (g.F + 7) / 8, kb_total = (g.T + kKB32 - 1) / kKB32;
+            const int cus = mi355_cus(h->ctx), groups = (g.F + 7) / 8, kb_total = (g.T + kKB32 - 1) / kKB32;
             int want = cus / groups;  // the most ranges that still run as one round of workgroups (125 groups x 3 ranges: a second round at 46 % -- slower than 2)
             if (want > kb_total / 2) want = kb_total / 2;
             while (want > 2 && (size_t)want * out_items * 8 > h->tile_bytes) want--;
@@ -1200,7 +1200,7 @@ int launch_xe_body(mi355_xengine *h, const void *in, void *out, int accumulate, 
         const size_t rows = (size_t)g.T * g.N;
         const int dst_units = g.F, src_units = g.Fout;  // 2-byte units per row (IChar one polarisation / packed: 2 bytes per channel)
         size_t blocks = (rows * dst_units + 255) / 256;
-        const size_t cap = (size_t)(h->ctx->num_cus > 0 ? h->ctx->num_cus : 256) * 16;
+        const size_t cap = (size_t)mi355_cus(h->ctx) * 16;
         if (blocks > cap) blocks = cap;
         if (h->data_type == MI355_DTYPE_COMPLEX) {
             const int du = g.F * g.npol, su = g.Fout * g.npol;  // complex values per row
@@ -1236,7 +1236,7 @@ int launch_xe_body(mi355_xengine *h, const void *in, void *out, int accumulate, 
             MI355_HIP(hipGetLastError());
             const size_t real_items = (size_t)g.Fout * (g.N * (g.N + 1) / 2) * g.npol * g.npol;
             size_t blocks = (real_items + 255) / 256;
-            const size_t cap = (size_t)(h->ctx->num_cus > 0 ? h->ctx->num_cus : 256) * 16;
+            const size_t cap = (size_t)mi355_cus(h->ctx) * 16;
             if (blocks > cap) blocks = cap;
             hipLaunchKernelGGL(k_xe_reduce, dim3((unsigned)blocks), dim3(256), 0, st, (const c32 *)tiles, (c32 *)out, real_items, out_items, tsplit, accumulate);
             MI355_HIP(hipGetLastError());
@@ -1341,7 +1341,7 @@ int launch_xe_body(mi355_xengine *h, const void *in, void *out, int accumulate, 
             SbArgs sa;
             sa.tiles = tiles; sa.out = (c32 *)out; sa.g = gs; sa.kd = kd; sa.accumulate = accumulate;
             sa.dbg = getenv("MI355_XE_DBG") ? atoi(getenv("MI355_XE_DBG")) : 0;
-            const int cus = h->ctx->num_cus > 0 ? h->ctx->num_cus : 256;
+            const int cus = mi355_cus(h->ctx);
             // 8 row tiles: the ring is 64 KiB and a workgroup four waves, so two workgroups share a CU -- one stores its matrix while the
             // other multiplies (what the 16-tile form cannot do: there one channel's accumulators fill half the CU's registers)
             const int wgs = cus * (g.NT == 8 ? 2 : g.NT == 6 ? 3 : 1);  // (6 row tiles: 48 KiB rings, three workgroups of three waves)

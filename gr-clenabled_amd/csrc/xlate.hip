@@ -343,7 +343,7 @@ int xl_set_taps(mi355_xlate *h, const void *taps, int K)
 // caller holds the lock and has set the device; `phase`: P_c of output 0 of this launch
 int xl_launch(mi355_xlate *h, long long n, const void *in, void *const *outs, const u64 *phase, hipStream_t st)
 {
-    const int cus = h->ctx->num_cus > 0 ? h->ctx->num_cus : 256;
+    const int cus = mi355_cus(h->ctx);
     if (h->fused && !h->generic) {
         XlArgs a = {};
         for (int c = 0; c < h->C; c++) { a.out[c] = (c32 *)outs[c]; a.phase[c] = phase[c]; a.inc[c] = h->inc[c]; }

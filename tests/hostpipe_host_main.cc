@@ -1,6 +1,6 @@
-// Stand-alone program around HostPipe, mi355_pageable_run and DevBuf (csrc/common.h, csrc/hostpipe.hip) for
+// Stand-alone program around HostPipe, mi355_pageable_run, DevBuf and DevWorkspace (csrc/common.h, csrc/hostpipe.hip) for
 // tests/test_hostpipe_host.py: the two drivers behind every block's host-pointer work(), the staging pipeline first and the piece
-// loop of the pageable paths after it, over SYNCHRONOUS HOST STUBS of the dozen HIP runtime calls they make, no device.  "Device"
+// loop of the pageable paths after it, then the stream-ordered workspace of clFFT, clPowerSpectrum and clFEngine, over SYNCHRONOUS HOST STUBS of the dozen HIP runtime calls they make, no device.  "Device"
 // and pinned buffers are heap blocks of exactly the size ensure() asked for and the caller's buffers are heap blocks of exactly the
 // size describe() names, so under -fsanitize=address,undefined a copy of one byte too many is caught.  The "kernel" is a host
 // function: output byte j of chunk ci = input byte j (xor the second input's) xor key(ci).  Every stubbed call is logged, and the
@@ -11,18 +11,19 @@
 #include <string>
 
 // ---- the log -------------------------------------------------------------------------------------------------------------------
-enum Kind { EV_RECORD, EV_SYNC, COPY_IN, COPY_OUT, H2D, D2H, STREAM_SYNC, DIRECT_SYNC, LAUNCH, DELIVER, FAIL, DEV_MALLOC, DEV_FREE };
+enum Kind { EV_RECORD, EV_SYNC, COPY_IN, COPY_OUT, H2D, D2H, STREAM_SYNC, DIRECT_SYNC, LAUNCH, DELIVER, FAIL, DEV_MALLOC, DEV_FREE, STREAM_WAIT };
 struct Entry { Kind kind; int slot; size_t arg; };
 static std::vector<Entry> g_log;
 static HostPipe *g_pipe = nullptr;  // nullptr: the pageable driver and DevBuf are under test, and hipMalloc / hipFree are logged too
 static int g_memcpy_calls = 0, g_memcpy_fail_at = -1;  // the g_memcpy_fail_at-th hipMemcpyAsync fails, once
 static int g_malloc_calls = 0, g_malloc_fail_at = -1;  // the same for hipMalloc
 static int g_sync_calls = 0, g_sync_fail_at = -1;      // and for hipStreamSynchronize
+static bool g_capturing = false;                       // what hipStreamIsCapturing answers
 static std::string g_err;
 
 static int slot_of_event(hipEvent_t e)
 {
-    for (int s = 0; s < HostPipe::kSlots; s++)
+    for (int s = 0; g_pipe && s < HostPipe::kSlots; s++)
         if (g_pipe->done[s] == e) return s;
     return -1;
 }
@@ -105,6 +106,16 @@ hipError_t hipEventRecord(hipEvent_t e, hipStream_t st)
 hipError_t hipEventSynchronize(hipEvent_t e)
 {
     g_log.push_back({EV_SYNC, slot_of_event(e), 0});
+    return hipSuccess;
+}
+hipError_t hipStreamWaitEvent(hipStream_t st, hipEvent_t, unsigned int)
+{
+    g_log.push_back({STREAM_WAIT, -1, (size_t)st});
+    return hipSuccess;
+}
+hipError_t hipStreamIsCapturing(hipStream_t, hipStreamCaptureStatus *status)
+{
+    *status = g_capturing ? hipStreamCaptureStatusActive : hipStreamCaptureStatusNone;
     return hipSuccess;
 }
 hipError_t hipStreamSynchronize(hipStream_t st)
@@ -461,6 +472,72 @@ static int devbuf_cases()
     return 0;
 }
 
+// DevWorkspace: what acquire / release / wait / destroy promise, read off the log (no pipe: hipMalloc / hipFree are logged)
+static int workspace_cases()
+{
+    const hipStream_t s1 = (hipStream_t)0x10, s2 = (hipStream_t)0x20;
+    const int allocs0 = g_live_allocs, events0 = g_live_events;
+    DevWorkspace w;
+    g_log.clear();
+    // the host wait with no user yet is a no-op
+    CHECK(w.wait() == MI355_OK && g_log.empty() && w.get() == nullptr && w.bytes() == 0);
+    // first acquire: no wait of either kind, the allocation alone; release records on the caller's stream and remembers it
+    CHECK(w.acquire(100, s1) == MI355_OK && w.get() != nullptr && w.bytes() == 100);
+    CHECK(g_log.size() == 1 && g_log[0].kind == DEV_MALLOC && g_log[0].arg == 100 && g_live_events == events0 + 1);
+    memset(w.get(), 1, 100);
+    CHECK(w.release(s1) == MI355_OK && g_log.size() == 2 && g_log[1].kind == EV_RECORD && (hipStream_t)g_log[1].arg == s1 && w.last_stream() == s1);
+    // the same stream again: no wait
+    g_log.clear();
+    CHECK(w.acquire(100, s1) == MI355_OK && g_log.empty() && w.release(s1) == MI355_OK);
+    // another stream: one stream-wait on the event, of that stream, before anything else
+    g_log.clear();
+    CHECK(w.acquire(50, s2) == MI355_OK && g_log.size() == 1 && g_log[0].kind == STREAM_WAIT && (hipStream_t)g_log[0].arg == s2);
+    CHECK(w.release(s2) == MI355_OK && w.last_stream() == s2 && w.bytes() == 100);
+    // grow while used: the host waits for the event before the old block is freed and the new one allocated
+    g_log.clear();
+    CHECK(w.acquire(200, s1) == MI355_OK && g_log.size() == 4 && log_is({STREAM_WAIT, EV_SYNC, DEV_FREE, DEV_MALLOC}, 0) && w.bytes() == 200);
+    memset(w.get(), 2, 200);
+    CHECK(w.release(s1) == MI355_OK);
+    g_log.clear();
+    CHECK(w.acquire(201, s1) == MI355_OK && g_log.size() == 3 && log_is({EV_SYNC, DEV_FREE, DEV_MALLOC}, 0) && w.release(s1) == MI355_OK);
+    // the host wait for the last user
+    g_log.clear();
+    CHECK(w.wait() == MI355_OK && g_log.size() == 1 && g_log[0].kind == EV_SYNC);
+    // release under capture: no event record, and the remembered stream stays
+    g_capturing = true;
+    g_log.clear();
+    CHECK(w.acquire(10, s2) == MI355_OK && w.release(s2) == MI355_OK);
+    g_capturing = false;
+    CHECK(count(EV_RECORD) == 0 && w.last_stream() == s1 && g_log.size() == 1 && g_log[0].kind == STREAM_WAIT);
+    // a failed hipMalloc leaves the workspace empty, and the next acquire allocates
+    g_malloc_fail_at = g_malloc_calls;
+    g_log.clear();
+    CHECK(w.acquire(1000, s1) == MI355_ERR_HIP && w.get() == nullptr && w.bytes() == 0 && g_live_allocs == allocs0);
+    CHECK(log_is({EV_SYNC, DEV_FREE, FAIL}, 0) && g_err.find("hipMalloc") != std::string::npos);
+    g_malloc_fail_at = -1;
+    g_log.clear();
+    CHECK(w.acquire(30, s1) == MI355_OK && w.get() != nullptr && w.bytes() == 30 && count(DEV_MALLOC) == 1 && count(DEV_FREE) == 0);
+    memset(w.get(), 3, 30);
+    CHECK(w.release(s1) == MI355_OK);
+    // grow while never used: no wait
+    {
+        DevWorkspace v;
+        g_log.clear();
+        CHECK(v.acquire(10, s1) == MI355_OK && v.acquire(20, s2) == MI355_OK && v.bytes() == 20);
+        CHECK(g_log.size() == 3 && log_is({DEV_MALLOC, DEV_FREE, DEV_MALLOC}, 0));
+        v.destroy();
+    }
+    // after destroy the allocation and the event are gone; twice is harmless, and the object starts over
+    w.destroy();
+    CHECK(w.get() == nullptr && w.bytes() == 0 && g_live_allocs == allocs0 && g_live_events == events0);
+    w.destroy();
+    g_log.clear();
+    CHECK(w.acquire(5, s2) == MI355_OK && g_log.size() == 1 && g_log[0].kind == DEV_MALLOC && w.release(s2) == MI355_OK);
+    w.destroy();
+    CHECK(g_live_allocs == allocs0 && g_live_events == events0);
+    return 0;
+}
+
 int main()
 {
     mi355_ctx ctx;
@@ -569,7 +646,8 @@ int main()
 
     CHECK(pageable_cases(&ctx) == 0);
     CHECK(devbuf_cases() == 0);
-    CHECK(g_live_allocs == 0);
+    CHECK(workspace_cases() == 0);
+    CHECK(g_live_allocs == 0 && g_live_events == 0);
     printf("hostpipe host ok\n");
     return 0;
 }

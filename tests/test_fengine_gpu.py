@@ -466,3 +466,38 @@ def test_cli_row(gpu):
     assert abs(got - base) <= slack, (got, base, slack, r.stdout)
     rows = [l for l in r.stdout.splitlines() if l.startswith("clFEngine (")]
     assert len(rows) == 2 and all(l.rstrip().endswith("ok") for l in rows), r.stdout
+
+
+def test_generic_route_one_handle_two_streams(gpu, pkg):
+    """the generic route's workspace handed between two streams: 6 calls per stream in turn with nothing waited for in between, the
+    first of 1 frame and the others of 3, so the workspace grows after it has been used.  Every output (filled with -128 first) is byte
+    for byte what a second handle gives for the same frames on one stream."""
+    import torch
+    S, npol, F, P, T = RANDOM[0]  # the smallest shape that runs the generic route above
+    xs, h, g, _ = _case(S, npol, F, P, T)
+    blk, single = (pkg.clFEngine(*GPU_ARGS, npol, S, F, h, P, F % 2 == 0, g) for _ in range(2))
+    for b in (blk, single):
+        b.set_generic(True)
+        assert b.route().startswith("generic F=%d P=%d" % (F, P)), b.route()
+    # stream s works on frames 3 s .. 3 s + 2
+    d_xs = [[torch.tensor(x[3 * s * F:], device="cuda") for x in xs] for s in range(2)]
+    out = lambda n: torch.full((n * blk.frame_bytes(),), -128, dtype=torch.int8, device="cuda")  # noqa: E731
+    refs = {}
+    for s in range(2):
+        for n in (1, 3):
+            refs[s, n] = out(n)
+            assert single.work_device(n, [d[:blk.items_per_input(n)] for d in d_xs[s]], [refs[s, n]]) == n
+            torch.cuda.synchronize()
+            assert not (refs[s, n] == -128).any()
+    count = lambda k, s: 1 if (k, s) == (0, 0) else 3  # noqa: E731
+    streams = [torch.cuda.Stream() for _ in range(2)]
+    ys = [[out(count(k, s)) for k in range(6)] for s in range(2)]
+    torch.cuda.synchronize()
+    for k in range(6):
+        for s in range(2):
+            with torch.cuda.stream(streams[s]):
+                blk.work_device(count(k, s), [d[:blk.items_per_input(count(k, s))] for d in d_xs[s]], [ys[s][k]])
+    torch.cuda.synchronize()
+    for s in range(2):
+        for k in range(6):
+            assert torch.equal(ys[s][k], refs[s, count(k, s)]), (s, k)

@@ -191,3 +191,53 @@ def test_two_handles_two_streams(gpu):
                     blks[s].work_device(frames, [x], [ys[s][k]])
         torch.cuda.synchronize()
     assert all(_same(y, refs[s]) for s in range(2) for y in ys[s])
+
+
+# ---- one handle's workspace on two streams ---------------------------------------------------------------------------------------
+# length, create-time switch, what mi355_fft_plan_text says of the length, the start of last_route()
+WORKSPACE_ROUTES = [
+    (65536, None, "two tile passes 256 x 256", "k_fft_tile 256x256"),
+    (131072, "MI355_FFT_NO_TILE", "two tile passes 256 x 512", "k_fft_sub+combine2 S=16x2"),  # three passes: both workspace halves
+    (20000, None, "mixed radix, two passes", "k_fft_mr_tile"),
+    (8209, None, "chirp-z, m = 32768", "bluestein m=32768"),                                   # the unfused five-launch path
+]
+
+
+def _plan_text(gpu, n):
+    import ctypes
+    b = ctypes.create_string_buffer(200)
+    assert gpu.lib().mi355_fft_plan_text(n, b, 200) == 0
+    return b.value.decode()
+
+
+@pytest.mark.parametrize("n,switch,plan,route", WORKSPACE_ROUTES)
+def test_one_handle_two_streams_workspace(gpu, monkeypatch, n, switch, plan, route):
+    """the routes that go through the handle's workspace: 6 calls per stream on two streams in turn with nothing waited for in
+    between, the first of 1 frame and the others of 3, so the workspace grows after it has been used and is handed from stream to
+    stream 11 times.  Every NaN-filled output is bit for bit what a second handle gives for the same input on one stream."""
+    if switch:
+        monkeypatch.setenv(switch, "1")  # read at create
+    assert _plan_text(gpu, n).startswith(plan)  # (the default plan: plan_text honours no switch)
+    blk, single = _blk(gpu, n), _blk(gpu, n)
+    xs = [_input(n, 3, False, 700 + n % 97 + i) for i in range(2)]
+    frames = lambda k, s: 1 if (k, s) == (0, 0) else 3  # noqa: E731
+    refs = {}
+    for s in range(2):
+        for f in (1, 3):
+            refs[s, f] = _nan_out(n, f)
+            single.work_device(f, [xs[s][:f * n]], [refs[s, f]])
+            torch.cuda.synchronize()
+    assert single.last_route().startswith(route), single.last_route()
+    streams = [torch.cuda.Stream() for _ in range(2)]
+    ys = [[_nan_out(n, frames(k, s)) for k in range(6)] for s in range(2)]
+    torch.cuda.synchronize()
+    for k in range(6):
+        for s in range(2):
+            with torch.cuda.stream(streams[s]):
+                blk.work_device(frames(k, s), [xs[s][:frames(k, s) * n]], [ys[s][k]])
+    torch.cuda.synchronize()
+    assert blk.last_route().startswith(route), blk.last_route()
+    for s in range(2):
+        for k in range(6):
+            assert torch.isfinite(ys[s][k]).all(), (s, k)
+            assert _same(ys[s][k], refs[s, frames(k, s)]), (s, k)

@@ -10,7 +10,11 @@ The same program then drives mi355_pageable_run, the piece loop of the seven blo
 their device scratch: 1 .. 5 pieces with a ragged last one over two inputs (one with a history overlap) and two outputs on
 exact-size buffers, the order H2D.. LAUNCH D2H.. STREAM_SYNC per piece, the clamp of the piece size, the wait behind a failed
 launch, a failed copy (every one of a call's sixteen) and a failed wait, with nothing logged after it and no output byte of a later
-piece touched; and DevBuf's keep / free-then-allocate / failed-allocation / release behaviour against the live-allocation count."""
+piece touched; and DevBuf's keep / free-then-allocate / failed-allocation / release behaviour against the live-allocation count.
+
+Last comes DevWorkspace, the stream-ordered workspace of clFFT, clPowerSpectrum and clFEngine: no wait at the first acquire or on
+the same stream, one stream-wait on the event for another stream, the host's event wait before free and malloc when a used buffer
+grows (none for an unused one), a failed allocation that leaves it empty, no event record under capture, and destroy."""
 import os
 import subprocess
 

@@ -407,3 +407,46 @@ def test_two_threads_one_handle_each(gpu):
         assert all(np.array_equal(r.view(np.uint32), res[i][0].view(np.uint32)) for r in res[i])
     for b in blks:
         b.stop()
+
+
+@pytest.mark.parametrize("generic", [False, True], ids=["fused", "generic"])
+def test_one_handle_two_streams(gpu, generic):
+    """the handle's workspace (fused: the partial sums of K = 2C + 3 > C frames; generic: gathered and transformed frames, H != N)
+    handed between two streams: 6 calls per stream in turn with nothing waited for in between, the first of 1 spectrum and the others
+    of 3, so the workspace grows after it has been used.  Every NaN-filled output is bit for bit what a second handle gives for the
+    same input on one stream."""
+    import torch
+    N = 256
+    probe = gpu.clPowerSpectrum(*GPU_ARGS, N, 1)
+    C = chunk_of(probe.route())
+    probe.stop()
+    K, H = 2 * C + 3, N // 2 if generic else N
+    w = ref.hann(N)
+    blk, single = (gpu.clPowerSpectrum(*GPU_ARGS, N, K, w, H, True) for _ in range(2))
+    for b in (blk, single):
+        b.set_generic(generic)
+        assert b.route() == ("generic N=%d batch=%d" % (N, (1 << 20) // N) if generic else "fused pow2 N=%d chunk=%d" % (N, C))
+    d_xs = [torch.from_numpy(ref.make_input(ref.plan(N, K, H, 3)[0], seed=40 + s)).cuda() for s in range(2)]
+    items = {S: ref.plan(N, K, H, S)[0] for S in (1, 3)}
+    nan_out = lambda S: torch.full((S * N,), float("nan"), dtype=torch.float32, device="cuda")  # noqa: E731
+    refs = {}
+    for s in range(2):
+        for S in (1, 3):
+            refs[s, S] = nan_out(S)
+            assert single.work_device(S, [d_xs[s][:items[S]]], [refs[s, S]]) == S * N
+            torch.cuda.synchronize()
+            assert torch.isfinite(refs[s, S]).all()
+    count = lambda k, s: 1 if (k, s) == (0, 0) else 3  # noqa: E731
+    streams = [torch.cuda.Stream() for _ in range(2)]
+    ys = [[nan_out(count(k, s)) for k in range(6)] for s in range(2)]
+    torch.cuda.synchronize()
+    for k in range(6):
+        for s in range(2):
+            with torch.cuda.stream(streams[s]):
+                blk.work_device(count(k, s), [d_xs[s][:items[count(k, s)]]], [ys[s][k]])
+    torch.cuda.synchronize()
+    for s in range(2):
+        for k in range(6):
+            assert torch.equal(ys[s][k].view(torch.int32), refs[s, count(k, s)].view(torch.int32)), (s, k)
+    for b in (blk, single):
+        b.stop()
