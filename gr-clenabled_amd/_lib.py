@@ -274,6 +274,19 @@ def lib():
         "mi355_psearch_work": (i, [vp, ll, vp, ll, vp, vp, ll, vp]),
         "mi355_psearch_work_dev": (i, [vp, ll, vp, ll, vp, vp, ll, vp, vp]),
         "mi355_psearch_measure": (i, [vp, ll, vp, ll, i, vp, vp]),
+        "mi355_fbclean_plan": (i, [i, i, i, llp, llp, llp]),
+        "mi355_fbclean_create": (i, [vp, i, i, i, d, d, d, d, i, vp, pp]),
+        "mi355_fbclean_destroy": (i, [vp]),
+        "mi355_fbclean_set_limits": (i, [vp, d, d, d, d, i]),
+        "mi355_fbclean_get_limits": (i, [vp, dp, dp, dp, dp, C.POINTER(i)]),
+        "mi355_fbclean_set_mask": (i, [vp, vp]),
+        "mi355_fbclean_get_mask": (i, [vp, vp, ll]),
+        "mi355_fbclean_block_len": (ll, [vp]),
+        "mi355_fbclean_set_generic": (i, [vp, i]),
+        "mi355_fbclean_route": (C.c_char_p, [vp]),
+        "mi355_fbclean_work": (i, [vp, ll, vp, vp, vp, vp, vp]),
+        "mi355_fbclean_work_dev": (i, [vp, ll, vp, vp, vp, vp, vp, vp]),
+        "mi355_fbclean_sk_estimate": (i, [vp, i, ll, d, dp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)  # AttributeError here = header/library mismatch: fail loudly

@@ -1793,3 +1793,125 @@ class clPulseSearch(_Block):
             counts = self._counts.detach().cpu().numpy().reshape(-1).view(np.uint8).view(np.uint32)
             cands = np.ascontiguousarray(self._cands.detach().cpu().numpy()).reshape(-1).view(np.uint8).view(PSEARCH_CAND)
         return cands[:int(counts[1])].copy(), int(counts[0])
+
+
+def sk_estimate(x, nd, stride=1):
+    """the spectral-kurtosis estimator of clFilterbankCleaner (mi355_fbclean_sk_estimate, host only) on one column of float32 samples
+    x[0], x[stride], ...: block_len = the number of samples of the column, a multiple of 16 in 16 .. 4096"""
+    a = _host(x, np.float32).reshape(-1)
+    stride = int(stride)
+    if stride < 1:
+        raise ValueError("stride must be >= 1")
+    sk = C.c_double()
+    check(lib().mi355_fbclean_sk_estimate(_hp(a), (a.size + stride - 1) // stride, stride, float(nd), C.byref(sk)), "mi355_fbclean_sk_estimate")
+    return sk.value
+
+
+class clFilterbankCleaner(_Block):
+    """Exact RFI excision between clBeamformer's POWER output and clDedisperser (beyond the reference module; the contract is in
+    include/mi355_clenabled.h): per (block of block_len samples, row, channel) float64 mean, variance and spectral kurtosis in a pinned
+    order, a channel flag (mask, var > 0, sk_lo <= sk <= sk_hi), y = (x - m32) is32 for the good channels and +0 for the flagged ones,
+    and with zero_dm the mean over the good channels removed per time sample, time samples with zs^2 > td^2 ng zeroed.  x[t][r][f]
+    float32 in, the same layout out; the flags and {m32, is32} are optional outputs.  Bit-exact on either route, for any split into
+    calls at block boundaries and any alignment; in place when input and output are the same buffer."""
+    _destroy = "mi355_fbclean_destroy"
+
+    def __init__(self, openCLPlatformType, devSelector, platformId, devId, num_rows, num_channels, block_len, nd=1.0, sk_lo=-np.inf,
+                 sk_hi=np.inf, td=np.inf, zero_dm=0, mask=None, setDebug=0):
+        self.num_rows, self.num_channels, self.block_len = int(num_rows), int(num_channels), int(block_len)
+        L = lib()
+        fs, cb, tb = C.c_longlong(), C.c_longlong(), C.c_longlong()
+        # argument errors before a context exists
+        check(L.mi355_fbclean_plan(self.num_rows, self.num_channels, self.block_len, C.byref(fs), C.byref(cb), C.byref(tb)), "mi355_fbclean_plan")
+        self._floats = fs.value
+        m = None if mask is None else self._mask(mask)
+        super().__init__(openCLPlatformType, devSelector, platformId, devId, setDebug)
+        check(self._L.mi355_fbclean_create(self._ctx, self.num_rows, self.num_channels, self.block_len, float(nd), float(sk_lo), float(sk_hi),
+                                           float(td), int(zero_dm), None if m is None else _hp(m), C.byref(self._h)), "mi355_fbclean_create")
+
+    def _mask(self, mask):
+        a = np.ascontiguousarray(mask)
+        if a.dtype != np.uint8:
+            raise TypeError("mask is uint8")
+        if a.size != self.num_channels:
+            raise ValueError("mask holds %d entries, the geometry has %d channels" % (a.size, self.num_channels))
+        return a
+
+    def floats_per_sample(self):
+        return self._floats
+
+    def route(self):
+        return self._L.mi355_fbclean_route(self._h).decode()
+
+    def set_generic(self, on):
+        check(self._L.mi355_fbclean_set_generic(self._h, 1 if on else 0), "mi355_fbclean_set_generic")
+
+    def set_limits(self, nd, sk_lo, sk_hi, td, zero_dm):
+        check(self._L.mi355_fbclean_set_limits(self._h, float(nd), float(sk_lo), float(sk_hi), float(td), int(zero_dm)), "mi355_fbclean_set_limits")
+
+    def limits(self):
+        """(nd, sk_lo, sk_hi, td, zero_dm)"""
+        v = [C.c_double() for _ in range(4)]
+        z = C.c_int()
+        check(self._L.mi355_fbclean_get_limits(self._h, *[C.byref(a) for a in v], C.byref(z)), "mi355_fbclean_get_limits")
+        return tuple(a.value for a in v) + (z.value,)
+
+    def set_mask(self, mask):
+        check(self._L.mi355_fbclean_set_mask(self._h, _hp(self._mask(mask))), "mi355_fbclean_set_mask")
+
+    def mask(self):
+        out = np.empty(self.num_channels, np.uint8)
+        check(self._L.mi355_fbclean_get_mask(self._h, _hp(out), out.size), "mi355_fbclean_get_mask")
+        return out
+
+    sk_estimate = staticmethod(sk_estimate)
+
+    def work(self, noutput_items, input_items, output_items):
+        """host buffers: noutput_items time samples, a multiple of block_len.  input_items[0] float32 [n][R][F]; output_items[0] the
+        same (it may be the input array: in place); output_items[1:4], each optional or None: cflags uint8 [n / block_len][R][F],
+        tflags uint8 [n][R], stats float32 [n / block_len][R][F][2]"""
+        n = int(noutput_items)
+        if n == 0:
+            return 0
+        nb = n // self.block_len
+        x = _host(input_items[0], np.float32)
+        _need("input", x, n * self._floats)
+        y = _host(output_items[0], np.float32, writable=True)
+        _need("output", y, n * self._floats)
+        opt = [None, None, None]
+        for k, (dtype, items) in enumerate(((np.uint8, nb * self._floats), (np.uint8, n * self.num_rows), (np.float32, 2 * nb * self._floats))):
+            if len(output_items) > k + 1 and output_items[k + 1] is not None:
+                opt[k] = _host(output_items[k + 1], dtype, writable=True)
+                _need("output %d" % (k + 1), opt[k], items)
+        check(self._L.mi355_fbclean_work(self._h, n, _hp(x), _hp(y), *[None if a is None else _hp(a) for a in opt]), "mi355_fbclean_work")
+        return n
+
+    def work_device(self, noutput_items, input_items, output_items):
+        """CUDA tensors, enqueue only on torch's current stream; the same buffers as work()"""
+        n = int(noutput_items)
+        if n == 0:
+            return 0
+        nb = n // self.block_len
+        opt = [None, None, None]
+        for k, nbytes in enumerate((nb * self._floats, n * self.num_rows, 8 * nb * self._floats)):
+            if len(output_items) > k + 1 and output_items[k + 1] is not None:
+                opt[k] = _dp(output_items[k + 1], nbytes, "output %d" % (k + 1))
+        check(self._L.mi355_fbclean_work_dev(self._h, n, _dp(input_items[0], n * self._floats * 4, "input"),
+                                             _dp(output_items[0], n * self._floats * 4, "output"), *opt, _torch_stream(self.device)),
+              "mi355_fbclean_work_dev")
+        return n
+
+    def clean(self, x, flags=False):
+        """work() on a numpy input [n][R][F]: the cleaned filterbank, or with flags (out, cflags, tflags, stats)"""
+        x = _host(x, np.float32)
+        n = x.size // self._floats
+        nb = n // self.block_len
+        y = np.empty((n, self.num_rows, self.num_channels), np.float32)
+        if not flags:
+            self.work(n, [x], [y])
+            return y
+        cf = np.empty((nb, self.num_rows, self.num_channels), np.uint8)
+        tf = np.empty((n, self.num_rows), np.uint8)
+        st = np.empty((nb, self.num_rows, self.num_channels, 2), np.float32)
+        self.work(n, [x], [y, cf, tf, st])
+        return y, cf, tf, st

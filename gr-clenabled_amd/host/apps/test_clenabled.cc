@@ -1025,11 +1025,75 @@ static int psearch_test(size_t n)
     return g_fail ? 1 : 0;
 }
 
+// --fbclean-only: clFilterbankCleaner at (R, F, Tb) = (2, 256, 32), 3 blocks, zero-DM on, on samples from the 32-bit linear
+// congruential generator of --beamform-only (the top byte of each state plus 1 as float: 1 .. 256, a power-like positive series) with
+// channel 7 masked.  Prints a "checksum" line that tests/test_fbclean_gpu.py compares with the numpy reference: sum_i (i % 7 + 1)
+// (bits of out_i) + sum_j (j % 5 + 1) tflag_j + sum_k (k % 3 + 1) cflag_k modulo 2^64, the channel flags taken once per block; then one
+// timing row.
+static int fbclean_test(size_t n)
+{
+    const int R = 2, F = 256, Tb = 32, NB = 3, N = NB * Tb;
+    uint32_t state = 12345u;
+    auto next = [&]() { state = state * 1664525u + 1013904223u; return (float)(state >> 24) + 1.0f; };
+    std::vector<float> x((size_t)N * R * F);
+    for (auto &v : x) v = next();
+    std::vector<uint8_t> mask((size_t)F, 0);
+    mask[7] = 1;
+    {
+        auto fc = clFilterbankCleaner::make(OCLTYPE_GPU, OCLDEVICESELECTOR_SPECIFIC, 0, g_dev, R, F, Tb, 1.0, 0.0, 1.0, 4.0, true, mask);
+        bool ok = (int)fc->history() == 1 && fc->output_multiple() == Tb && fc->block_len() == Tb && fc->route().compare(0, 5, "slab ") == 0 &&
+                  fc->mask() == mask && fc->limits() == std::vector<double>{1.0, 0.0, 1.0, 4.0, 1.0};
+        std::vector<float> y(x.size(), -1e30f);
+        std::vector<uint8_t> tf((size_t)N * R, 0xEE), cf((size_t)N * R * F, 0xEE);
+        gr_vector_const_void_star in = {x.data()};
+        gr_vector_void_star out = {y.data(), tf.data(), cf.data()};
+        auto t0 = std::chrono::steady_clock::now();
+        ok = ok && fc->work(N, in, out) == N;
+        std::chrono::duration<double> dt = std::chrono::steady_clock::now() - t0;
+        unsigned long long sum = 0;
+        for (size_t i = 0; i < y.size(); i++) {
+            uint32_t bits;
+            memcpy(&bits, &y[i], 4);
+            ok = ok && y[i] != -1e30f;
+            sum += (unsigned long long)(i % 7 + 1) * bits;
+        }
+        for (size_t j = 0; j < tf.size(); j++) {
+            ok = ok && tf[j] <= 1;
+            sum += (unsigned long long)(j % 5 + 1) * tf[j];
+        }
+        const size_t cb = (size_t)R * F;
+        for (size_t t = 0; t < (size_t)N; t++)  // every item of a block carries its block's flags
+            ok = ok && memcmp(cf.data() + t * cb, cf.data() + (t / Tb) * Tb * cb, cb) == 0;
+        for (size_t b = 0; b < (size_t)NB; b++)
+            for (size_t k = 0; k < cb; k++) {
+                const uint8_t c = cf[b * Tb * cb + k];
+                ok = ok && c <= 1 && (k % F != 7 || c == 1);
+                sum += (unsigned long long)((b * cb + k) % 3 + 1) * c;
+            }
+        printf("clFilterbankCleaner checksum %llu\n", sum);
+        report("clFilterbankCleaner (2 rows, 256 channels, blocks of 32)", (size_t)N, dt.count(), ok);
+    }
+    {
+        const int Rt = 4, Ft = 1024, Tbt = 256, nb = (int)std::max<size_t>(n / 4096, 2), nt = nb * Tbt;
+        std::vector<float> xt((size_t)nt * Rt * Ft);
+        for (size_t i = 0; i < xt.size(); i++) xt[i] = (i / ((size_t)Rt * Ft)) & 1 ? 3.0f : 1.0f;  // 1, 3, 1, 3 along time: m 2, var 1
+        auto fc = clFilterbankCleaner::make(OCLTYPE_GPU, OCLDEVICESELECTOR_SPECIFIC, 0, g_dev, Rt, Ft, Tbt);
+        std::vector<float> y(xt.size(), 0.0f);
+        gr_vector_const_void_star in = {xt.data()};
+        gr_vector_void_star out = {y.data()};
+        int got = 0;
+        const double t = time_calls([&] { got = fc->work(nt, in, out); });
+        report("clFilterbankCleaner (4 x 1024 channels, blocks of 256, timing)", (size_t)nt, t,
+               got == nt && y[0] == -1.0f && y[(size_t)Rt * Ft] == 1.0f && y.back() == 1.0f);
+    }
+    return g_fail ? 1 : 0;
+}
+
 int main(int argc, char **argv)
 {
     size_t n = 8192;  // the reference's default block size
     int fft_size = 4096, ntaps = 65;
-    bool only_fft = false, only_xcorrelate = false, xc_complex = false, only_loops = false, only_resampler = false, only_synth = false, only_pspec = false, only_xlate = false, only_beamform = false, only_fengine = false, only_dedisp = false, only_psearch = false;
+    bool only_fft = false, only_xcorrelate = false, xc_complex = false, only_loops = false, only_resampler = false, only_synth = false, only_pspec = false, only_xlate = false, only_beamform = false, only_fengine = false, only_dedisp = false, only_psearch = false, only_fbclean = false;
     int xc_inputs = 2, xc_maxsearch = 512;
     for (int i = 1; i < argc; i++) {
         if (!strncmp(argv[i], "--device=", 9)) g_dev = atoi(argv[i] + 9);
@@ -1048,6 +1112,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--fengine-only")) only_fengine = true;
         else if (!strcmp(argv[i], "--dedisp-only")) only_dedisp = true;
         else if (!strcmp(argv[i], "--psearch-only")) only_psearch = true;
+        else if (!strcmp(argv[i], "--fbclean-only")) only_fbclean = true;
         else if (!strncmp(argv[i], "--num_inputs=", 13)) xc_inputs = atoi(argv[i] + 13);
         else if (!strncmp(argv[i], "--maxsearch=", 12)) xc_maxsearch = atoi(argv[i] + 12);
         else if (!strcmp(argv[i], "--input_complex")) xc_complex = true;
@@ -1074,8 +1139,9 @@ int main(int argc, char **argv)
                    "       %s --beamform-only [--iterations N] [block size]\n"
                    "       %s --fengine-only [--iterations N] [block size]\n"
                    "       %s --dedisp-only [--iterations N] [block size]\n"
-                   "       %s --psearch-only [--iterations N] [block size]\n",
-                   argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
+                   "       %s --psearch-only [--iterations N] [block size]\n"
+                   "       %s --fbclean-only [--iterations N] [block size]\n",
+                   argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
             return 0;
         } else n = strtoull(argv[i], nullptr, 10);
     }
@@ -1113,6 +1179,10 @@ int main(int argc, char **argv)
     }
     if (only_psearch) {
         try { return psearch_test(n); }
+        catch (const std::exception &e) { std::cerr << "error: " << e.what() << std::endl; return 2; }
+    }
+    if (only_fbclean) {
+        try { return fbclean_test(n); }
         catch (const std::exception &e) { std::cerr << "error: " << e.what() << std::endl; return 2; }
     }
     if (only_xcorrelate) {

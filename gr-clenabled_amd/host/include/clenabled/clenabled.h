@@ -23,6 +23,8 @@
 #include "clQuadratureDemod.h"
 #include "clxcorrelate_fft_vcf.h"
 
+#include <limits>
+
 namespace gr {
 namespace clenabled {
 
@@ -243,6 +245,31 @@ public:
     virtual std::vector<float> mean() const = 0;
     virtual std::vector<float> inv_sigma() const = 0;
     virtual int lookahead() const = 0;      // 2^(num_widths - 1) - 1
+    virtual void set_generic(bool on) = 0;  // the generic route for every later call
+    virtual std::string route() const = 0;
+};
+
+// gr::clenabled::clFilterbankCleaner -- exact RFI excision between clBeamformer's POWER output and clDedisperser: per (block of block_len
+// samples, row, channel) float64 statistics in a pinned order, a channel flag (static mask, variance > 0, sk_lo <= spectral kurtosis <=
+// sk_hi), normalisation to zero mean and unit variance, and with zero_dm the mean over the good channels removed per time sample, time
+// samples whose sum exceeds td sigma zeroed.  Beyond the reference module; the contract is in mi355_clenabled.h.  A sync_block with
+// output multiple block_len and no history: one input stream whose item is a time sample of num_rows num_channels floats ([row][chan],
+// the item clBeamformer writes in POWER mode), output 0 the same item cleaned (the item clDedisperser reads); the optional output 1
+// carries num_rows time-sample flag bytes per item, the optional output 2 the num_rows num_channels channel-flag bytes of the block
+// the item lies in (repeated for every item of the block).  mask: num_channels bytes, nonzero = always flagged; empty = none.
+// (No per-block header of this name is installed by this build yet.)
+class CLENABLED_API clFilterbankCleaner : virtual public gr::sync_block {
+public:
+    typedef std::shared_ptr<clFilterbankCleaner> sptr;
+    static sptr make(int openCLPlatformType, int devSelector, int platformId, int devId, int num_rows, int num_channels, int block_len,
+                     double nd = 1.0, double sk_lo = -std::numeric_limits<double>::infinity(), double sk_hi = std::numeric_limits<double>::infinity(),
+                     double td = std::numeric_limits<double>::infinity(), bool zero_dm = false,
+                     const std::vector<uint8_t> &mask = std::vector<uint8_t>(), int setDebug = 0);
+    virtual void set_limits(double nd, double sk_lo, double sk_hi, double td, bool zero_dm) = 0;  // for the calls after it returns
+    virtual std::vector<double> limits() const = 0;                                               // {nd, sk_lo, sk_hi, td, zero_dm}
+    virtual void set_mask(const std::vector<uint8_t> &mask) = 0;                                  // num_channels entries, anything else throws
+    virtual std::vector<uint8_t> mask() const = 0;
+    virtual int block_len() const = 0;
     virtual void set_generic(bool on) = 0;  // the generic route for every later call
     virtual std::string route() const = 0;
 };

@@ -510,4 +510,33 @@ PYBIND11_MODULE(clenabled_python, m)
         .def("decimation", [](clPulseSearch &b) { return b.decimation(); })
         .def("history", [](clPulseSearch &b) { return b.history(); })
         .def("work", &call_work<clPulseSearch>, py::arg("noutput_items"), py::arg("input_items"), py::arg("output_items"));
+
+    // filterbank cleaner (lib/clFilterbankCleaner_impl.cc): items are time samples of R F floats in and out, noutput_items a multiple of
+    // block_len; output_items[1] (R bytes per item) and output_items[2] (R F bytes per item) are the optional flag streams
+    using u8array = py::array_t<uint8_t, py::array::c_style | py::array::forcecast>;
+    py::class_<clFilterbankCleaner SYNC_BASES, std::shared_ptr<clFilterbankCleaner>>(m, "clFilterbankCleaner")
+        .def(py::init([](int openCLPlatformType, int devSelector, int platformId, int devId, int num_rows, int num_channels, int block_len, double nd,
+                         double sk_lo, double sk_hi, double td, bool zero_dm, const u8array &mask, int setDebug) {
+                 return clFilterbankCleaner::make(openCLPlatformType, devSelector, platformId, devId, num_rows, num_channels, block_len, nd, sk_lo,
+                                                  sk_hi, td, zero_dm, std::vector<uint8_t>(mask.data(), mask.data() + mask.size()), setDebug);
+             }),
+             py::arg("openCLPlatformType"), py::arg("devSelector"), py::arg("platformId"), py::arg("devId"), py::arg("num_rows"),
+             py::arg("num_channels"), py::arg("block_len"), py::arg("nd") = 1.0, py::arg("sk_lo") = -std::numeric_limits<double>::infinity(),
+             py::arg("sk_hi") = std::numeric_limits<double>::infinity(), py::arg("td") = std::numeric_limits<double>::infinity(),
+             py::arg("zero_dm") = false, py::arg("mask") = u8array(0), py::arg("setDebug") = 0)
+        .def("set_limits", &clFilterbankCleaner::set_limits, py::arg("nd"), py::arg("sk_lo"), py::arg("sk_hi"), py::arg("td"), py::arg("zero_dm"))
+        .def("limits", &clFilterbankCleaner::limits)
+        .def("set_mask", [](clFilterbankCleaner &b, const u8array &t) { b.set_mask(std::vector<uint8_t>(t.data(), t.data() + t.size())); },
+             py::arg("mask"))
+        .def("mask",
+             [](clFilterbankCleaner &b) {
+                 const std::vector<uint8_t> t = b.mask();
+                 return u8array(t.size(), t.data());
+             })
+        .def("block_len", &clFilterbankCleaner::block_len)
+        .def("set_generic", &clFilterbankCleaner::set_generic, py::arg("on"))
+        .def("route", &clFilterbankCleaner::route)
+        .def("output_multiple", [](clFilterbankCleaner &b) { return b.output_multiple(); })
+        .def("history", [](clFilterbankCleaner &b) { return b.history(); })
+        .def("work", &call_work<clFilterbankCleaner>, py::arg("noutput_items"), py::arg("input_items"), py::arg("output_items"));
 }

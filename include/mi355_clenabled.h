@@ -1007,6 +1007,95 @@ int mi355_psearch_work_dev(mi355_psearch *h, long long n, const void *in, long l
                            void *counts, void *stream);
 int mi355_psearch_measure(mi355_psearch *h, long long n, const void *in, long long in_pitch, int in_is_device, float *mean, float *inv_sigma);
 
+/* ------------------------------------------------------------------------------------------------
+ * Filterbank cleaner: clFilterbankCleaner, exact RFI excision between clBeamformer's POWER output and clDedisperser: per-channel
+ * normalisation over short blocks, a spectral-kurtosis channel flagger with a static channel mask, and the zero-DM filter with a
+ * broadband time-sample flag.  Beyond the reference module, which has nothing of the kind (this comment is the contract).  The
+ * arithmetic is pinned, so there is no tolerance anywhere.
+ *     R = num_rows (beams) 1 .. 4096;  F = num_channels 1 .. 16384;  Tb = block_len, a multiple of 16 in 16 .. 4096, fixed per handle;
+ *     M = (double)Tb;  L = Tb / 16.
+ * Input: x[t][r][f] float32, channel fastest.  A call cleans n time samples, n a multiple of Tb; n == 0 is a no-op.  Blocks are
+ * independent and the handle keeps no stream state: any split of a stream into calls at block boundaries gives identical bits.
+ * Parameters, by value, changeable by _set_limits / _set_mask:
+ *     nd      double > 0, finite: the raw power samples summed into one input sample times the shape factor (Ti npol for
+ *             clBeamformer POWER with stokes_i)
+ *     sk_lo <= sk_hi   doubles; -Inf / +Inf disable that side.  NaN is refused.
+ *     td      double >= 0; +Inf disables the time-sample flag.  td2 = td td, rounded once on the host.  NaN is refused.
+ *     zero_dm 0 or 1
+ *     mask[f] uint8, nonzero: channel f is always flagged.  NULL at _create: all zero.
+ * Step 1, statistics per (block b, r, f), IEEE binary64, x converted to double:
+ *     segment s = 0 .. 15 holds the samples t = b Tb + s L .. + L - 1;
+ *     a1_s = ((+0.0 + x_0) + x_1) + ...      a2_s = ((+0.0 + x_0 x_0) + x_1 x_1) + ...      in ascending t
+ *     (x x is exact in double, so a fused multiply-add there gives the same bits);
+ *     s1, s2 = the adjacent-pair binary tree over the 16 segment sums: (((a_0 + a_1) + (a_2 + a_3)) + ((a_4 + a_5) + (a_6 + a_7))) +
+ *     (the same over a_8 .. a_15).  (A plain sequential sum gives other bits and does not conform.)
+ * Step 2, the flag, every operation rounded on its own and never contracted:
+ *     m = s1 / M;     var = s2 / M - m m;     sk = ((M nd + 1) / (M - 1)) ((M s2) / (s1 s1) - 1)
+ *     (the generalised spectral-kurtosis estimator of Nita & Gary, 1 for clean noise);
+ *     good = mask[f] == 0 && var > 0 && sk >= sk_lo && sk <= sk_hi        any NaN makes a comparison false
+ *     m32 = (float)m;     is32 = (float)(1.0 / sqrt(var)), the square root IEEE correctly rounded.
+ * A NaN or +-Inf anywhere in the column, or a constant column, therefore flags that (block, r, f) and reaches nothing else.
+ * Step 3, normalise, binary32, two roundings: y = (x - m32) is32 for good channels, +0.0f for flagged ones.
+ * Step 4, zero-DM, per (t, r), only when zero_dm is set:
+ *     the binary64 partial p_j, j = 0 .. 63, starts at +0.0 and adds, in ascending f, the y of every channel with floor(f / 4) mod 64
+ *     == j (flagged channels are skipped or added as +0.0: the same bits);  zs = the adjacent-pair tree over p_0 .. p_63;
+ *     ng = the number of good channels of (b, r), as a double;
+ *     tflag = zs zs > td2 ng;     z32 = (float)(zs / ng);
+ *     y' = y - z32 for the good channels of unflagged time samples, +0.0f everywhere else (ng == 0 included).
+ *   With zero_dm == 0: y' = y and every tflag is 0.
+ * Outputs: out[t][r][f] float32 = y', the input's layout, directly clDedisperser's input.  Optional (NULL: not wanted):
+ *     cflags[b][r][f] uint8, 1 = flagged;     tflags[t][r] uint8;
+ *     stats[b][r][f] float32 pairs {m32, is32} wherever var > 0, flagged or not, and {+0.0f, +0.0f} elsewhere (8-byte aligned).
+ * out == in exactly is allowed: a filterbank is cleaned in place.  Any other overlap of two buffers is MI355_ERR_INVALID_ARG.
+ * Invariance: either route, any split at block boundaries, any 4-byte alignment of in / out and any n give identical bits.  There
+ * are no float atomics.  Results with a subnormal float32 intermediate are unspecified, as are the bits of an output that the
+ * formulas make NaN (a good channel with is32 = +Inf).
+ * Routes, fixed at _create by the shape and named by _route():
+ *   "slab R=64 F=1024 Tb=256 fg=256" -- F a multiple of 256 in 256 .. 4096, every Tb: ONE launch, a workgroup of 16 waves owns a
+ *       (block, row) slab of Tb F floats.  Phase A: waves are segments, lanes run along channels with 16-byte loads, the segment sums
+ *       of a group of fg channels meet in LDS in the contract's tree and step 2 runs once per channel.  Phase B: a wave takes a time
+ *       sample, normalises, reduces its float64 partials with a cross-lane butterfly, subtracts and stores.  The slab is read twice
+ *       (the second time from the caches, if they hold it) and written once.  R = 1 with few blocks per call launches few
+ *       workgroups (one per block): accepted for this first form.
+ *   "generic R=3 F=52 Tb=48" -- every other shape and every handle under _set_generic(h, 1): three plain kernels, one thread per
+ *       (b, r, f), one per (t, r), one per output, through a scratch buffer allocated at _create (at least one block's 9 R F + 5 Tb R
+ *       bytes, 16 MiB if that holds more than one); a call is walked in chunks of whole blocks that fit it.
+ * The route is forced by _set_generic only; there is no environment switch.
+ * Mask updates: a call enqueued before _set_mask returns uses the old mask entirely, a later call the new one entirely (versioned
+ * device buffers, released behind the event of their last launch; nothing on the work path waits for the device).  A refused update,
+ * of the mask or the limits, changes nothing.
+ * Errors (nothing launched): NULL in or out, in or out not 4-byte aligned, stats not 8-byte aligned, overlapping buffers other than
+ * out == in, n < 0 or n % Tb != 0, a parameter outside the ranges above: MI355_ERR_INVALID_ARG.  More than 2^40 bytes per buffer
+ * and call: MI355_ERR_UNSUPPORTED.
+ *   _plan         floats_per_sample = R F, cflag_bytes_per_block = R F, tflag_bytes_per_sample = R; no device; any pointer may be NULL
+ *   _create       everything that can be told without a device is checked before ctx is touched
+ *   _set_limits   by value; takes effect for the calls enqueued after it returns.  _get_limits: any pointer may be NULL
+ *   _set_mask     replaces the F entries;  _get_mask copies them (as 0 / 1), cap_entries is the size of `out`
+ *   _block_len    Tb
+ *   _set_generic  on != 0: the generic route for every later call of the handle; 0: back
+ *   _route        valid until the next _set_generic / _destroy of the handle; "" for NULL
+ *   _work         host pointers, blocking: pieces of whole blocks, cleaned in place on the device
+ *   _work_dev     device pointers, enqueue only: allocates nothing and waits for nothing
+ * mi355_fbclean_sk_estimate (host only, no context): steps 1 and 2 on the one column x[0], x[stride], ..., x[(Tb - 1) stride]: *sk
+ * receives the estimator, bit for bit what the device compares with sk_lo / sk_hi, so a caller calibrates limits without a device.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct mi355_fbclean mi355_fbclean;
+int mi355_fbclean_plan(int num_rows, int num_channels, int block_len, long long *floats_per_sample, long long *cflag_bytes_per_block,
+                       long long *tflag_bytes_per_sample);
+int mi355_fbclean_create(mi355_ctx *ctx, int num_rows, int num_channels, int block_len, double nd, double sk_lo, double sk_hi, double td,
+                         int zero_dm, const uint8_t *mask, mi355_fbclean **out);
+int mi355_fbclean_destroy(mi355_fbclean *h);
+int mi355_fbclean_set_limits(mi355_fbclean *h, double nd, double sk_lo, double sk_hi, double td, int zero_dm);
+int mi355_fbclean_get_limits(const mi355_fbclean *h, double *nd, double *sk_lo, double *sk_hi, double *td, int *zero_dm);
+int mi355_fbclean_set_mask(mi355_fbclean *h, const uint8_t *mask);
+int mi355_fbclean_get_mask(const mi355_fbclean *h, uint8_t *out, long long cap_entries);
+long long mi355_fbclean_block_len(const mi355_fbclean *h);
+int mi355_fbclean_set_generic(mi355_fbclean *h, int on);
+const char *mi355_fbclean_route(const mi355_fbclean *h);
+int mi355_fbclean_work(mi355_fbclean *h, long long n, const void *in, void *out, void *cflags, void *tflags, void *stats);
+int mi355_fbclean_work_dev(mi355_fbclean *h, long long n, const void *in, void *out, void *cflags, void *tflags, void *stats, void *stream);
+int mi355_fbclean_sk_estimate(const float *x, int block_len, long long stride, double nd, double *sk);
+
 #ifdef __cplusplus
 }
 #endif
