@@ -287,6 +287,21 @@ def lib():
         "mi355_fbclean_work": (i, [vp, ll, vp, vp, vp, vp, vp]),
         "mi355_fbclean_work_dev": (i, [vp, ll, vp, vp, vp, vp, vp, vp]),
         "mi355_fbclean_sk_estimate": (i, [vp, i, ll, d, dp]),
+        "mi355_fold_plan": (i, [i, i, i, i, llp, llp, llp]),
+        "mi355_fold_create": (i, [vp, i, i, i, i, vp, pp]),
+        "mi355_fold_destroy": (i, [vp]),
+        "mi355_fold_set_models": (i, [vp, vp]),
+        "mi355_fold_get_models": (i, [vp, vp, ll]),
+        "mi355_fold_sample": (i, [vp, C.POINTER(C.c_ulonglong)]),
+        "mi355_fold_set_sample": (i, [vp, C.c_ulonglong]),
+        "mi355_fold_skip": (i, [vp, ll]),
+        "mi355_fold_subint_len": (ll, [vp]),
+        "mi355_fold_set_generic": (i, [vp, i]),
+        "mi355_fold_route": (C.c_char_p, [vp]),
+        "mi355_fold_work": (i, [vp, ll, vp, vp, vp, vp]),
+        "mi355_fold_work_dev": (i, [vp, ll, vp, vp, vp, vp, vp]),
+        "mi355_fold_model": (i, [d, d, d, d, vp]),
+        "mi355_fold_bins": (i, [vp, C.c_ulonglong, ll, i, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)  # AttributeError here = header/library mismatch: fail loudly

@@ -1915,3 +1915,141 @@ class clFilterbankCleaner(_Block):
         st = np.empty((nb, self.num_rows, self.num_channels, 2), np.float32)
         self.work(n, [x], [y, cf, tf, st])
         return y, cf, tf, st
+
+
+def fold_model(period_s, pdot, tsamp_s, phase0_turns=0.0):
+    """the three uint64 words {phi0, nu, nudot} of clFolder's phase model (mi355_fold_model, host only, computed in long double): a
+    pulsar of period `period_s` seconds and period derivative `pdot` sampled every `tsamp_s` seconds, at `phase0_turns` at sample 0"""
+    out = np.empty(3, np.uint64)
+    check(lib().mi355_fold_model(float(period_s), float(pdot), float(tsamp_s), float(phase0_turns), _hp(out)), "mi355_fold_model")
+    return out
+
+
+def fold_bins(model, T0, n, nbin):
+    """bin(T) of T = T0 .. T0 + n - 1 for one model of three uint64 words, bit for bit as clFolder computes it (mi355_fold_bins, host
+    only): int32 [n]"""
+    m = np.ascontiguousarray(model, np.uint64).reshape(-1)
+    if m.size != 3:
+        raise ValueError("a model is three 64-bit words")
+    out = np.empty(max(int(n), 0), np.int32)
+    check(lib().mi355_fold_bins(_hp(m), int(T0) & 0xFFFFFFFFFFFFFFFF, int(n), int(nbin), _hp(out)), "mi355_fold_bins")
+    return out
+
+
+class clFolder(_Block):
+    """Exact pulsar folding behind clBeamformer's POWER output and clFilterbankCleaner (beyond the reference module; the contract is in
+    include/mi355_clenabled.h): x[t][r][f] float32, optionally with the cleaner's tflags[t][r], folded modulo a per-row integer phase
+    model {phi0, nu, nudot} (units of 2^-64 turn) into out[j][r][b][f] per sub-integration of subint_len samples, each sum in ascending
+    time with one binary32 rounding per addition, and optionally hits[j][r][b] uint32.  The handle counts the absolute sample index.
+    Bit-exact on either route, for any split into calls at sub-integration boundaries and any alignment."""
+    _destroy = "mi355_fold_destroy"
+
+    def __init__(self, openCLPlatformType, devSelector, platformId, devId, num_rows, num_channels, nbin, subint_len, models, setDebug=0):
+        self.num_rows, self.num_channels, self.nbin, self.subint_len = int(num_rows), int(num_channels), int(nbin), int(subint_len)
+        L = lib()
+        fs, fo, hs = C.c_longlong(), C.c_longlong(), C.c_longlong()
+        # argument errors before a context exists
+        check(L.mi355_fold_plan(self.num_rows, self.num_channels, self.nbin, self.subint_len, C.byref(fs), C.byref(fo), C.byref(hs)), "mi355_fold_plan")
+        self._floats, self._out_floats, self._hits = fs.value, fo.value, hs.value
+        m = self._models(models)
+        super().__init__(openCLPlatformType, devSelector, platformId, devId, setDebug)
+        check(self._L.mi355_fold_create(self._ctx, self.num_rows, self.num_channels, self.nbin, self.subint_len, _hp(m), C.byref(self._h)),
+              "mi355_fold_create")
+
+    def _models(self, models):
+        a = np.ascontiguousarray(models)
+        if a.dtype != np.uint64:
+            raise TypeError("models are uint64 words (nudot as two's complement)")
+        if a.size != 3 * self.num_rows:
+            raise ValueError("models hold %d words, the geometry has %d rows of 3" % (a.size, self.num_rows))
+        return a
+
+    def floats_per_sample(self):
+        return self._floats
+
+    def floats_per_subint(self):
+        return self._out_floats
+
+    def hits_per_subint(self):
+        return self._hits
+
+    def route(self):
+        return self._L.mi355_fold_route(self._h).decode()
+
+    def set_generic(self, on):
+        check(self._L.mi355_fold_set_generic(self._h, 1 if on else 0), "mi355_fold_set_generic")
+
+    def set_models(self, models):
+        check(self._L.mi355_fold_set_models(self._h, _hp(self._models(models))), "mi355_fold_set_models")
+
+    def models(self):
+        out = np.empty((self.num_rows, 3), np.uint64)
+        check(self._L.mi355_fold_get_models(self._h, _hp(out), out.size), "mi355_fold_get_models")
+        return out
+
+    def sample(self):
+        """the absolute index of the next sample"""
+        t = C.c_ulonglong()
+        check(self._L.mi355_fold_sample(self._h, C.byref(t)), "mi355_fold_sample")
+        return t.value
+
+    def set_sample(self, T):
+        check(self._L.mi355_fold_set_sample(self._h, int(T) & 0xFFFFFFFFFFFFFFFF), "mi355_fold_set_sample")
+
+    def skip(self, n):
+        check(self._L.mi355_fold_skip(self._h, int(n)), "mi355_fold_skip")
+
+    fold_model = staticmethod(fold_model)
+    fold_bins = staticmethod(fold_bins)
+
+    def work(self, noutput_items, input_items, output_items):
+        """host buffers: noutput_items sub-integrations.  input_items[0] float32 [n subint_len][R][F]; input_items[1], optional or None:
+        tflags uint8 [n subint_len][R]; output_items[0] float32 [n][R][nbin][F]; output_items[1], optional or None: hits uint32
+        [n][R][nbin]"""
+        ns = int(noutput_items)
+        if ns == 0:
+            return 0
+        n = ns * self.subint_len
+        x = _host(input_items[0], np.float32)
+        _need("input", x, n * self._floats)
+        tf = None
+        if len(input_items) > 1 and input_items[1] is not None:
+            tf = _host(input_items[1], np.uint8)
+            _need("input 1", tf, n * self.num_rows)
+        y = _host(output_items[0], np.float32, writable=True)
+        _need("output", y, ns * self._out_floats)
+        hits = None
+        if len(output_items) > 1 and output_items[1] is not None:
+            hits = _host(output_items[1], np.uint32, writable=True)
+            _need("output 1", hits, ns * self._hits)
+        check(self._L.mi355_fold_work(self._h, n, _hp(x), None if tf is None else _hp(tf), _hp(y), None if hits is None else _hp(hits)),
+              "mi355_fold_work")
+        return ns
+
+    def work_device(self, noutput_items, input_items, output_items):
+        """CUDA tensors, enqueue only on torch's current stream; the same buffers as work()"""
+        ns = int(noutput_items)
+        if ns == 0:
+            return 0
+        n = ns * self.subint_len
+        tf = hits = None
+        if len(input_items) > 1 and input_items[1] is not None:
+            tf = _dp(input_items[1], n * self.num_rows, "input 1")
+        if len(output_items) > 1 and output_items[1] is not None:
+            hits = _dp(output_items[1], 4 * ns * self._hits, "output 1")
+        check(self._L.mi355_fold_work_dev(self._h, n, _dp(input_items[0], n * self._floats * 4, "input"), tf,
+                                          _dp(output_items[0], ns * self._out_floats * 4, "output"), hits, _torch_stream(self.device)),
+              "mi355_fold_work_dev")
+        return ns
+
+    def fold(self, x, tflags=None, hits=False):
+        """work() on a numpy input [n][R][F]: the archive [n / subint_len][R][nbin][F], or with hits (archive, hits)"""
+        x = _host(x, np.float32)
+        ns = x.size // self._floats // self.subint_len
+        y = np.empty((ns, self.num_rows, self.nbin, self.num_channels), np.float32)
+        if not hits:
+            self.work(ns, [x, tflags], [y])
+            return y
+        h = np.empty((ns, self.num_rows, self.nbin), np.uint32)
+        self.work(ns, [x, tflags], [y, h])
+        return y, h

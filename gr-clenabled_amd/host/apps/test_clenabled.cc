@@ -1089,11 +1089,76 @@ static int fbclean_test(size_t n)
     return g_fail ? 1 : 0;
 }
 
+// --fold-only: clFolder at (R, F, nbin, Ts) = (2, 256, 8, 32), 3 sub-integrations from T = 1000, on the samples of --fbclean-only, with the
+// models {0, floor(2^64 / 9), 0} and {2^62, floor(2^64 / 5) + 3, -2^44}, through the optional hits output and the "models" port.  Prints a
+// "checksum" line that tests/test_fold_gpu.py compares with the numpy reference: sum_i (i % 7 + 1) (bits of out_i) + sum_j (j % 5 + 1)
+// hits_j modulo 2^64; then one timing row.
+static int fold_test(size_t n)
+{
+    const int R = 2, F = 256, NBIN = 8, Ts = 32, NS = 3, N = NS * Ts;
+    uint32_t state = 12345u;
+    auto next = [&]() { state = state * 1664525u + 1013904223u; return (float)(state >> 24) + 1.0f; };
+    std::vector<float> x((size_t)N * R * F);
+    for (auto &v : x) v = next();
+    const std::vector<uint64_t> models = {0, UINT64_MAX / 9, 0, 1ull << 62, UINT64_MAX / 5 + 3, (uint64_t)-(1ll << 44)};
+    {
+        auto fo = clFolder::make(OCLTYPE_GPU, OCLDEVICESELECTOR_SPECIFIC, 0, g_dev, R, F, NBIN, Ts, std::vector<uint64_t>(6, 0));
+        bool ok = (int)fo->history() == 1 && (int)fo->decimation() == Ts && fo->subint_len() == Ts && fo->nbin() == NBIN &&
+                  fo->route().compare(0, 5, "bins ") == 0;
+#ifndef MI355_WITH_GNURADIO
+        ok = ok && fo->message_ports_in().size() == 1 && fo->message_ports_in()[0] == "models";
+        ok = ok && fo->post_u64vector("models", models) && fo->models() == models;
+        ok = ok && fo->post_u64vector("models", std::vector<uint64_t>(5, 1)) && fo->models() == models;  // a message of another size is dropped
+#else
+        fo->set_models(models);
+#endif
+        fo->set_sample(900);
+        fo->skip(100);
+        std::vector<float> y((size_t)NS * R * NBIN * F, -1e30f);
+        std::vector<uint32_t> hits((size_t)NS * R * NBIN, 0xEEEEEEEEu);
+        gr_vector_const_void_star in = {x.data()};
+        gr_vector_void_star out = {y.data(), hits.data()};
+        auto t0 = std::chrono::steady_clock::now();
+        ok = ok && fo->work(NS, in, out) == NS && fo->sample() == 1000u + N;
+        std::chrono::duration<double> dt = std::chrono::steady_clock::now() - t0;
+        unsigned long long sum = 0, total = 0;
+        for (size_t i = 0; i < y.size(); i++) {
+            uint32_t bits;
+            memcpy(&bits, &y[i], 4);
+            ok = ok && y[i] >= 0.0f;
+            sum += (unsigned long long)(i % 7 + 1) * bits;
+        }
+        for (size_t j = 0; j < hits.size(); j++) {
+            total += hits[j];
+            sum += (unsigned long long)(j % 5 + 1) * hits[j];
+        }
+        ok = ok && total == (unsigned long long)N * R;
+        printf("clFolder checksum %llu\n", sum);
+        report("clFolder (2 rows, 256 channels, 8 bins, sub-integrations of 32)", (size_t)N, dt.count(), ok);
+    }
+    {
+        const int Rt = 4, Ft = 1024, Bt = 4, Tst = 256, ns = (int)std::max<size_t>(n / 4096, 2), nt = ns * Tst;
+        std::vector<float> xt((size_t)nt * Rt * Ft);
+        for (size_t i = 0; i < xt.size(); i++) xt[i] = (float)((i / ((size_t)Rt * Ft)) & 3);  // 0, 1, 2, 3 along time
+        std::vector<uint64_t> mt;
+        for (int r = 0; r < Rt; r++) { mt.push_back(0); mt.push_back(1ull << 62); mt.push_back(0); }  // a period of four samples: bin = T mod 4
+        auto fo = clFolder::make(OCLTYPE_GPU, OCLDEVICESELECTOR_SPECIFIC, 0, g_dev, Rt, Ft, Bt, Tst, mt);
+        std::vector<float> y((size_t)ns * Rt * Bt * Ft, -1.0f);
+        gr_vector_const_void_star in = {xt.data()};
+        gr_vector_void_star out = {y.data()};
+        int got = 0;
+        const double t = time_calls([&] { fo->set_sample(0); got = fo->work(ns, in, out); });
+        report("clFolder (4 x 1024 channels, 4 bins, sub-integrations of 256, timing)", (size_t)nt, t,
+               got == ns && y[0] == 0.0f && y[(size_t)Ft] == 64.0f && y[(size_t)3 * Ft] == 192.0f && y.back() == 192.0f);
+    }
+    return g_fail ? 1 : 0;
+}
+
 int main(int argc, char **argv)
 {
     size_t n = 8192;  // the reference's default block size
     int fft_size = 4096, ntaps = 65;
-    bool only_fft = false, only_xcorrelate = false, xc_complex = false, only_loops = false, only_resampler = false, only_synth = false, only_pspec = false, only_xlate = false, only_beamform = false, only_fengine = false, only_dedisp = false, only_psearch = false, only_fbclean = false;
+    bool only_fft = false, only_xcorrelate = false, xc_complex = false, only_loops = false, only_resampler = false, only_synth = false, only_pspec = false, only_xlate = false, only_beamform = false, only_fengine = false, only_dedisp = false, only_psearch = false, only_fbclean = false, only_fold = false;
     int xc_inputs = 2, xc_maxsearch = 512;
     for (int i = 1; i < argc; i++) {
         if (!strncmp(argv[i], "--device=", 9)) g_dev = atoi(argv[i] + 9);
@@ -1113,6 +1178,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--dedisp-only")) only_dedisp = true;
         else if (!strcmp(argv[i], "--psearch-only")) only_psearch = true;
         else if (!strcmp(argv[i], "--fbclean-only")) only_fbclean = true;
+        else if (!strcmp(argv[i], "--fold-only")) only_fold = true;
         else if (!strncmp(argv[i], "--num_inputs=", 13)) xc_inputs = atoi(argv[i] + 13);
         else if (!strncmp(argv[i], "--maxsearch=", 12)) xc_maxsearch = atoi(argv[i] + 12);
         else if (!strcmp(argv[i], "--input_complex")) xc_complex = true;
@@ -1140,8 +1206,9 @@ int main(int argc, char **argv)
                    "       %s --fengine-only [--iterations N] [block size]\n"
                    "       %s --dedisp-only [--iterations N] [block size]\n"
                    "       %s --psearch-only [--iterations N] [block size]\n"
-                   "       %s --fbclean-only [--iterations N] [block size]\n",
-                   argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
+                   "       %s --fbclean-only [--iterations N] [block size]\n"
+                   "       %s --fold-only [--iterations N] [block size]\n",
+                   argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
             return 0;
         } else n = strtoull(argv[i], nullptr, 10);
     }
@@ -1183,6 +1250,10 @@ int main(int argc, char **argv)
     }
     if (only_fbclean) {
         try { return fbclean_test(n); }
+        catch (const std::exception &e) { std::cerr << "error: " << e.what() << std::endl; return 2; }
+    }
+    if (only_fold) {
+        try { return fold_test(n); }
         catch (const std::exception &e) { std::cerr << "error: " << e.what() << std::endl; return 2; }
     }
     if (only_xcorrelate) {

@@ -274,5 +274,30 @@ public:
     virtual std::string route() const = 0;
 };
 
+// gr::clenabled::clFolder -- exact pulsar folding of the filterbank that clBeamformer POWER and clFilterbankCleaner write, modulo a
+// known period: an integer phase model {phi0, nu, nudot} per row (units of 2^-64 turn; mi355_fold_model makes one), sums per (row,
+// phase bin, channel) in ascending time with one binary32 rounding each.  Beyond the reference module; the contract is in
+// mi355_clenabled.h.  A sync_decimator by subint_len: input 0 carries time samples of num_rows num_channels floats, the optional input
+// 1 the num_rows time-flag bytes of each sample (clFilterbankCleaner's output 1); an output item is one sub-integration of num_rows
+// nbin num_channels floats ([row][bin][chan]), the optional output 1 its num_rows nbin hit counts (uint32).  models: 3 num_rows words,
+// row-major.  The input message port "models" takes a pair whose cdr is a u64vector of 3 num_rows words and calls set_models; a
+// message of another size is dropped.  The library handle counts the absolute sample index.
+// (No per-block header of this name is installed by this build yet.)
+class CLENABLED_API clFolder : virtual public gr::sync_decimator {
+public:
+    typedef std::shared_ptr<clFolder> sptr;
+    static sptr make(int openCLPlatformType, int devSelector, int platformId, int devId, int num_rows, int num_channels, int nbin, int subint_len,
+                     const std::vector<uint64_t> &models, int setDebug = 0);
+    virtual void set_models(const std::vector<uint64_t> &models) = 0;  // 3 num_rows words, anything else throws; for the calls after it returns
+    virtual std::vector<uint64_t> models() const = 0;
+    virtual uint64_t sample() const = 0;          // the absolute index of the next sample
+    virtual void set_sample(uint64_t T) = 0;
+    virtual void skip(long long n) = 0;           // n >= 0 samples that are not folded
+    virtual int nbin() const = 0;
+    virtual int subint_len() const = 0;
+    virtual void set_generic(bool on) = 0;  // the generic route for every later call
+    virtual std::string route() const = 0;
+};
+
 }  // namespace clenabled
 }  // namespace gr

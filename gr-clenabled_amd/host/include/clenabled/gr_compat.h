@@ -70,6 +70,7 @@ class basic_block_shim {
     std::vector<long> d_offered, d_offer_base;  // set_offered(): what the caller acting as scheduler offers the next general_work()
     std::vector<std::string> d_out_ports, d_in_ports;
     std::map<std::string, std::function<void(double)>> d_in_handlers;
+    std::map<std::string, std::function<void(const std::vector<uint64_t> &)>> d_in_u64_handlers;
     std::deque<shim_message> d_messages;
     std::vector<uint64_t> d_first_tags;  // what get_tags_in_window(i, 0, 1) would return, set by the caller acting as scheduler
 
@@ -139,6 +140,15 @@ public:
     {
         auto it = d_in_handlers.find(port);
         if (it == d_in_handlers.end()) return false;
+        it->second(value);
+        return true;
+    }
+    // input message ports that carry a vector of 64-bit words (cons(key, u64vector) under GNU Radio), delivered the same way
+    void set_u64vector_handler(const std::string &port, std::function<void(const std::vector<uint64_t> &)> fn) { d_in_u64_handlers[port] = std::move(fn); }
+    bool post_u64vector(const std::string &port, const std::vector<uint64_t> &value)
+    {
+        auto it = d_in_u64_handlers.find(port);
+        if (it == d_in_u64_handlers.end()) return false;
         it->second(value);
         return true;
     }

@@ -539,4 +539,33 @@ PYBIND11_MODULE(clenabled_python, m)
         .def("output_multiple", [](clFilterbankCleaner &b) { return b.output_multiple(); })
         .def("history", [](clFilterbankCleaner &b) { return b.history(); })
         .def("work", &call_work<clFilterbankCleaner>, py::arg("noutput_items"), py::arg("input_items"), py::arg("output_items"));
+
+    // folder (lib/clFolder_impl.cc): input items are time samples of R F floats (input_items[1], optional: R flag bytes per sample), an
+    // output item is one sub-integration of R nbin F floats (output_items[1], optional: R nbin uint32 hit counts); models are 3 R uint64
+    using u64array = py::array_t<uint64_t, py::array::c_style | py::array::forcecast>;
+    py::class_<clFolder DECIM_BASES, std::shared_ptr<clFolder>>(m, "clFolder")
+        .def(py::init([](int openCLPlatformType, int devSelector, int platformId, int devId, int num_rows, int num_channels, int nbin, int subint_len,
+                         const u64array &models, int setDebug) {
+                 return clFolder::make(openCLPlatformType, devSelector, platformId, devId, num_rows, num_channels, nbin, subint_len,
+                                       std::vector<uint64_t>(models.data(), models.data() + models.size()), setDebug);
+             }),
+             py::arg("openCLPlatformType"), py::arg("devSelector"), py::arg("platformId"), py::arg("devId"), py::arg("num_rows"),
+             py::arg("num_channels"), py::arg("nbin"), py::arg("subint_len"), py::arg("models"), py::arg("setDebug") = 0)
+        .def("set_models", [](clFolder &b, const u64array &t) { b.set_models(std::vector<uint64_t>(t.data(), t.data() + t.size())); },
+             py::arg("models"))
+        .def("models",
+             [](clFolder &b) {
+                 const std::vector<uint64_t> t = b.models();
+                 return u64array(t.size(), t.data());
+             })
+        .def("sample", &clFolder::sample)
+        .def("set_sample", &clFolder::set_sample, py::arg("T"))
+        .def("skip", &clFolder::skip, py::arg("n"))
+        .def("nbin", &clFolder::nbin)
+        .def("subint_len", &clFolder::subint_len)
+        .def("set_generic", &clFolder::set_generic, py::arg("on"))
+        .def("route", &clFolder::route)
+        .def("decimation", [](clFolder &b) { return b.decimation(); })
+        .def("history", [](clFolder &b) { return b.history(); })
+        .def("work", &call_work<clFolder>, py::arg("noutput_items"), py::arg("input_items"), py::arg("output_items"));
 }

@@ -1096,6 +1096,90 @@ int mi355_fbclean_work(mi355_fbclean *h, long long n, const void *in, void *out,
 int mi355_fbclean_work_dev(mi355_fbclean *h, long long n, const void *in, void *out, void *cflags, void *tflags, void *stats, void *stream);
 int mi355_fbclean_sk_estimate(const float *x, int block_len, long long stride, double nd, double *sk);
 
+/* ------------------------------------------------------------------------------------------------
+ * Folder: clFolder, exact pulsar folding of the filterbank that clBeamformer POWER and clFilterbankCleaner write, modulo a known
+ * period, into an archive of sub-integrations x rows x phase bins x channels.  Beyond the reference module, which has nothing of the
+ * kind (this comment is the contract).  The phase is integer and the summation order is pinned, so there is no tolerance anywhere.
+ *     R = num_rows (beams) 1 .. 4096;  F = num_channels 1 .. 16384;  nbin 2 .. 4096, any integer;
+ *     Ts = subint_len, a multiple of 16 in 16 .. 16384, fixed per handle.
+ * Input: x[t][r][f] float32, channel fastest.  Optional tflags[t][r] uint8, clFilterbankCleaner's time-flag output as it stands: a
+ * nonzero flag takes that sample out of every channel of that row and out of the hit count; NULL: none.
+ * Phase model, one per row: three 64-bit words {phi0, nu, nudot}.  phi0 and nu are unsigned, in 2^-64 turn and 2^-64 turn per sample;
+ * nudot is signed two's complement, in 2^-64 turn per sample^2.  T is the absolute sample index of the stream, an unsigned 64-bit
+ * counter kept by the handle (0 at _create; _set_sample, _skip).  All arithmetic wraps modulo 2^64, T included:
+ *     tri(T) = (T even) ? (T / 2) (T - 1) : T ((T - 1) / 2)
+ *     phi(T) = phi0 + nu T + nudot tri(T)
+ *     bin(T) = (((phi(T) >> 32) nbin) >> 32)                      0 .. nbin - 1
+ * No float touches the phase, so it does not drift at any stream length (as clFreqXlatingFIRFilter's).  Every value of the three words
+ * is legal: nu = 0 puts everything of a row in one bin; periods shorter than two samples (nu >= 2^63) alias but are defined.  The
+ * resolution of nudot: one unit moves the phase by 2^-64 T^2 / 2 turns, i.e. by one bin of 4096 after T = 2^26.5 ~ 9.5e7 samples; the
+ * top 32 bits of the phase decide the bin, so two phases closer than 2^-32 turn may share a bin edge.
+ * Stream: a call folds n samples T = T0 .. T0 + n - 1, then T0 += n.  n is a multiple of Ts; n == 0 is a no-op.  Sub-integration j of a
+ * call covers its samples j Ts .. (j + 1) Ts - 1.  Sub-integrations are independent; T0 is the only stream state.
+ * Outputs: out[j][r][b][f] float32, channel fastest -- a filterbank whose time axis is phase, so what reads a filterbank reads an
+ * archive row.  out[j][r][b][f] starts from +0.0f and adds, in ascending T, one binary32 rounding each, every unflagged x[T][r][f] of
+ * the sub-integration with bin_r(T) == b.  An empty bin is +0.0f.  Nothing is accumulated into what `out` held before.
+ * Optional hits[j][r][b] uint32: the number of samples that entered (NULL: not wanted).
+ * THE SUMMATION ORDER IS THE CONTRACT: a tree or a float atomic gives other bits and does not conform.  Consequences: a NaN or +-Inf
+ * at (T, r, f) reaches out[j][r][bin_r(T)][f] and nothing else; a column of -0.0f folds to +0.0f.  Results with a subnormal
+ * intermediate are unspecified, as elsewhere in the library.
+ * Invariance: either route, any split of a stream into calls at sub-integration boundaries, _skip(n) over samples that are not folded,
+ * any 4-byte alignment of in and out (hits 4-byte) and any n give identical bits.
+ * Routes, fixed at _create by the shape and named by _route():
+ *   "bins R=64 F=1024 nbin=256 Ts=4096" -- F a multiple of 64, every nbin and Ts.  An index launch per chunk of whole
+ *       sub-integrations (1 / F of the data): a workgroup per (sub-integration, row) computes bin(T), drops the flagged samples, sorts
+ *       the distinct keys (bin, t) in LDS and leaves per-bin lists, in ascending t, in a scratch buffer allocated at _create (at least
+ *       one sub-integration's 4 R (Ts + nbin + 1) bytes, 16 MiB if that holds more than one); hits are the list lengths.  Then a wave
+ *       owns (sub-integration, row, a group of 256, 128 or 64 channels by the largest of them that divides F, a run of bins holding
+ *       about 32 rows): lanes run along channels (16-byte loads where F is a multiple of 256), the accumulators stay in registers over
+ *       the bin's list, 8 rows' loads in flight before the 8 additions that consume them in order.  Bins partition time: every sample
+ *       is read exactly once, there is no LDS accumulator and no float atomic, and a bin leaves as one whole channel run.
+ *   "generic R=3 F=52 nbin=7 Ts=48" -- every other shape and every handle under _set_generic(h, 1): one thread per output walks its
+ *       sub-integration.
+ * The route is forced by _set_generic only; there is no environment switch.
+ * Model updates: a call enqueued before _set_models returns uses the old table entirely, a later call the new one entirely (versioned
+ * device buffers, released behind the event of their last launch; nothing on the work path waits for the device).  A refused update
+ * changes nothing.
+ * Errors (nothing launched, T0 unchanged): NULL in or out, in, out or hits not 4-byte aligned, any two buffers overlapping, n < 0 or
+ * n % Ts != 0, a shape outside the ranges above: MI355_ERR_INVALID_ARG.  More than 2^40 bytes per buffer and call:
+ * MI355_ERR_UNSUPPORTED.
+ *   _plan         floats_per_sample = R F, floats_per_subint = R nbin F, hits_per_subint = R nbin; no device; any pointer may be NULL
+ *   _create       models: 3 R words, row-major; everything that can be told without a device is checked before ctx is touched
+ *   _set_models   replaces the 3 R words;  _get_models copies them, cap_words is the size of `out` in words
+ *   _sample       *T = T0;  _set_sample: T0 = T;  _skip: T0 += n, n >= 0 (samples that are not folded)
+ *   _subint_len   Ts
+ *   _set_generic  on != 0: the generic route for every later call of the handle; 0: back
+ *   _route        valid until the next _set_generic / _destroy of the handle; "" for NULL
+ *   _work         host pointers, blocking: the shared staging pipeline in pieces of whole sub-integrations
+ *   _work_dev     device pointers, enqueue only: allocates nothing and waits for nothing
+ * Host-only helpers, no context:
+ *   mi355_fold_model  the three words of a pulsar of period `period_s` seconds with period derivative `pdot` (s/s) sampled every
+ *       `tsamp_s` seconds, at phase `phase0_turns` at T = 0, computed in long double: q = tsamp / period, nudot = -pdot q^2 (the
+ *       frequency derivative -pdot / period^2 times tsamp^2), nu = q + nudot / 2 (so that nu T + nudot tri(T) is f0 t + fdot t^2 / 2 at
+ *       t = T tsamp), phi0 and nu taken modulo one turn.  Rounding: each word is its long double value times 2^64 rounded to the
+ *       nearest integer (ties to even), and with the errors of the long double quotient and sum each word lies within two units
+ *       (2^-63) of the exact value where long double has a 64-bit significand and tsamp < period.  Refuses non-finite input, period <= 0, tsamp <= 0 and |nudot| >= 1/2.
+ *   mi355_fold_bins   bins[i] = bin(T0 + i), i = 0 .. n - 1, of one model, bit for bit as the device computes it: a caller checks a
+ *       setup or builds a template without a device (the counterpart of mi355_fbclean_sk_estimate).
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct mi355_fold mi355_fold;
+int mi355_fold_plan(int num_rows, int num_channels, int nbin, int subint_len, long long *floats_per_sample, long long *floats_per_subint,
+                    long long *hits_per_subint);
+int mi355_fold_create(mi355_ctx *ctx, int num_rows, int num_channels, int nbin, int subint_len, const uint64_t *models, mi355_fold **out);
+int mi355_fold_destroy(mi355_fold *h);
+int mi355_fold_set_models(mi355_fold *h, const uint64_t *models);
+int mi355_fold_get_models(const mi355_fold *h, uint64_t *out, long long cap_words);
+int mi355_fold_sample(const mi355_fold *h, unsigned long long *T);
+int mi355_fold_set_sample(mi355_fold *h, unsigned long long T);
+int mi355_fold_skip(mi355_fold *h, long long n);
+long long mi355_fold_subint_len(const mi355_fold *h);
+int mi355_fold_set_generic(mi355_fold *h, int on);
+const char *mi355_fold_route(const mi355_fold *h);
+int mi355_fold_work(mi355_fold *h, long long n, const void *in, const void *tflags, void *out, void *hits);
+int mi355_fold_work_dev(mi355_fold *h, long long n, const void *in, const void *tflags, void *out, void *hits, void *stream);
+int mi355_fold_model(double period_s, double pdot, double tsamp_s, double phase0_turns, uint64_t out[3]);
+int mi355_fold_bins(const uint64_t model[3], uint64_t T0, long long n, int nbin, int32_t *bins);
+
 #ifdef __cplusplus
 }
 #endif
