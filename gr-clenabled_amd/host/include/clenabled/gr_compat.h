@@ -15,6 +15,8 @@
 #include <gnuradio/sync_block.h>
 #include <gnuradio/sync_decimator.h>
 #include <pmt/pmt.h>
+#include <functional>
+#include <vector>
 #else
 #include <complex>
 #include <cstdint>
@@ -208,6 +210,34 @@ inline void publish_u64(gr::basic_block *b, const char *port, const char *key, u
 {
     b->message_port_pub(pmt::mp(port), pmt::cons(pmt::intern(key), pmt::from_uint64(value)));
 }
+// clXCorrelate's PDU: cons(dict{"corrvect": f32vector, "corrective_lags": s32vector}, PMT_NIL) -- lib/clXCorrelate_impl.cc:1594-1600
+inline void publish_corr_pdu(gr::basic_block *b, const char *port, const std::vector<float> &corr, const std::vector<int32_t> &lags)
+{
+    pmt::pmt_t meta = pmt::make_dict();
+    meta = pmt::dict_add(meta, pmt::mp("corrvect"), pmt::init_f32vector(corr.size(), corr.data()));
+    meta = pmt::dict_add(meta, pmt::mp("corrective_lags"), pmt::init_s32vector(lags.size(), lags.data()));
+    b->message_port_pub(pmt::mp(port), pmt::cons(meta, pmt::PMT_NIL));
+}
+// input ports that carry cons(key, real) / cons(key, u64vector): a message that is no pair, or whose cdr is of another type, is dropped
+// (the scheduler's thread has nobody to throw to)
+inline void register_in_double(gr::basic_block *b, const char *port, std::function<void(double)> fn)
+{
+    b->message_port_register_in(pmt::mp(port));
+    b->set_msg_handler(pmt::mp(port), [fn](pmt::pmt_t msg) {
+        if (!pmt::is_pair(msg)) return;
+        const pmt::pmt_t v = pmt::cdr(msg);
+        if (pmt::is_real(v)) fn(pmt::to_double(v));
+    });
+}
+inline void register_in_u64vector(gr::basic_block *b, const char *port, std::function<void(const std::vector<uint64_t> &)> fn)
+{
+    b->message_port_register_in(pmt::mp(port));
+    b->set_msg_handler(pmt::mp(port), [fn](pmt::pmt_t msg) {
+        if (!pmt::is_pair(msg)) return;
+        const pmt::pmt_t v = pmt::cdr(msg);
+        if (pmt::is_u64vector(v)) fn(pmt::u64vector_elements(v));
+    });
+}
 // (reading the first tag of an input, get_tags_in_window, is protected in gr::block: a member of clXEngine_impl does it)
 // blocks are handed to the scheduler through GNU Radio's initial-sptr registry, as every make() of the reference does
 template <class T> std::shared_ptr<T> adopt(T *p) { return gnuradio::get_initial_sptr(p); }
@@ -229,6 +259,26 @@ inline void publish_u64(gr::basic_block_shim *b, const char *port, const char *k
     m.key = key;
     m.u64 = value;
     b->shim_publish(std::move(m));
+}
+// (one message with key "corrvect" and both vectors, see shim_message)
+inline void publish_corr_pdu(gr::basic_block_shim *b, const char *port, const std::vector<float> &corr, const std::vector<int32_t> &lags)
+{
+    gr::shim_message m;
+    m.port = port;
+    m.key = "corrvect";
+    m.f32 = corr;
+    m.s32 = lags;
+    b->shim_publish(std::move(m));
+}
+inline void register_in_double(gr::basic_block_shim *b, const char *port, std::function<void(double)> fn)
+{
+    b->message_port_register_in(port);
+    b->set_double_handler(port, std::move(fn));
+}
+inline void register_in_u64vector(gr::basic_block_shim *b, const char *port, std::function<void(const std::vector<uint64_t> &)> fn)
+{
+    b->message_port_register_in(port);
+    b->set_u64vector_handler(port, std::move(fn));
 }
 template <class T> std::shared_ptr<T> adopt(T *p) { return std::shared_ptr<T>(p); }
 inline void no_tag_propagation(gr::basic_block_shim *) {}

@@ -2,7 +2,7 @@
 // input item is one frame and whose output item is one unit's output: decimation 1 in VOLTAGE mode, `integration` in POWER mode, so a
 // call for n output items hands the library n units = n decimation frames.  Weights live in the library handle.
 #include <clenabled/clenabled.h>
-#include <mi355_clenabled.h>
+#include "block_base.h"
 
 #include <mutex>
 #include <stdexcept>
@@ -13,12 +13,6 @@ namespace gr {
 namespace clenabled {
 namespace {
 
-void chk(int rc, const char *what)
-{
-    if (rc == MI355_ERR_INVALID_ARG) throw std::invalid_argument(std::string(what) + ": " + mi355_last_error());
-    if (rc < 0) throw std::runtime_error(std::string(what) + ": " + mi355_strerror(rc) + ": " + mi355_last_error());
-}
-
 struct Plan {
     long long frame_bytes = 0, out_bytes = 0;
     int frames_per_unit = 1;
@@ -28,14 +22,12 @@ struct Plan {
 Plan plan(int mode, int npol, int S, int F, int B, int Ti, bool stokes)
 {
     Plan p;
-    chk(mi355_beamform_plan(mode, npol, S, F, B, Ti, stokes ? 1 : 0, &p.frame_bytes, &p.frames_per_unit, &p.out_bytes), "clBeamformer");
-    if (p.frame_bytes > 0x7fffffffll || p.out_bytes > 0x7fffffffll) throw std::invalid_argument("clBeamformer: a stream item of 2 GiB or more");
+    chk_arg(mi355_beamform_plan(mode, npol, S, F, B, Ti, stokes ? 1 : 0, &p.frame_bytes, &p.frames_per_unit, &p.out_bytes), "clBeamformer");
+    check_stream_item("clBeamformer", {p.frame_bytes, p.out_bytes});
     return p;
 }
 
-class clBeamformer_impl : public clBeamformer {
-    mi355_ctx *d_ctx = nullptr;
-    mi355_beamform *d_h = nullptr;
+class clBeamformer_impl : public clBeamformer, BlockBase<mi355_beamform, mi355_beamform_destroy> {
     const Plan d_plan;
     const size_t d_wbytes, d_beam_bytes;
     const int d_beams;
@@ -51,26 +43,16 @@ public:
         if (!weights.empty() && weights.size() != d_wbytes)
             throw std::invalid_argument("clBeamformer: weights hold " + std::to_string(weights.size()) + " bytes, the geometry needs " +
                                         std::to_string(d_wbytes));
-        chk(mi355_ctx_create(openCLPlatformType, devSelector, platformId, devId, setDebug ? 1 : 0, &d_ctx), "mi355_ctx_create");
-        const int rc = mi355_beamform_create(d_ctx, mode, npol, S, F, B, Ti, stokes ? 1 : 0, weights.empty() ? nullptr : weights.data(), &d_h);
-        if (rc) {
-            const std::string msg = std::string("mi355_beamform_create: ") + mi355_strerror(rc) + ": " + mi355_last_error();
-            mi355_ctx_destroy(d_ctx);
-            if (rc == MI355_ERR_INVALID_ARG) throw std::invalid_argument(msg);
-            throw std::runtime_error(msg);
-        }
-    }
-    ~clBeamformer_impl() override
-    {
-        mi355_beamform_destroy(d_h);
-        mi355_ctx_destroy(d_ctx);
+        d_ctx.open(openCLPlatformType, devSelector, platformId, devId, setDebug, chk_arg);
+        created(mi355_beamform_create(d_ctx, mode, npol, S, F, B, Ti, stokes ? 1 : 0, weights.empty() ? nullptr : weights.data(), d_h.adopt()),
+                "mi355_beamform_create");
     }
     void set_weights(const std::vector<int8_t> &weights) override
     {
         if (weights.size() != d_wbytes)
             throw std::invalid_argument("clBeamformer: set_weights() takes " + std::to_string(d_wbytes) + " bytes, got " + std::to_string(weights.size()));
         std::lock_guard<std::mutex> g(d_lock);
-        chk(mi355_beamform_set_weights(d_h, weights.data()), "mi355_beamform_set_weights");
+        chk_arg(mi355_beamform_set_weights(d_h, weights.data()), "mi355_beamform_set_weights");
     }
     void set_beam_weights(int beam, const std::vector<int8_t> &w_beam) override
     {
@@ -78,23 +60,23 @@ public:
             throw std::invalid_argument("clBeamformer: set_beam_weights() takes " + std::to_string(d_beam_bytes) + " bytes, got " +
                                         std::to_string(w_beam.size()));
         std::lock_guard<std::mutex> g(d_lock);
-        chk(mi355_beamform_set_beam_weights(d_h, beam, w_beam.data()), "mi355_beamform_set_beam_weights");
+        chk_arg(mi355_beamform_set_beam_weights(d_h, beam, w_beam.data()), "mi355_beamform_set_beam_weights");
     }
     std::vector<int8_t> weights() const override
     {
         std::vector<int8_t> w(d_wbytes);
-        chk(mi355_beamform_get_weights(d_h, w.data(), (long long)w.size()), "mi355_beamform_get_weights");
+        chk_arg(mi355_beamform_get_weights(d_h, w.data(), (long long)w.size()), "mi355_beamform_get_weights");
         return w;
     }
     int num_beams() const override { return d_beams; }
     long long frame_bytes() const override { return d_plan.frame_bytes; }
     long long out_bytes_per_unit() const override { return d_plan.out_bytes; }
-    void set_generic(bool on) override { chk(mi355_beamform_set_generic(d_h, on ? 1 : 0), "mi355_beamform_set_generic"); }
+    void set_generic(bool on) override { chk_arg(mi355_beamform_set_generic(d_h, on ? 1 : 0), "mi355_beamform_set_generic"); }
     std::string route() const override { return mi355_beamform_route(d_h); }
     int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
     {
         std::lock_guard<std::mutex> g(d_lock);
-        chk(mi355_beamform_work(d_h, noutput_items, in[0], out[0]), "mi355_beamform_work");
+        chk_arg(mi355_beamform_work(d_h, noutput_items, in[0], out[0]), "mi355_beamform_work");
         return noutput_items;
     }
 };

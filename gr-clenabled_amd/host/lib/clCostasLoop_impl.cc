@@ -1,7 +1,7 @@
 // clCostasLoop_impl: the reference's lib/clCostasLoop_impl.cc over the C ABI (mi355_costas_*), one stream.  The loop state (phase,
 // frequency, error) lives on the device and carries from one work() call to the next (:525-596); the getters read it back.
 #include <clenabled/clenabled.h>
-#include <mi355_clenabled.h>
+#include "block_base.h"
 
 #include <stdexcept>
 #include <string>
@@ -11,14 +11,7 @@ namespace gr {
 namespace clenabled {
 namespace {
 
-void chk(int rc, const char *what)
-{
-    if (rc < 0) throw std::runtime_error(std::string(what) + ": " + mi355_strerror(rc) + ": " + mi355_last_error());
-}
-
-class clCostasLoop_impl : public clCostasLoop {
-    mi355_ctx *d_ctx = nullptr;
-    mi355_costas *d_h = nullptr;
+class clCostasLoop_impl : public clCostasLoop, BlockBase<mi355_costas, mi355_costas_destroy> {
     const int d_order;
     float d_loop_bw, d_alpha = 0, d_beta = 0;
 
@@ -26,7 +19,7 @@ class clCostasLoop_impl : public clCostasLoop {
     {
         const int rc = mi355_costas_plan(bw, d_order, &d_alpha, &d_beta);
         if (rc == MI355_ERR_INVALID_ARG) throw std::invalid_argument(std::string("clCostasLoop: ") + mi355_last_error());
-        chk(rc, "mi355_costas_plan");
+        chk_runtime(rc, "mi355_costas_plan");
         d_loop_bw = bw;
     }
 
@@ -37,23 +30,13 @@ public:
           d_order(order), d_loop_bw(loop_bw)
     {
         plan(loop_bw);
-        chk(mi355_ctx_create(openCLPlatformType, devSelector, platformId, devId, setDebug ? 1 : 0, &d_ctx), "mi355_ctx_create");
-        const int rc = mi355_costas_create(d_ctx, loop_bw, order, 1, &d_h);
-        if (rc) {
-            const std::string msg = std::string("mi355_costas_create: ") + mi355_strerror(rc) + ": " + mi355_last_error();
-            mi355_ctx_destroy(d_ctx);
-            throw std::runtime_error(msg);
-        }
-    }
-    ~clCostasLoop_impl() override
-    {
-        mi355_costas_destroy(d_h);
-        mi355_ctx_destroy(d_ctx);
+        d_ctx.open(openCLPlatformType, devSelector, platformId, devId, setDebug);
+        created(mi355_costas_create(d_ctx, loop_bw, order, 1, d_h.adopt()), "mi355_costas_create", ArgIs::runtime_error);
     }
     void set_loop_bandwidth(float bw) override
     {
         plan(bw);
-        chk(mi355_costas_set_loop_bandwidth(d_h, bw), "mi355_costas_set_loop_bandwidth");
+        chk_runtime(mi355_costas_set_loop_bandwidth(d_h, bw), "mi355_costas_set_loop_bandwidth");
     }
     float get_loop_bandwidth() const override { return d_loop_bw; }
     float get_alpha() const override { return d_alpha; }
@@ -61,29 +44,29 @@ public:
     float get_frequency() const override
     {
         double v = 0;
-        chk(mi355_costas_get_state(d_h, nullptr, &v, nullptr), "mi355_costas_get_state");
+        chk_runtime(mi355_costas_get_state(d_h, nullptr, &v, nullptr), "mi355_costas_get_state");
         return (float)v;
     }
     float get_phase() const override
     {
         double v = 0;
-        chk(mi355_costas_get_state(d_h, &v, nullptr, nullptr), "mi355_costas_get_state");
+        chk_runtime(mi355_costas_get_state(d_h, &v, nullptr, nullptr), "mi355_costas_get_state");
         return (float)v;
     }
     void set_frequency(float freq) override
     {
         const double v = freq;
-        chk(mi355_costas_set_state(d_h, nullptr, &v), "mi355_costas_set_state");
+        chk_runtime(mi355_costas_set_state(d_h, nullptr, &v), "mi355_costas_set_state");
     }
     void set_phase(float phase) override
     {
         const double v = phase;
-        chk(mi355_costas_set_state(d_h, &v, nullptr), "mi355_costas_set_state");
+        chk_runtime(mi355_costas_set_state(d_h, &v, nullptr), "mi355_costas_set_state");
     }
     int work(int noutput_items, gr_vector_const_void_star &input_items, gr_vector_void_star &output_items) override
     {
         float *foptr = output_items.size() >= 2 ? (float *)output_items[1] : nullptr;  // :456-458
-        chk(mi355_costas_work(d_h, (size_t)noutput_items, input_items[0], output_items[0], foptr), "mi355_costas_work");
+        chk_runtime(mi355_costas_work(d_h, (size_t)noutput_items, input_items[0], output_items[0], foptr), "mi355_costas_work");
         return noutput_items;
     }
 };

@@ -2,7 +2,7 @@
 // of R F floats and whose output item is that sample's R D sums (TIME_MAJOR); history max_delay + 1, so a call for n output items hands
 // the library the n samples with max_delay samples of look-ahead behind them.  The delay table lives in the library handle.
 #include <clenabled/clenabled.h>
-#include <mi355_clenabled.h>
+#include "block_base.h"
 
 #include <mutex>
 #include <stdexcept>
@@ -13,12 +13,6 @@ namespace gr {
 namespace clenabled {
 namespace {
 
-void chk(int rc, const char *what)
-{
-    if (rc == MI355_ERR_INVALID_ARG) throw std::invalid_argument(std::string(what) + ": " + mi355_last_error());
-    if (rc < 0) throw std::runtime_error(std::string(what) + ": " + mi355_strerror(rc) + ": " + mi355_last_error());
-}
-
 struct Plan {
     long long in_floats = 0, history = 0, out_floats = 0;
 };
@@ -27,14 +21,12 @@ struct Plan {
 Plan plan(int R, int F, int D, int H)
 {
     Plan p;
-    chk(mi355_dedisp_plan(R, F, D, H, MI355_DEDISP_TIME_MAJOR, &p.in_floats, &p.history, &p.out_floats), "clDedisperser");
-    if (p.in_floats * 4 > 0x7fffffffll || p.out_floats * 4 > 0x7fffffffll) throw std::invalid_argument("clDedisperser: a stream item of 2 GiB or more");
+    chk_arg(mi355_dedisp_plan(R, F, D, H, MI355_DEDISP_TIME_MAJOR, &p.in_floats, &p.history, &p.out_floats), "clDedisperser");
+    check_stream_item("clDedisperser", {p.in_floats * 4, p.out_floats * 4});
     return p;
 }
 
-class clDedisperser_impl : public clDedisperser {
-    mi355_ctx *d_ctx = nullptr;
-    mi355_dedisp *d_h = nullptr;
+class clDedisperser_impl : public clDedisperser, BlockBase<mi355_dedisp, mi355_dedisp_destroy> {
     const Plan d_plan;
     const size_t d_entries;
     std::mutex d_lock;
@@ -49,40 +41,30 @@ public:
             throw std::invalid_argument("clDedisperser: delays hold " + std::to_string(delays.size()) + " entries, the geometry needs " +
                                         std::to_string(d_entries));
         set_history((unsigned)p.history + 1);
-        chk(mi355_ctx_create(openCLPlatformType, devSelector, platformId, devId, setDebug ? 1 : 0, &d_ctx), "mi355_ctx_create");
-        const int rc = mi355_dedisp_create(d_ctx, R, F, D, H, MI355_DEDISP_TIME_MAJOR, delays.empty() ? nullptr : delays.data(), &d_h);
-        if (rc) {
-            const std::string msg = std::string("mi355_dedisp_create: ") + mi355_strerror(rc) + ": " + mi355_last_error();
-            mi355_ctx_destroy(d_ctx);
-            if (rc == MI355_ERR_INVALID_ARG) throw std::invalid_argument(msg);
-            throw std::runtime_error(msg);
-        }
-    }
-    ~clDedisperser_impl() override
-    {
-        mi355_dedisp_destroy(d_h);
-        mi355_ctx_destroy(d_ctx);
+        d_ctx.open(openCLPlatformType, devSelector, platformId, devId, setDebug, chk_arg);
+        created(mi355_dedisp_create(d_ctx, R, F, D, H, MI355_DEDISP_TIME_MAJOR, delays.empty() ? nullptr : delays.data(), d_h.adopt()),
+                "mi355_dedisp_create");
     }
     void set_delays(const std::vector<int32_t> &delays) override
     {
         if (delays.size() != d_entries)
             throw std::invalid_argument("clDedisperser: set_delays() takes " + std::to_string(d_entries) + " entries, got " + std::to_string(delays.size()));
         std::lock_guard<std::mutex> g(d_lock);
-        chk(mi355_dedisp_set_delays(d_h, delays.data()), "mi355_dedisp_set_delays");
+        chk_arg(mi355_dedisp_set_delays(d_h, delays.data()), "mi355_dedisp_set_delays");
     }
     std::vector<int32_t> delays() const override
     {
         std::vector<int32_t> t(d_entries);
-        chk(mi355_dedisp_get_delays(d_h, t.data(), (long long)t.size()), "mi355_dedisp_get_delays");
+        chk_arg(mi355_dedisp_get_delays(d_h, t.data(), (long long)t.size()), "mi355_dedisp_get_delays");
         return t;
     }
     int max_delay() const override { return (int)d_plan.history; }
-    void set_generic(bool on) override { chk(mi355_dedisp_set_generic(d_h, on ? 1 : 0), "mi355_dedisp_set_generic"); }
+    void set_generic(bool on) override { chk_arg(mi355_dedisp_set_generic(d_h, on ? 1 : 0), "mi355_dedisp_set_generic"); }
     std::string route() const override { return mi355_dedisp_route(d_h); }
     int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
     {
         std::lock_guard<std::mutex> g(d_lock);
-        chk(mi355_dedisp_work(d_h, noutput_items, in[0], out[0], 0), "mi355_dedisp_work");
+        chk_arg(mi355_dedisp_work(d_h, noutput_items, in[0], out[0], 0), "mi355_dedisp_work");
         return noutput_items;
     }
 };

@@ -3,7 +3,7 @@
 // a call for n output items hands the library, per input, the n num_channels new items with (P - 1) num_channels items in front.
 // Taps, gains and the clip counters live in the library handle.
 #include <clenabled/clenabled.h>
-#include <mi355_clenabled.h>
+#include "block_base.h"
 
 #include <mutex>
 #include <stdexcept>
@@ -14,12 +14,6 @@ namespace gr {
 namespace clenabled {
 namespace {
 
-void chk(int rc, const char *what)
-{
-    if (rc == MI355_ERR_INVALID_ARG) throw std::invalid_argument(std::string(what) + ": " + mi355_last_error());
-    if (rc < 0) throw std::runtime_error(std::string(what) + ": " + mi355_strerror(rc) + ": " + mi355_last_error());
-}
-
 struct Plan {
     long long frame_bytes = 0, history_items = 0;
 };
@@ -28,14 +22,12 @@ struct Plan {
 Plan plan(int npol, int S, int F, int P, bool shift)
 {
     Plan p;
-    chk(mi355_fengine_plan(S, npol, F, P, shift ? 1 : 0, 0, &p.frame_bytes, &p.history_items, nullptr), "clFEngine");
+    chk_arg(mi355_fengine_plan(S, npol, F, P, shift ? 1 : 0, 0, &p.frame_bytes, &p.history_items, nullptr), "clFEngine");
     if (p.frame_bytes > 0x7fffffffll || p.history_items >= 0x7fffffffll) throw std::invalid_argument("clFEngine: a stream item or a history of 2 GiB or more");
     return p;
 }
 
-class clFEngine_impl : public clFEngine {
-    mi355_ctx *d_ctx = nullptr;
-    mi355_fengine *d_h = nullptr;
+class clFEngine_impl : public clFEngine, BlockBase<mi355_fengine, mi355_fengine_destroy> {
     const Plan d_plan;
     const int d_nin, d_nchan;
     std::mutex d_lock;
@@ -54,20 +46,10 @@ public:
             throw std::invalid_argument("clFEngine: gains hold " + std::to_string(gains.size()) + " values, the geometry needs " +
                                         std::to_string((size_t)d_nin * F));
         set_history((unsigned)p.history_items + 1);
-        chk(mi355_ctx_create(openCLPlatformType, devSelector, platformId, devId, setDebug ? 1 : 0, &d_ctx), "mi355_ctx_create");
-        const int rc = mi355_fengine_create(d_ctx, S, npol, F, P, taps.empty() ? nullptr : taps.data(), shift ? 1 : 0,
-                                            gains.empty() ? nullptr : gains.data(), &d_h);
-        if (rc) {
-            const std::string msg = std::string("mi355_fengine_create: ") + mi355_strerror(rc) + ": " + mi355_last_error();
-            mi355_ctx_destroy(d_ctx);
-            if (rc == MI355_ERR_INVALID_ARG) throw std::invalid_argument(msg);
-            throw std::runtime_error(msg);
-        }
-    }
-    ~clFEngine_impl() override
-    {
-        mi355_fengine_destroy(d_h);
-        mi355_ctx_destroy(d_ctx);
+        d_ctx.open(openCLPlatformType, devSelector, platformId, devId, setDebug, chk_arg);
+        created(mi355_fengine_create(d_ctx, S, npol, F, P, taps.empty() ? nullptr : taps.data(), shift ? 1 : 0,
+                                     gains.empty() ? nullptr : gains.data(), d_h.adopt()),
+                "mi355_fengine_create");
     }
     void set_gains(const std::vector<float> &gains) override
     {
@@ -75,35 +57,35 @@ public:
             throw std::invalid_argument("clFEngine: set_gains() takes " + std::to_string((size_t)d_nin * d_nchan) + " values, got " +
                                         std::to_string(gains.size()));
         std::lock_guard<std::mutex> g(d_lock);
-        chk(mi355_fengine_set_gains(d_h, gains.data()), "mi355_fengine_set_gains");
+        chk_arg(mi355_fengine_set_gains(d_h, gains.data()), "mi355_fengine_set_gains");
     }
     void set_input_gain(int input, const std::vector<float> &gain) override
     {
         if (gain.size() != (size_t)d_nchan)
             throw std::invalid_argument("clFEngine: set_input_gain() takes " + std::to_string(d_nchan) + " values, got " + std::to_string(gain.size()));
         std::lock_guard<std::mutex> g(d_lock);
-        chk(mi355_fengine_set_input_gain(d_h, input, gain.data()), "mi355_fengine_set_input_gain");
+        chk_arg(mi355_fengine_set_input_gain(d_h, input, gain.data()), "mi355_fengine_set_input_gain");
     }
     std::vector<float> gains() const override
     {
         std::vector<float> g((size_t)d_nin * d_nchan);
-        chk(mi355_fengine_get_gains(d_h, g.data(), (long long)g.size()), "mi355_fengine_get_gains");
+        chk_arg(mi355_fengine_get_gains(d_h, g.data(), (long long)g.size()), "mi355_fengine_get_gains");
         return g;
     }
     std::vector<uint64_t> clips(bool reset) override
     {
         std::vector<unsigned long long> c((size_t)d_nin);
         std::lock_guard<std::mutex> g(d_lock);
-        chk(mi355_fengine_get_clips(d_h, c.data(), reset ? 1 : 0), "mi355_fengine_get_clips");
+        chk_arg(mi355_fengine_get_clips(d_h, c.data(), reset ? 1 : 0), "mi355_fengine_get_clips");
         return std::vector<uint64_t>(c.begin(), c.end());
     }
     long long frame_bytes() const override { return d_plan.frame_bytes; }
-    void set_generic(bool on) override { chk(mi355_fengine_set_generic(d_h, on ? 1 : 0), "mi355_fengine_set_generic"); }
+    void set_generic(bool on) override { chk_arg(mi355_fengine_set_generic(d_h, on ? 1 : 0), "mi355_fengine_set_generic"); }
     std::string route() const override { return mi355_fengine_route(d_h); }
     int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
     {
         std::lock_guard<std::mutex> g(d_lock);
-        chk(mi355_fengine_work(d_h, noutput_items, in.data(), out[0]), "mi355_fengine_work");
+        chk_arg(mi355_fengine_work(d_h, noutput_items, in.data(), out[0]), "mi355_fengine_work");
         return noutput_items;
     }
 };

@@ -4,7 +4,7 @@
 // the block the item lies in (the same bytes for all block_len items of a block, so that the stream stays sample-synchronous).  The
 // limits and the mask live in the library handle; the block keeps no stream state.
 #include <clenabled/clenabled.h>
-#include <mi355_clenabled.h>
+#include "block_base.h"
 
 #include <cstring>
 #include <mutex>
@@ -16,12 +16,6 @@ namespace gr {
 namespace clenabled {
 namespace {
 
-void chk(int rc, const char *what)
-{
-    if (rc == MI355_ERR_INVALID_ARG) throw std::invalid_argument(std::string(what) + ": " + mi355_last_error());
-    if (rc < 0) throw std::runtime_error(std::string(what) + ": " + mi355_strerror(rc) + ": " + mi355_last_error());
-}
-
 struct Plan {
     long long floats = 0, cflag_bytes = 0, tflag_bytes = 0;
 };
@@ -30,14 +24,12 @@ struct Plan {
 Plan plan(int R, int F, int Tb)
 {
     Plan p;
-    chk(mi355_fbclean_plan(R, F, Tb, &p.floats, &p.cflag_bytes, &p.tflag_bytes), "clFilterbankCleaner");
-    if (p.floats * 4 > 0x7fffffffll) throw std::invalid_argument("clFilterbankCleaner: a stream item of 2 GiB or more");
+    chk_arg(mi355_fbclean_plan(R, F, Tb, &p.floats, &p.cflag_bytes, &p.tflag_bytes), "clFilterbankCleaner");
+    check_stream_item("clFilterbankCleaner", {p.floats * 4});
     return p;
 }
 
-class clFilterbankCleaner_impl : public clFilterbankCleaner {
-    mi355_ctx *d_ctx = nullptr;
-    mi355_fbclean *d_h = nullptr;
+class clFilterbankCleaner_impl : public clFilterbankCleaner, BlockBase<mi355_fbclean, mi355_fbclean_destroy> {
     const Plan d_plan;
     const size_t d_channels;
     const int d_block_len;
@@ -55,30 +47,20 @@ public:
             throw std::invalid_argument("clFilterbankCleaner: the mask holds " + std::to_string(mask.size()) + " entries, the geometry has " +
                                         std::to_string(d_channels) + " channels");
         set_output_multiple(Tb);
-        chk(mi355_ctx_create(openCLPlatformType, devSelector, platformId, devId, setDebug ? 1 : 0, &d_ctx), "mi355_ctx_create");
-        const int rc = mi355_fbclean_create(d_ctx, R, F, Tb, nd, sk_lo, sk_hi, td, zero_dm ? 1 : 0, mask.empty() ? nullptr : mask.data(), &d_h);
-        if (rc) {
-            const std::string msg = std::string("mi355_fbclean_create: ") + mi355_strerror(rc) + ": " + mi355_last_error();
-            mi355_ctx_destroy(d_ctx);
-            if (rc == MI355_ERR_INVALID_ARG) throw std::invalid_argument(msg);
-            throw std::runtime_error(msg);
-        }
-    }
-    ~clFilterbankCleaner_impl() override
-    {
-        mi355_fbclean_destroy(d_h);
-        mi355_ctx_destroy(d_ctx);
+        d_ctx.open(openCLPlatformType, devSelector, platformId, devId, setDebug, chk_arg);
+        created(mi355_fbclean_create(d_ctx, R, F, Tb, nd, sk_lo, sk_hi, td, zero_dm ? 1 : 0, mask.empty() ? nullptr : mask.data(), d_h.adopt()),
+                "mi355_fbclean_create");
     }
     void set_limits(double nd, double sk_lo, double sk_hi, double td, bool zero_dm) override
     {
         std::lock_guard<std::mutex> g(d_lock);
-        chk(mi355_fbclean_set_limits(d_h, nd, sk_lo, sk_hi, td, zero_dm ? 1 : 0), "mi355_fbclean_set_limits");
+        chk_arg(mi355_fbclean_set_limits(d_h, nd, sk_lo, sk_hi, td, zero_dm ? 1 : 0), "mi355_fbclean_set_limits");
     }
     std::vector<double> limits() const override
     {
         std::vector<double> v(5);
         int z = 0;
-        chk(mi355_fbclean_get_limits(d_h, &v[0], &v[1], &v[2], &v[3], &z), "mi355_fbclean_get_limits");
+        chk_arg(mi355_fbclean_get_limits(d_h, &v[0], &v[1], &v[2], &v[3], &z), "mi355_fbclean_get_limits");
         v[4] = z;
         return v;
     }
@@ -88,16 +70,16 @@ public:
             throw std::invalid_argument("clFilterbankCleaner: set_mask() takes " + std::to_string(d_channels) + " entries, got " +
                                         std::to_string(mask.size()));
         std::lock_guard<std::mutex> g(d_lock);
-        chk(mi355_fbclean_set_mask(d_h, mask.data()), "mi355_fbclean_set_mask");
+        chk_arg(mi355_fbclean_set_mask(d_h, mask.data()), "mi355_fbclean_set_mask");
     }
     std::vector<uint8_t> mask() const override
     {
         std::vector<uint8_t> t(d_channels);
-        chk(mi355_fbclean_get_mask(d_h, t.data(), (long long)t.size()), "mi355_fbclean_get_mask");
+        chk_arg(mi355_fbclean_get_mask(d_h, t.data(), (long long)t.size()), "mi355_fbclean_get_mask");
         return t;
     }
     int block_len() const override { return d_block_len; }
-    void set_generic(bool on) override { chk(mi355_fbclean_set_generic(d_h, on ? 1 : 0), "mi355_fbclean_set_generic"); }
+    void set_generic(bool on) override { chk_arg(mi355_fbclean_set_generic(d_h, on ? 1 : 0), "mi355_fbclean_set_generic"); }
     std::string route() const override { return mi355_fbclean_route(d_h); }
     int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
     {
@@ -108,7 +90,7 @@ public:
         uint8_t *per_item = out.size() >= 3 ? (uint8_t *)out[2] : nullptr;
         const size_t cb = (size_t)d_plan.cflag_bytes, nblk = (size_t)(n / d_block_len);
         if (per_item) d_cflags.resize(nblk * cb);
-        chk(mi355_fbclean_work(d_h, n, in[0], out[0], per_item ? d_cflags.data() : nullptr, tflags, nullptr), "mi355_fbclean_work");
+        chk_arg(mi355_fbclean_work(d_h, n, in[0], out[0], per_item ? d_cflags.data() : nullptr, tflags, nullptr), "mi355_fbclean_work");
         if (per_item)
             for (size_t t = 0; t < (size_t)n; t++) memcpy(per_item + t * cb, d_cflags.data() + (t / (size_t)d_block_len) * cb, cb);
         return n;

@@ -3,7 +3,7 @@
 // history-prefixed input (n decimation + ntaps - 1 items, what the scheduler guarantees) and the output pointers as they come.  The
 // phase of every channel lives in the library handle; the message port "freq" retunes channel 0.
 #include <clenabled/clenabled.h>
-#include <mi355_clenabled.h>
+#include "block_base.h"
 
 #include <mutex>
 #include <stdexcept>
@@ -14,33 +14,15 @@ namespace gr {
 namespace clenabled {
 namespace {
 
-void chk(int rc, const char *what)
-{
-    if (rc == MI355_ERR_INVALID_ARG) throw std::invalid_argument(std::string(what) + ": " + mi355_last_error());
-    if (rc < 0) throw std::runtime_error(std::string(what) + ": " + mi355_strerror(rc) + ": " + mi355_last_error());
-}
-
 int streams(const std::vector<double> &freqs) { return freqs.empty() ? 1 : (int)freqs.size(); }
 
-class clFreqXlatingFIRFilter_impl : public clFreqXlatingFIRFilter {
-    mi355_ctx *d_ctx = nullptr;
-    mi355_xlate *d_h = nullptr;
+class clFreqXlatingFIRFilter_impl : public clFreqXlatingFIRFilter, BlockBase<mi355_xlate, mi355_xlate_destroy> {
     const int d_nch;
     const bool d_complex;
     std::mutex d_lock;
     bool d_updated = false;
 
-    // real taps: the real parts, and an imaginary part that is not zero is refused
-    std::vector<float> flat(const std::vector<gr_complex> &taps) const
-    {
-        std::vector<float> t;
-        for (const gr_complex &v : taps) {
-            t.push_back(v.real());
-            if (d_complex) t.push_back(v.imag());
-            else if (v.imag() != 0.0f) throw std::invalid_argument("clFreqXlatingFIRFilter: complex taps for a block made with real taps");
-        }
-        return t;
-    }
+    std::vector<float> flat(const std::vector<gr_complex> &taps) const { return clenabled::flat(taps, d_complex, "clFreqXlatingFIRFilter"); }
 
 public:
     clFreqXlatingFIRFilter_impl(int openCLPlatformType, int devSelector, int platformId, int devId, int decimation, const std::vector<gr_complex> &taps,
@@ -51,51 +33,31 @@ public:
           d_nch((int)center_freqs.size()), d_complex(complex_taps)
     {
         // argument errors before any device work
-        chk(mi355_xlate_plan(decimation, (int)taps.size(), 0, nullptr, nullptr), "clFreqXlatingFIRFilter");
+        chk_arg(mi355_xlate_plan(decimation, (int)taps.size(), 0, nullptr, nullptr), "clFreqXlatingFIRFilter");
         if (center_freqs.empty()) throw std::invalid_argument("clFreqXlatingFIRFilter: at least one centre frequency");
         const std::vector<float> t = flat(taps);
-        chk(mi355_ctx_create(openCLPlatformType, devSelector, platformId, devId, setDebug ? 1 : 0, &d_ctx), "mi355_ctx_create");
-        const int rc = mi355_xlate_create(d_ctx, decimation, t.data(), (int)taps.size(), complex_taps ? 1 : 0, sampling_freq, center_freqs.data(),
-                                          d_nch, use_time ? 1 : 0, &d_h);
-        if (rc) {
-            const std::string msg = std::string("mi355_xlate_create: ") + mi355_strerror(rc) + ": " + mi355_last_error();
-            mi355_ctx_destroy(d_ctx);
-            if (rc == MI355_ERR_INVALID_ARG) throw std::invalid_argument(msg);
-            throw std::runtime_error(msg);
-        }
+        d_ctx.open(openCLPlatformType, devSelector, platformId, devId, setDebug, chk_arg);
+        created(mi355_xlate_create(d_ctx, decimation, t.data(), (int)taps.size(), complex_taps ? 1 : 0, sampling_freq, center_freqs.data(), d_nch,
+                                   use_time ? 1 : 0, d_h.adopt()),
+                "mi355_xlate_create");
         set_history((unsigned)taps.size());
-#ifdef MI355_WITH_GNURADIO
-        message_port_register_in(pmt::mp("freq"));
-        set_msg_handler(pmt::mp("freq"), [this](pmt::pmt_t msg) {
-            if (!pmt::is_pair(msg)) return;
-            const pmt::pmt_t v = pmt::cdr(msg);
-            if (pmt::is_real(v)) set_center_freq(pmt::to_double(v), 0);
-        });
-#else
-        message_port_register_in("freq");
-        set_double_handler("freq", [this](double f) { set_center_freq(f, 0); });
-#endif
-    }
-    ~clFreqXlatingFIRFilter_impl() override
-    {
-        mi355_xlate_destroy(d_h);
-        mi355_ctx_destroy(d_ctx);
+        sched::register_in_double(this, "freq", [this](double f) { set_center_freq(f, 0); });
     }
     void set_center_freq(double center_freq, int channel) override
     {
-        chk(mi355_xlate_set_center_freq(d_h, channel, center_freq), "mi355_xlate_set_center_freq");
+        chk_arg(mi355_xlate_set_center_freq(d_h, channel, center_freq), "mi355_xlate_set_center_freq");
     }
     double center_freq(int channel) const override
     {
         double f = 0.0;
-        chk(mi355_xlate_get_center_freq(d_h, channel, &f), "mi355_xlate_get_center_freq");
+        chk_arg(mi355_xlate_get_center_freq(d_h, channel, &f), "mi355_xlate_get_center_freq");
         return f;
     }
     std::vector<gr_complex> taps() const override
     {
         const int n = mi355_xlate_ntaps(d_h);
         std::vector<float> t((size_t)n * (d_complex ? 2 : 1));
-        chk(mi355_xlate_get_taps(d_h, t.data(), n), "mi355_xlate_get_taps");
+        chk_arg(mi355_xlate_get_taps(d_h, t.data(), n), "mi355_xlate_get_taps");
         std::vector<gr_complex> out((size_t)n);
         for (int k = 0; k < n; k++) out[k] = d_complex ? gr_complex(t[2 * k], t[2 * k + 1]) : gr_complex(t[k], 0.0f);
         return out;
@@ -104,12 +66,12 @@ public:
     {
         const std::vector<float> t = flat(taps);
         std::lock_guard<std::mutex> g(d_lock);
-        chk(mi355_xlate_set_taps(d_h, t.data(), (int)taps.size()), "mi355_xlate_set_taps");
+        chk_arg(mi355_xlate_set_taps(d_h, t.data(), (int)taps.size()), "mi355_xlate_set_taps");
         d_updated = true;
     }
     int num_channels() const override { return d_nch; }
-    void skip(long long noutputs) override { chk(mi355_xlate_skip(d_h, noutputs), "mi355_xlate_skip"); }
-    void set_generic(bool on) override { chk(mi355_xlate_set_generic(d_h, on ? 1 : 0), "mi355_xlate_set_generic"); }
+    void skip(long long noutputs) override { chk_arg(mi355_xlate_skip(d_h, noutputs), "mi355_xlate_skip"); }
+    void set_generic(bool on) override { chk_arg(mi355_xlate_set_generic(d_h, on ? 1 : 0), "mi355_xlate_set_generic"); }
     std::string route() const override { return mi355_xlate_route(d_h); }
     int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
     {
@@ -120,7 +82,7 @@ public:
             return 0;
         }
         if ((int)out.size() < d_nch) throw std::logic_error("clFreqXlatingFIRFilter: fewer output streams than centre frequencies");
-        chk(mi355_xlate_work(d_h, noutput_items, in[0], out.data()), "mi355_xlate_work");
+        chk_arg(mi355_xlate_work(d_h, noutput_items, in[0], out.data()), "mi355_xlate_work");
         return noutput_items;
     }
 };

@@ -2,7 +2,7 @@
 // nmap items in, num_channels items out, (taps_per_arm - 1) frames of history in front; what a call reads and writes comes from the
 // library's own bookkeeping (mi355_synth_plan), so the block and the kernels cannot disagree about a frame.
 #include <clenabled/clenabled.h>
-#include <mi355_clenabled.h>
+#include "block_base.h"
 
 #include <stdexcept>
 #include <string>
@@ -12,14 +12,7 @@ namespace gr {
 namespace clenabled {
 namespace {
 
-void chk(int rc, const char *what)
-{
-    if (rc < 0) throw std::runtime_error(std::string(what) + ": " + mi355_strerror(rc) + ": " + mi355_last_error());
-}
-
-class clPolyphaseSynthesizer_impl : public clPolyphaseSynthesizer {
-    mi355_ctx *d_ctx = nullptr;
-    mi355_synth *d_h = nullptr;
+class clPolyphaseSynthesizer_impl : public clPolyphaseSynthesizer, BlockBase<mi355_synth, mi355_synth_destroy> {
     const int d_M, d_nmap;
 
     void apply_history() { set_history((unsigned)((mi355_synth_taps_per_arm(d_h) - 1) * d_nmap + 1)); }
@@ -33,34 +26,24 @@ public:
         // argument errors before any device work
         const int rc = mi355_synth_plan((int)taps.size(), num_channels, d_nmap, 0, nullptr, nullptr, nullptr);
         if (rc == MI355_ERR_INVALID_ARG) throw std::invalid_argument(std::string("clPolyphaseSynthesizer: ") + mi355_last_error());
-        chk(rc, "mi355_synth_plan");
-        chk(mi355_ctx_create(openCLPlatformType, devSelector, platformId, devId, setDebug ? 1 : 0, &d_ctx), "mi355_ctx_create");
-        const int rc2 = mi355_synth_create(d_ctx, taps.data(), (int)taps.size(), num_channels, ch_map.empty() ? nullptr : ch_map.data(), d_nmap, &d_h);
-        if (rc2) {
-            const std::string msg = std::string("mi355_synth_create: ") + mi355_strerror(rc2) + ": " + mi355_last_error();
-            mi355_ctx_destroy(d_ctx);
-            if (rc2 == MI355_ERR_INVALID_ARG) throw std::invalid_argument(msg);
-            throw std::runtime_error(msg);
-        }
+        chk_runtime(rc, "mi355_synth_plan");
+        d_ctx.open(openCLPlatformType, devSelector, platformId, devId, setDebug);
+        created(mi355_synth_create(d_ctx, taps.data(), (int)taps.size(), num_channels, ch_map.empty() ? nullptr : ch_map.data(), d_nmap, d_h.adopt()),
+                "mi355_synth_create");
         apply_history();
         set_relative_rate((uint64_t)d_M, (uint64_t)d_nmap);
         set_output_multiple(d_M);
-    }
-    ~clPolyphaseSynthesizer_impl() override
-    {
-        mi355_synth_destroy(d_h);
-        mi355_ctx_destroy(d_ctx);
     }
     std::vector<float> taps() const override
     {
         const int n = mi355_synth_ntaps(d_h);
         std::vector<float> t((size_t)n);
-        chk(mi355_synth_get_taps(d_h, t.data(), n), "mi355_synth_get_taps");
+        chk_runtime(mi355_synth_get_taps(d_h, t.data(), n), "mi355_synth_get_taps");
         return t;
     }
     void set_taps(const std::vector<float> &taps) override
     {
-        chk(mi355_synth_set_taps(d_h, taps.data(), (int)taps.size()), "mi355_synth_set_taps");
+        chk_runtime(mi355_synth_set_taps(d_h, taps.data(), (int)taps.size()), "mi355_synth_set_taps");
         apply_history();
     }
     int taps_per_arm() const override { return mi355_synth_taps_per_arm(d_h); }
@@ -70,7 +53,7 @@ public:
     void forecast(int noutput_items, gr_vector_int &req) override
     {
         long long nin = 0;
-        chk(mi355_synth_plan(mi355_synth_ntaps(d_h), d_M, d_nmap, noutput_items / d_M, nullptr, &nin, nullptr), "mi355_synth_plan");
+        chk_runtime(mi355_synth_plan(mi355_synth_ntaps(d_h), d_M, d_nmap, noutput_items / d_M, nullptr, &nin, nullptr), "mi355_synth_plan");
         for (auto &r : req) r = (int)nin;
     }
     // as many whole frames as the offered input and the output room allow: one library call, consume_each(frames x nmap)
@@ -79,7 +62,7 @@ public:
         const long long hist = (long long)(mi355_synth_taps_per_arm(d_h) - 1) * d_nmap;
         long long n = ninput_items[0] >= hist ? (ninput_items[0] - hist) / d_nmap : 0;
         if (n > noutput_items / d_M) n = noutput_items / d_M;
-        chk(mi355_synth_work(d_h, n, in[0], out[0]), "mi355_synth_work");
+        chk_runtime(mi355_synth_work(d_h, n, in[0], out[0]), "mi355_synth_work");
         consume_each((int)(n * d_nmap));
         return (int)(n * d_M);
     }

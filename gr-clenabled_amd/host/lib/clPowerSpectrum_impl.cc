@@ -4,7 +4,7 @@
 // items consumed reach past the last frame read: the block then waits until the scheduler offers all navg hop items of a spectrum, so
 // that it never consumes more than it was offered (the library is still handed, and reads, only (S navg - 1) hop + fft_size items).
 #include <clenabled/clenabled.h>
-#include <mi355_clenabled.h>
+#include "block_base.h"
 
 #include <stdexcept>
 #include <string>
@@ -14,14 +14,7 @@ namespace gr {
 namespace clenabled {
 namespace {
 
-void chk(int rc, const char *what)
-{
-    if (rc < 0) throw std::runtime_error(std::string(what) + ": " + mi355_strerror(rc) + ": " + mi355_last_error());
-}
-
-class clPowerSpectrum_impl : public clPowerSpectrum {
-    mi355_ctx *d_ctx = nullptr;
-    mi355_pspec *d_h = nullptr;
+class clPowerSpectrum_impl : public clPowerSpectrum, BlockBase<mi355_pspec, mi355_pspec_destroy> {
     const int d_N, d_K, d_H;
 
 public:
@@ -34,40 +27,30 @@ public:
         // argument errors before any device work
         const int rc = mi355_pspec_plan(d_N, d_K, d_H, 0, nullptr, nullptr);
         if (rc == MI355_ERR_INVALID_ARG) throw std::invalid_argument(std::string("clPowerSpectrum: ") + mi355_last_error());
-        chk(rc, "mi355_pspec_plan");
+        chk_runtime(rc, "mi355_pspec_plan");
         if (!window.empty() && (int)window.size() != d_N) throw std::invalid_argument("clPowerSpectrum: window not the same length as fft_size");
-        chk(mi355_ctx_create(openCLPlatformType, devSelector, platformId, devId, setDebug ? 1 : 0, &d_ctx), "mi355_ctx_create");
-        const int rc2 = mi355_pspec_create(d_ctx, d_N, window.empty() ? nullptr : window.data(), (int)window.size(), d_K, d_H, shift ? 1 : 0,
-                                           log_output ? 1 : 0, scale, &d_h);
-        if (rc2) {
-            const std::string msg = std::string("mi355_pspec_create: ") + mi355_strerror(rc2) + ": " + mi355_last_error();
-            mi355_ctx_destroy(d_ctx);
-            if (rc2 == MI355_ERR_INVALID_ARG) throw std::invalid_argument(msg);
-            throw std::runtime_error(msg);
-        }
+        d_ctx.open(openCLPlatformType, devSelector, platformId, devId, setDebug);
+        created(mi355_pspec_create(d_ctx, d_N, window.empty() ? nullptr : window.data(), (int)window.size(), d_K, d_H, shift ? 1 : 0,
+                                   log_output ? 1 : 0, scale, d_h.adopt()),
+                "mi355_pspec_create");
         set_history((unsigned)((d_N > d_H ? d_N - d_H : 0) + 1));
         set_relative_rate((uint64_t)1, (uint64_t)d_K * (uint64_t)d_H);
-    }
-    ~clPowerSpectrum_impl() override
-    {
-        mi355_pspec_destroy(d_h);
-        mi355_ctx_destroy(d_ctx);
     }
     int fft_size() const override { return d_N; }
     int navg() const override { return d_K; }
     int hop() const override { return d_H; }
-    void set_scale(float scale) override { chk(mi355_pspec_set_scale(d_h, scale), "mi355_pspec_set_scale"); }
+    void set_scale(float scale) override { chk_runtime(mi355_pspec_set_scale(d_h, scale), "mi355_pspec_set_scale"); }
     void set_window(const std::vector<float> &window) override
     {
         if (!window.empty() && (int)window.size() != d_N) throw std::invalid_argument("clPowerSpectrum: window not the same length as fft_size");
-        chk(mi355_pspec_set_window(d_h, window.empty() ? nullptr : window.data(), (int)window.size()), "mi355_pspec_set_window");
+        chk_runtime(mi355_pspec_set_window(d_h, window.empty() ? nullptr : window.data(), (int)window.size()), "mi355_pspec_set_window");
     }
-    void set_generic(bool on) override { chk(mi355_pspec_set_generic(d_h, on ? 1 : 0), "mi355_pspec_set_generic"); }
+    void set_generic(bool on) override { chk_runtime(mi355_pspec_set_generic(d_h, on ? 1 : 0), "mi355_pspec_set_generic"); }
     std::string route() const override { return mi355_pspec_route(d_h); }
     void forecast(int noutput_items, gr_vector_int &req) override
     {
         long long nin = 0;
-        chk(mi355_pspec_plan(d_N, d_K, d_H, noutput_items, &nin, nullptr), "mi355_pspec_plan");
+        chk_runtime(mi355_pspec_plan(d_N, d_K, d_H, noutput_items, &nin, nullptr), "mi355_pspec_plan");
         const long long used = (long long)noutput_items * d_K * d_H;  // what general_work() will consume: more than it reads when hop > fft_size
         for (auto &r : req) r = (int)(nin > used ? nin : used);
     }
@@ -78,7 +61,7 @@ public:
         long long n = have >= d_N ? ((have - d_N) / d_H + 1) / d_K : 0;  // frames that fit, in whole spectra
         if (d_H > d_N) n = have / ((long long)d_K * d_H);                // ... and whose skipped items were offered too
         if (n > noutput_items) n = noutput_items;
-        chk(mi355_pspec_work(d_h, n, in[0], out[0]), "mi355_pspec_work");
+        chk_runtime(mi355_pspec_work(d_h, n, in[0], out[0]), "mi355_pspec_work");
         consume_each((int)(n * d_K * d_H));
         return (int)n;
     }

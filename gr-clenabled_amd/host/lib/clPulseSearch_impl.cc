@@ -3,7 +3,7 @@
 // history 2^(K-1), so a call for n output items hands the library n block_len samples with 2^(K-1) - 1 samples of look-ahead behind
 // them.  The statistics live in the library handle.  Candidates are not exposed here: there is no message port.
 #include <clenabled/clenabled.h>
-#include <mi355_clenabled.h>
+#include "block_base.h"
 
 #include <mutex>
 #include <stdexcept>
@@ -14,12 +14,6 @@ namespace gr {
 namespace clenabled {
 namespace {
 
-void chk(int rc, const char *what)
-{
-    if (rc == MI355_ERR_INVALID_ARG) throw std::invalid_argument(std::string(what) + ": " + mi355_last_error());
-    if (rc < 0) throw std::runtime_error(std::string(what) + ": " + mi355_strerror(rc) + ": " + mi355_last_error());
-}
-
 struct Plan {
     long long in_floats = 0, history = 0, peaks = 0;
 };
@@ -28,13 +22,11 @@ struct Plan {
 Plan plan(int R, int D, int K, int Tb)
 {
     Plan p;
-    chk(mi355_psearch_plan(R, D, K, Tb, MI355_PSEARCH_TIME_MAJOR, &p.in_floats, &p.history, &p.peaks), "clPulseSearch");
+    chk_arg(mi355_psearch_plan(R, D, K, Tb, MI355_PSEARCH_TIME_MAJOR, &p.in_floats, &p.history, &p.peaks), "clPulseSearch");
     return p;
 }
 
-class clPulseSearch_impl : public clPulseSearch {
-    mi355_ctx *d_ctx = nullptr;
-    mi355_psearch *d_h = nullptr;
+class clPulseSearch_impl : public clPulseSearch, BlockBase<mi355_psearch, mi355_psearch_destroy> {
     const Plan d_plan;
     const size_t d_series;
     const int d_block_len;
@@ -43,7 +35,7 @@ class clPulseSearch_impl : public clPulseSearch {
     std::vector<float> stats(bool second) const
     {
         std::vector<float> m(d_series), g(d_series);
-        chk(mi355_psearch_get_stats(d_h, m.data(), g.data(), (long long)d_series), "mi355_psearch_get_stats");
+        chk_arg(mi355_psearch_get_stats(d_h, m.data(), g.data(), (long long)d_series), "mi355_psearch_get_stats");
         return second ? g : m;
     }
 
@@ -58,20 +50,10 @@ public:
             throw std::invalid_argument("clPulseSearch: mean and inv_sigma hold " + std::to_string(mean.size()) + " and " +
                                         std::to_string(inv_sigma.size()) + " entries, the geometry has " + std::to_string(d_series) + " series");
         set_history((unsigned)p.history + 1);
-        chk(mi355_ctx_create(openCLPlatformType, devSelector, platformId, devId, setDebug ? 1 : 0, &d_ctx), "mi355_ctx_create");
-        const int rc = mi355_psearch_create(d_ctx, R, D, K, Tb, MI355_PSEARCH_TIME_MAJOR, mean.empty() ? nullptr : mean.data(),
-                                            inv_sigma.empty() ? nullptr : inv_sigma.data(), &d_h);
-        if (rc) {
-            const std::string msg = std::string("mi355_psearch_create: ") + mi355_strerror(rc) + ": " + mi355_last_error();
-            mi355_ctx_destroy(d_ctx);
-            if (rc == MI355_ERR_INVALID_ARG) throw std::invalid_argument(msg);
-            throw std::runtime_error(msg);
-        }
-    }
-    ~clPulseSearch_impl() override
-    {
-        mi355_psearch_destroy(d_h);
-        mi355_ctx_destroy(d_ctx);
+        d_ctx.open(openCLPlatformType, devSelector, platformId, devId, setDebug, chk_arg);
+        created(mi355_psearch_create(d_ctx, R, D, K, Tb, MI355_PSEARCH_TIME_MAJOR, mean.empty() ? nullptr : mean.data(),
+                                     inv_sigma.empty() ? nullptr : inv_sigma.data(), d_h.adopt()),
+                "mi355_psearch_create");
     }
     void set_stats(const std::vector<float> &mean, const std::vector<float> &inv_sigma) override
     {
@@ -79,17 +61,17 @@ public:
             throw std::invalid_argument("clPulseSearch: set_stats() takes " + std::to_string(d_series) + " entries each, got " +
                                         std::to_string(mean.size()) + " and " + std::to_string(inv_sigma.size()));
         std::lock_guard<std::mutex> g(d_lock);
-        chk(mi355_psearch_set_stats(d_h, mean.data(), inv_sigma.data()), "mi355_psearch_set_stats");
+        chk_arg(mi355_psearch_set_stats(d_h, mean.data(), inv_sigma.data()), "mi355_psearch_set_stats");
     }
     std::vector<float> mean() const override { return stats(false); }
     std::vector<float> inv_sigma() const override { return stats(true); }
     int lookahead() const override { return (int)d_plan.history; }
-    void set_generic(bool on) override { chk(mi355_psearch_set_generic(d_h, on ? 1 : 0), "mi355_psearch_set_generic"); }
+    void set_generic(bool on) override { chk_arg(mi355_psearch_set_generic(d_h, on ? 1 : 0), "mi355_psearch_set_generic"); }
     std::string route() const override { return mi355_psearch_route(d_h); }
     int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
     {
         std::lock_guard<std::mutex> g(d_lock);
-        chk(mi355_psearch_work(d_h, (long long)noutput_items * d_block_len, in[0], 0, out[0], nullptr, 0, nullptr), "mi355_psearch_work");
+        chk_arg(mi355_psearch_work(d_h, (long long)noutput_items * d_block_len, in[0], 0, out[0], nullptr, 0, nullptr), "mi355_psearch_work");
         return noutput_items;
     }
 };

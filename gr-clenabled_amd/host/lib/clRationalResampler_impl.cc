@@ -2,7 +2,7 @@
 // history nt = ceil(ntaps / L), relative rate L / M, forecast() and the number of outputs a call may make both come from the
 // library's own bookkeeping (mi355_resampler_plan / _noutput_for), so the block and the kernels cannot disagree about a window.
 #include <clenabled/clenabled.h>
-#include <mi355_clenabled.h>
+#include "block_base.h"
 
 #include <stdexcept>
 #include <string>
@@ -12,34 +12,17 @@ namespace gr {
 namespace clenabled {
 namespace {
 
-void chk(int rc, const char *what)
-{
-    if (rc < 0) throw std::runtime_error(std::string(what) + ": " + mi355_strerror(rc) + ": " + mi355_last_error());
-}
-
-class clRationalResampler_impl : public clRationalResampler {
-    mi355_ctx *d_ctx = nullptr;
-    mi355_resampler *d_h = nullptr;
+class clRationalResampler_impl : public clRationalResampler, BlockBase<mi355_resampler, mi355_resampler_destroy> {
     const int d_interp, d_decim;
     const bool d_complex;
 
     int phase() const
     {
         int c = 0;
-        chk(mi355_resampler_get_phase(d_h, &c), "mi355_resampler_get_phase");
+        chk_runtime(mi355_resampler_get_phase(d_h, &c), "mi355_resampler_get_phase");
         return c;
     }
-    // real taps: the real parts, and an imaginary part that is not zero is refused
-    std::vector<float> flat(const std::vector<gr_complex> &taps) const
-    {
-        std::vector<float> t;
-        for (const gr_complex &v : taps) {
-            t.push_back(v.real());
-            if (d_complex) t.push_back(v.imag());
-            else if (v.imag() != 0.0f) throw std::invalid_argument("clRationalResampler: complex taps for a block made with real taps");
-        }
-        return t;
-    }
+    std::vector<float> flat(const std::vector<gr_complex> &taps) const { return clenabled::flat(taps, d_complex, "clRationalResampler"); }
 
 public:
     clRationalResampler_impl(int openCLPlatformType, int devSelector, int platformId, int devId, int interpolation, int decimation,
@@ -50,29 +33,20 @@ public:
         int nt = 0;  // argument errors before any device work
         const int rc = mi355_resampler_plan(interpolation, decimation, (int)taps.size(), 0, 0, &nt, nullptr, nullptr, nullptr);
         if (rc == MI355_ERR_INVALID_ARG) throw std::invalid_argument(std::string("clRationalResampler: ") + mi355_last_error());
-        chk(rc, "mi355_resampler_plan");
+        chk_runtime(rc, "mi355_resampler_plan");
         const std::vector<float> t = flat(taps);
-        chk(mi355_ctx_create(openCLPlatformType, devSelector, platformId, devId, setDebug ? 1 : 0, &d_ctx), "mi355_ctx_create");
-        const int rc2 = mi355_resampler_create(d_ctx, interpolation, decimation, t.data(), (int)taps.size(), complex_taps ? 1 : 0, &d_h);
-        if (rc2) {
-            const std::string msg = std::string("mi355_resampler_create: ") + mi355_strerror(rc2) + ": " + mi355_last_error();
-            mi355_ctx_destroy(d_ctx);
-            throw std::runtime_error(msg);
-        }
+        d_ctx.open(openCLPlatformType, devSelector, platformId, devId, setDebug);
+        created(mi355_resampler_create(d_ctx, interpolation, decimation, t.data(), (int)taps.size(), complex_taps ? 1 : 0, d_h.adopt()),
+                "mi355_resampler_create", ArgIs::runtime_error);
         set_history(nt);
         set_relative_rate((uint64_t)interpolation, (uint64_t)decimation);
         set_output_multiple(1);
-    }
-    ~clRationalResampler_impl() override
-    {
-        mi355_resampler_destroy(d_h);
-        mi355_ctx_destroy(d_ctx);
     }
     std::vector<gr_complex> taps() const override
     {
         const int n = mi355_resampler_ntaps(d_h);
         std::vector<float> t((size_t)n * (d_complex ? 2 : 1));
-        chk(mi355_resampler_get_taps(d_h, t.data(), n), "mi355_resampler_get_taps");
+        chk_runtime(mi355_resampler_get_taps(d_h, t.data(), n), "mi355_resampler_get_taps");
         std::vector<gr_complex> out((size_t)n);
         for (int k = 0; k < n; k++) out[k] = d_complex ? gr_complex(t[2 * k], t[2 * k + 1]) : gr_complex(t[k], 0.0f);
         return out;
@@ -80,7 +54,7 @@ public:
     void set_taps(const std::vector<gr_complex> &taps) override
     {
         const std::vector<float> t = flat(taps);
-        chk(mi355_resampler_set_taps(d_h, t.data(), (int)taps.size()), "mi355_resampler_set_taps");
+        chk_runtime(mi355_resampler_set_taps(d_h, t.data(), (int)taps.size()), "mi355_resampler_set_taps");
         set_history(mi355_resampler_history(d_h));  // the phase is kept
     }
     int interpolation() const override { return d_interp; }
@@ -88,18 +62,18 @@ public:
     void forecast(int noutput_items, gr_vector_int &req) override
     {
         long long needed = 0;
-        chk(mi355_resampler_plan(d_interp, d_decim, mi355_resampler_ntaps(d_h), phase(), noutput_items, nullptr, nullptr, &needed, nullptr),
-            "mi355_resampler_plan");
+        chk_runtime(mi355_resampler_plan(d_interp, d_decim, mi355_resampler_ntaps(d_h), phase(), noutput_items, nullptr, nullptr, &needed, nullptr),
+                    "mi355_resampler_plan");
         for (auto &r : req) r = (int)needed;
     }
     // as many outputs as the offered input allows, at most noutput_items: one library call, consume_each(what it consumed)
     int general_work(int noutput_items, gr_vector_int &ninput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
     {
         long long n = mi355_resampler_noutput_for(d_interp, d_decim, mi355_resampler_ntaps(d_h), phase(), ninput_items[0]);
-        if (n < 0) chk((int)n, "mi355_resampler_noutput_for");
+        if (n < 0) chk_runtime((int)n, "mi355_resampler_noutput_for");
         if (n > noutput_items) n = noutput_items;
         long long consumed = 0;
-        chk(mi355_resampler_work(d_h, n, in[0], out[0], &consumed), "mi355_resampler_work");
+        chk_runtime(mi355_resampler_work(d_h, n, in[0], out[0], &consumed), "mi355_resampler_work");
         consume_each((int)consumed);
         return (int)n;
     }

@@ -3,7 +3,7 @@
 // submit-and-return with the previous result published when the next frame is accepted; the handle's stream stands in for the
 // reference's worker thread.
 #include <clenabled/clenabled.h>
-#include <mi355_clenabled.h>
+#include "block_base.h"
 
 #include <mutex>
 #include <stdexcept>
@@ -14,14 +14,7 @@ namespace gr {
 namespace clenabled {
 namespace {
 
-void chk(int rc, const char *what)
-{
-    if (rc < 0) throw std::runtime_error(std::string(what) + ": " + mi355_strerror(rc) + ": " + mi355_last_error());
-}
-
-class clXCorrelate_impl : public clXCorrelate {
-    mi355_ctx *d_ctx = nullptr;
-    mi355_xcorr_td *d_h = nullptr;
+class clXCorrelate_impl : public clXCorrelate, BlockBase<mi355_xcorr_td, mi355_xcorr_td_destroy> {
     const int d_num_inputs, d_signal_length, d_decim_frames;
     const bool d_async;
     int cur_frame_counter = 1;   // :708
@@ -39,22 +32,7 @@ class clXCorrelate_impl : public clXCorrelate {
         }
         return true;
     }
-    void publish()  // :1594-1600
-    {
-#ifdef MI355_WITH_GNURADIO
-        pmt::pmt_t meta = pmt::make_dict();
-        meta = pmt::dict_add(meta, pmt::mp("corrvect"), pmt::init_f32vector(d_corr.size(), d_corr.data()));
-        meta = pmt::dict_add(meta, pmt::mp("corrective_lags"), pmt::init_s32vector(d_lags.size(), d_lags.data()));
-        message_port_pub(pmt::mp("corr"), pmt::cons(meta, pmt::PMT_NIL));
-#else
-        gr::shim_message m;
-        m.port = "corr";
-        m.key = "corrvect";
-        m.f32 = d_corr;
-        m.s32 = d_lags;
-        shim_publish(std::move(m));
-#endif
-    }
+    void publish() { sched::publish_corr_pdu(this, "corr", d_corr, d_lags); }  // :1594-1600
 
 public:
     clXCorrelate_impl(int openCLPlatformType, int devSelector, int platformId, int devId, bool setDebug, int num_inputs,
@@ -63,24 +41,16 @@ public:
           d_num_inputs(num_inputs), d_signal_length(signal_length), d_decim_frames(decim_frames), d_async(async),
           d_corr(num_inputs > 1 ? num_inputs - 1 : 1), d_lags(num_inputs > 1 ? num_inputs - 1 : 1)
     {
-        chk(mi355_ctx_create(openCLPlatformType, devSelector, platformId, devId, setDebug ? 1 : 0, &d_ctx), "mi355_ctx_create");
-        const int rc = mi355_xcorr_td_create(d_ctx, num_inputs, signal_length, data_type, data_size, max_search_index, &d_h);
-        if (rc) {
-            const std::string msg = std::string("mi355_xcorr_td_create: ") + mi355_strerror(rc) + ": " + mi355_last_error();
-            mi355_ctx_destroy(d_ctx);
-            throw std::runtime_error(msg);  // (the reference exit(1)s)
-        }
+        d_ctx.open(openCLPlatformType, devSelector, platformId, devId, setDebug);
+        created(mi355_xcorr_td_create(d_ctx, num_inputs, signal_length, data_type, data_size, max_search_index, d_h.adopt()), "mi355_xcorr_td_create",
+                ArgIs::runtime_error);  // (the reference exit(1)s)
         set_output_multiple(signal_length);  // :839
         sched::register_out(this, "corr");
     }
-    ~clXCorrelate_impl() override
-    {
-        mi355_xcorr_td_destroy(d_h);  // a result still pending is dropped, as at the reference's stop()
-        mi355_ctx_destroy(d_ctx);
-    }
+    // (at destruction a result still pending is dropped, as at the reference's stop())
     int max_shift() const override { return mi355_xcorr_td_max_shift(d_h); }
     int signal_length() const override { return d_signal_length; }
-    void wait() override { chk(mi355_xcorr_td_wait(d_h), "mi355_xcorr_td_wait"); }
+    void wait() override { chk_runtime(mi355_xcorr_td_wait(d_h), "mi355_xcorr_td_wait"); }
 
     int work(int noutput_items, gr_vector_const_void_star &input_items, gr_vector_void_star &) override
     {
@@ -89,13 +59,13 @@ public:
         std::lock_guard<std::mutex> guard(d_mutex);
         if (!d_async) {
             if (!take_frame()) return d_signal_length;
-            chk(mi355_xcorr_td_work(d_h, input_items.data(), d_corr.data(), d_lags.data()), "mi355_xcorr_td_work");
+            chk_runtime(mi355_xcorr_td_work(d_h, input_items.data(), d_corr.data(), d_lags.data()), "mi355_xcorr_td_work");
             publish();
             return d_signal_length;
         }
         if (d_pending) {
             const int r = mi355_xcorr_td_poll(d_h, d_corr.data(), d_lags.data());
-            chk(r, "mi355_xcorr_td_poll");
+            chk_runtime(r, "mi355_xcorr_td_poll");
             if (r == 0) return d_signal_length;  // still running: the frame passes through, uncounted
             d_pending = false;
             d_have_result = true;
@@ -105,7 +75,7 @@ public:
             publish();
             d_have_result = false;
         }
-        chk(mi355_xcorr_td_submit(d_h, input_items.data()), "mi355_xcorr_td_submit");
+        chk_runtime(mi355_xcorr_td_submit(d_h, input_items.data()), "mi355_xcorr_td_submit");
         d_pending = true;
         return d_signal_length;
     }

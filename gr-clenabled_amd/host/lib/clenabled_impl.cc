@@ -1,97 +1,49 @@
 // _impl classes of the hot-path blocks: every work() is a call into the C ABI (mi355_clenabled.h).
 // Structure follows the reference's lib/cl*_impl.cc with the GRCLBase base class replaced by
-// MI355Base; constructor-time errors throw the same exception types as the reference.
+// BlockBase (block_base.h); constructor-time errors throw the same exception types as the reference.
 #include <clenabled/clenabled.h>
-#include <mi355_clenabled.h>
-
-#include <cstdio>
-#include <mutex>
-#include <stdexcept>
+#include "block_base.h"
 
 namespace gr {
 namespace clenabled {
 
 namespace {
-// The library's diagnostics (mi355_set_log_callback) go where the reference's go: GNU Radio's logger (GR_LOG_INFO / GR_LOG_ERROR,
-// lib/clXEngine_impl.cc:107,137,257).  Stand-alone build: stderr, one "clenabled :level: text" line each, like the logger's format.
-void log_sink(void *, int level, const char *message)
+size_t dsize(int idataType)
 {
-#ifdef MI355_WITH_GNURADIO
-    // (configure_default_loggers + the GR_LOG_* macros exist in 3.9's log4cpp logger and in 3.10's spdlog one alike)
-    static gr::logger_ptr logger, debug_logger;
-    static const bool configured = gr::configure_default_loggers(logger, debug_logger, "clenabled");
-    (void)configured;
-    const std::string text(message);
-    switch (level) {
-    case MI355_LOG_DEBUG: GR_LOG_DEBUG(debug_logger, text); break;
-    case MI355_LOG_INFO: GR_LOG_INFO(logger, text); break;
-    case MI355_LOG_WARN: GR_LOG_WARN(logger, text); break;
-    default: GR_LOG_ERROR(logger, text); break;
+    switch (idataType) {  // lib/clMathOp_impl.cc:35-47
+    case DTYPE_COMPLEX: return sizeof(gr_complex);
+    case DTYPE_INT: return sizeof(int);
+    default: return sizeof(float);
     }
-#else
-    static const char *const names[] = {"debug", "info", "warning", "error"};
-    fprintf(stderr, "clenabled :%s: %s\n", names[level < 0 ? 0 : level > 3 ? 3 : level], message);
-#endif
 }
 
-// stands where "public GRCLBase" was (include/clenabled/GRCLBase.h:77-141)
-class MI355Base {
-protected:
-    mi355_ctx *d_ctx = nullptr;
-    bool debugMode;
-    MI355Base(int openCLPlatformType, int devSelector, int platformId, int devId, bool setDebug) : debugMode(setDebug)
-    {
-        static std::once_flag once;
-        std::call_once(once, [] { mi355_set_log_callback(&log_sink, nullptr); });
-        // the reference prints and exit(0)s on failure (lib/GRCLBase.cpp:239-257); throw instead
-        chk(mi355_ctx_create(openCLPlatformType, devSelector, platformId, devId, setDebug ? 1 : 0, &d_ctx), "mi355_ctx_create");
-    }
-    ~MI355Base() { mi355_ctx_destroy(d_ctx); }
-    static void chk(int rc, const char *what)
-    {
-        if (rc != MI355_OK) throw std::runtime_error(std::string(what) + ": " + mi355_strerror(rc) + ": " + mi355_last_error());
-    }
-    static size_t dsize(int idataType)
-    {
-        switch (idataType) {  // lib/clMathOp_impl.cc:35-47
-        case DTYPE_COMPLEX: return sizeof(gr_complex);
-        case DTYPE_INT: return sizeof(int);
-        default: return sizeof(float);
-        }
-    }
-};
-
-class clMathOp_impl : public clMathOp, public MI355Base {
-    mi355_mathop *d_h = nullptr;
+class clMathOp_impl : public clMathOp, BlockBase<mi355_mathop, mi355_mathop_destroy> {
 public:
     clMathOp_impl(int idataType, int openCLPlatformType, int devSelector, int platformId, int devId, int operatorType, bool setDebug)
-        : gr::sync_block("clMathOp", gr::io_signature::make(2, 2, (int)dsize(idataType)), gr::io_signature::make(1, 1, (int)dsize(idataType))),  // lib/clMathOp_impl.cc:63-65
-          MI355Base(openCLPlatformType, devSelector, platformId, devId, setDebug)
+        : gr::sync_block("clMathOp", gr::io_signature::make(2, 2, (int)dsize(idataType)), gr::io_signature::make(1, 1, (int)dsize(idataType)))  // lib/clMathOp_impl.cc:63-65
     {
-        chk(mi355_mathop_create(d_ctx, idataType, operatorType, 8192, &d_h), "mi355_mathop_create");
+        d_ctx.open(openCLPlatformType, devSelector, platformId, devId, setDebug);
+        created(mi355_mathop_create(d_ctx, idataType, operatorType, 8192, d_h.adopt()), "mi355_mathop_create", ArgIs::runtime_error);
     }
-    ~clMathOp_impl() override { mi355_mathop_destroy(d_h); }
     int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
     {
-        chk(mi355_mathop_work(d_h, (size_t)noutput_items, in[0], in[1], out[0]), "mi355_mathop_work");
+        chk_runtime(mi355_mathop_work(d_h, (size_t)noutput_items, in[0], in[1], out[0]), "mi355_mathop_work");
         return noutput_items;
     }
     int testOpenCL(int n, gr_vector_int &, gr_vector_const_void_star &in, gr_vector_void_star &out) override { return work(n, in, out); }
 };
 
-class clMathConst_impl : public clMathConst, public MI355Base {
-    mi355_mathconst *d_h = nullptr;
+class clMathConst_impl : public clMathConst, BlockBase<mi355_mathconst, mi355_mathconst_destroy> {
 public:
     clMathConst_impl(int idataType, int openCLPlatformType, int devSelector, int platformId, int devId, float fValue,
                      int operatorType, bool setDebug)
-        : gr::sync_block("clMathConst", gr::io_signature::make(1, 1, (int)dsize(idataType)), gr::io_signature::make(1, 1, (int)dsize(idataType))),
-          MI355Base(openCLPlatformType, devSelector, platformId, devId, setDebug)
+        : gr::sync_block("clMathConst", gr::io_signature::make(1, 1, (int)dsize(idataType)), gr::io_signature::make(1, 1, (int)dsize(idataType)))
     {
-        chk(mi355_mathconst_create(d_ctx, idataType, operatorType, fValue, 8192, &d_h), "mi355_mathconst_create");
+        d_ctx.open(openCLPlatformType, devSelector, platformId, devId, setDebug);
+        created(mi355_mathconst_create(d_ctx, idataType, operatorType, fValue, 8192, d_h.adopt()), "mi355_mathconst_create", ArgIs::runtime_error);
     }
-    ~clMathConst_impl() override { mi355_mathconst_destroy(d_h); }
     float k() const override { float v = 0; mi355_mathconst_get_k(d_h, &v); return v; }
-    void set_k(float v) override { chk(mi355_mathconst_set_k(d_h, v), "mi355_mathconst_set_k"); }
+    void set_k(float v) override { chk_runtime(mi355_mathconst_set_k(d_h, v), "mi355_mathconst_set_k"); }
 #if defined(MI355_WITH_GNURADIO) && defined(GR_CTRLPORT)
     // ControlPort: the constant as a readable and writable real "Constant" (lib/clMathConst_impl.cc:377-401)
     void setup_rpc() override
@@ -105,30 +57,29 @@ public:
 #endif
     int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
     {
-        chk(mi355_mathconst_work(d_h, (size_t)noutput_items, in[0], out[0]), "mi355_mathconst_work");
+        chk_runtime(mi355_mathconst_work(d_h, (size_t)noutput_items, in[0], out[0]), "mi355_mathconst_work");
         return noutput_items;
     }
     int testOpenCL(int n, gr_vector_int &, gr_vector_const_void_star &in, gr_vector_void_star &out) override { return work(n, in, out); }
 };
 
-class clFFT_impl : public clFFT, public MI355Base {
-    mi355_fft *d_h = nullptr;
+class clFFT_impl : public clFFT, BlockBase<mi355_fft, mi355_fft_destroy> {
     int d_fft_size;
 public:
     clFFT_impl(int fftSize, int clFFTDir, const std::vector<float> &window, int idataType, int openCLPlatformType, int devSelector,
                int platformId, int devId, bool setDebug, int num_streams, bool shift)
         : gr::sync_block("clFFT", gr::io_signature::make(1, num_streams, fftSize * (int)dsize(idataType)), gr::io_signature::make(1, num_streams, fftSize * (int)sizeof(gr_complex))),  // lib/clFFT_impl.cc:68-70
-          MI355Base(openCLPlatformType, devSelector, platformId, devId, setDebug), d_fft_size(fftSize)
+          d_fft_size(fftSize)
     {
+        d_ctx.open(openCLPlatformType, devSelector, platformId, devId, setDebug);
         if (!(window.empty() || window.size() == (size_t)fftSize))  // lib/clFFT_impl.cc:74-76
             throw std::runtime_error("OpenCL FFT: window not the same length as fft_size\n");
-        chk(mi355_fft_create(d_ctx, fftSize, clFFTDir, window.empty() ? nullptr : window.data(), (int)window.size(), idataType,
-                             num_streams, shift ? 1 : 0, &d_h), "mi355_fft_create");
+        created(mi355_fft_create(d_ctx, fftSize, clFFTDir, window.empty() ? nullptr : window.data(), (int)window.size(), idataType,
+                                 num_streams, shift ? 1 : 0, d_h.adopt()), "mi355_fft_create", ArgIs::runtime_error);
     }
-    ~clFFT_impl() override { mi355_fft_destroy(d_h); }
     int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
     {
-        chk(mi355_fft_work(d_h, noutput_items, in.data(), out.data()), "mi355_fft_work");  // noutput_items = vectors (:637-654)
+        chk_runtime(mi355_fft_work(d_h, noutput_items, in.data(), out.data()), "mi355_fft_work");  // noutput_items = vectors (:637-654)
         return noutput_items;
     }
     int testOpenCL(int nsamples, gr_vector_const_void_star &in, gr_vector_void_star &out) override
@@ -138,25 +89,23 @@ public:
 };
 
 template <class Base, class Tap>
-class filter_impl_t : public Base, public MI355Base {
+class filter_impl_t : public Base, protected BlockBase<mi355_filter, mi355_filter_destroy> {
 protected:
-    mi355_filter *d_h = nullptr;
     std::mutex d_lock;
     bool d_updated = false;
 public:
     filter_impl_t(const char *name, int openclPlatform, int devSelector, int platformId, int devId, int decimation,
                   const std::vector<Tap> &taps, bool setDebug, bool complex_taps, bool use_time)
-        : gr::sync_decimator(name, gr::io_signature::make(1, 1, (int)sizeof(gr_complex)), gr::io_signature::make(1, 1, (int)sizeof(gr_complex)), decimation),
-          MI355Base(openclPlatform, devSelector, platformId, devId, setDebug)
+        : gr::sync_decimator(name, gr::io_signature::make(1, 1, (int)sizeof(gr_complex)), gr::io_signature::make(1, 1, (int)sizeof(gr_complex)), decimation)
     {
-        chk(mi355_filter_create(d_ctx, decimation, taps.data(), (int)taps.size(), complex_taps, use_time, &d_h), "mi355_filter_create");
+        d_ctx.open(openclPlatform, devSelector, platformId, devId, setDebug);
+        created(mi355_filter_create(d_ctx, decimation, taps.data(), (int)taps.size(), complex_taps, use_time, d_h.adopt()), "mi355_filter_create", ArgIs::runtime_error);
         this->set_history(taps.size());  // lib/clFilter_impl.cc:78
     }
-    ~filter_impl_t() override { mi355_filter_destroy(d_h); }
     void set_taps2(const std::vector<Tap> &taps) override
     {
         std::lock_guard<std::mutex> g(d_lock);  // lib/clFilter_impl.cc:443
-        chk(mi355_filter_set_taps(d_h, taps.data(), (int)taps.size()), "mi355_filter_set_taps");
+        chk_runtime(mi355_filter_set_taps(d_h, taps.data(), (int)taps.size()), "mi355_filter_set_taps");
         d_updated = true;
     }
     std::vector<Tap> taps() const override
@@ -173,7 +122,7 @@ public:
             d_updated = false;
             return 0;
         }
-        chk(mi355_filter_work(d_h, (size_t)noutput_items, in[0], out[0]), "mi355_filter_work");
+        chk_runtime(mi355_filter_work(d_h, (size_t)noutput_items, in[0], out[0]), "mi355_filter_work");
         return noutput_items;
     }
     int testOpenCL(int n, gr_vector_const_void_star &in, gr_vector_void_star &out) override { return work(n, in, out); }
@@ -194,23 +143,22 @@ public:
           filter_impl_t("clComplexFilter", p, s, pl, d, decim, taps, dbg, true, true) {}
 };
 
-class clPolyphaseChannelizer_impl : public clPolyphaseChannelizer, public MI355Base {
-    mi355_pfb *d_h = nullptr;
+class clPolyphaseChannelizer_impl : public clPolyphaseChannelizer, BlockBase<mi355_pfb, mi355_pfb_destroy> {
     int d_buf_items;
 public:
     clPolyphaseChannelizer_impl(int p, int s, int pl, int d, const std::vector<float> &taps, int buf_items, int num_channels,
                                 int ninputs_per_iter, const std::vector<int> &ch_map, bool dbg)
         : gr::block("clPolyphaseChannelizer", gr::io_signature::make(1, 1, (int)sizeof(gr_complex)), gr::io_signature::make(1, 1, (int)sizeof(gr_complex))),  // lib/clPolyphaseChannelizer_impl.cc:50-51
-          MI355Base(p, s, pl, d, dbg), d_buf_items(buf_items)
+          d_buf_items(buf_items)
     {
+        d_ctx.open(p, s, pl, d, dbg);
         if (num_channels <= 0 || buf_items % num_channels != 0)  // lib/clPolyphaseChannelizer_impl.cc:59-62
             throw std::invalid_argument("buf_items must be a multiple of num_channels");
-        chk(mi355_pfb_create(d_ctx, taps.data(), (int)taps.size(), buf_items, num_channels, ninputs_per_iter, ch_map.data(),
-                             (int)ch_map.size(), &d_h), "mi355_pfb_create");
+        created(mi355_pfb_create(d_ctx, taps.data(), (int)taps.size(), buf_items, num_channels, ninputs_per_iter, ch_map.data(),
+                                 (int)ch_map.size(), d_h.adopt()), "mi355_pfb_create", ArgIs::runtime_error);
         set_history(taps.size());                     // :63
         set_output_multiple(mi355_pfb_noutput(d_h));  // :64
     }
-    ~clPolyphaseChannelizer_impl() override { mi355_pfb_destroy(d_h); }
     // ninput_items_required = ninputs_per_iter * noutput_items / nmap + history() - num_channels (:78-82); for one output multiple
     // that is mi355_pfb_ninput(); every further multiple needs buf_items more
     void forecast(int noutput_items, gr_vector_int &req) override
@@ -224,22 +172,22 @@ public:
     {
         const int per = mi355_pfb_noutput(d_h), k = noutput_items > per ? noutput_items / per : 1;
         for (int b = 0; b < k; b++)
-            chk(mi355_pfb_work(d_h, (const gr_complex *)in[0] + (size_t)b * d_buf_items, (gr_complex *)out[0] + (size_t)b * per), "mi355_pfb_work");
+            chk_runtime(mi355_pfb_work(d_h, (const gr_complex *)in[0] + (size_t)b * d_buf_items, (gr_complex *)out[0] + (size_t)b * per), "mi355_pfb_work");
         consume_each(k * d_buf_items);  // :105
         return k * per;
     }
 };
 
-class clXEngine_impl : public clXEngine, public MI355Base {
-    mi355_xengine *d_h = nullptr;
+class clXEngine_impl : public clXEngine, BlockBase<mi355_xengine, mi355_xengine_destroy> {
     // several devices behind ONE block (set_shard_devices / MI355_XENGINE_DEVICES): antenna groups in, channel slabs out, the corner turn
     // between the devices inside mi355_xengine_shard_* -- the reference has one device per block (devId, lib/GRCLBase.cpp:115-134)
     bool d_sharded = false;                         // set_shard_devices() with two or more devices
-    mi355_xengine_shard *d_shard = nullptr;         // one window per call: xcorrelate(char*, XComplex*), pipeline integration -- created at first use
+    typedef Handle<mi355_xengine_shard, mi355_xengine_shard_destroy> Shard;
+    Shard d_shard;  // one window per call: xcorrelate(char*, XComplex*), pipeline integration -- created at first use
     // the STREAMING path of work_test(): d_shard_windows integration windows per exchange, gathered straight into the handle's pinned frame slots
     // (mi355_xengine_shard_acquire / submit_acquired / wait: every device uploads its antenna group over its own link, asynchronously, while the next
     // windows are gathered) -- created at the first streamed window
-    mi355_xengine_shard *d_shard_stream = nullptr;
+    Shard d_shard_stream;
     std::vector<int> d_shard_ids;
     int d_shard_windows = 4, d_batch_fill = 0;
     char *d_batch_base = nullptr;
@@ -320,7 +268,7 @@ class clXEngine_impl : public clXEngine, public MI355Base {
     }
     void collect_shard()
     {
-        chk(mi355_xengine_shard_wait(d_shard_stream, d_result_batch.data()), "mi355_xengine_shard_wait");
+        chk_runtime(mi355_xengine_shard_wait(d_shard_stream, d_result_batch.data()), "mi355_xengine_shard_wait");
         const std::vector<long> firsts = d_shard_pending_first.front();
         d_shard_pending_first.erase(d_shard_pending_first.begin());
         for (size_t w = 0; w < firsts.size(); w++) deliver(d_result_batch.data() + w * d_matrix_len, firsts[w]);
@@ -329,13 +277,13 @@ class clXEngine_impl : public clXEngine, public MI355Base {
     mi355_xengine_shard *sync_shard()  // the one-window-per-call handle (the streaming path has its own, with windows_per_exchange windows)
     {
         if (!d_shard)
-            chk(mi355_xengine_shard_create((int)d_shard_ids.size(), d_shard_ids.data(), d_npol, d_num_inputs, d_num_channels, d_integration, 1, &d_shard),
-                "mi355_xengine_shard_create");
+            chk_runtime(mi355_xengine_shard_create((int)d_shard_ids.size(), d_shard_ids.data(), d_npol, d_num_inputs, d_num_channels, d_integration, 1, d_shard.adopt()),
+                        "mi355_xengine_shard_create");
         return d_shard;
     }
     void collect_one()
     {
-        chk(mi355_xengine_wait(d_h, d_result.data()), "mi355_xengine_wait");
+        chk_runtime(mi355_xengine_wait(d_h, d_result.data()), "mi355_xengine_wait");
         deliver(d_result.data(), d_pending_first.front());
         d_pending_first.erase(d_pending_first.begin());
     }
@@ -351,15 +299,16 @@ public:
                     gr::io_signature::make(2, num_inputs * (data_type == DTYPE_PACKEDXY ? 1 : polarization),
                                            num_channels * (data_type == DTYPE_PACKEDXY ? 2 : item_bytes(data_type))),
                     gr::io_signature::make(0, 0, 0)),
-          MI355Base(p, s, pl, d, dbg), d_data_type(data_type), d_npol(data_type == DTYPE_PACKEDXY ? 2 : polarization),
+          d_data_type(data_type), d_npol(data_type == DTYPE_PACKEDXY ? 2 : polarization),
           d_num_inputs(num_inputs), d_num_channels(num_channels), d_integration(integration),
           d_pipeline_integration(pipeline_integration), d_first_channel(first_channel), d_disable_output(disable_output),
           d_output_file(output_file && !disable_output), d_file_base(file_base), d_object_name(object_name),
           d_sync_timestamp(sync_timestamp), d_start_freq(start_freq), d_chan_width(chan_width)
     {
+        d_ctx.open(p, s, pl, d, dbg);
         if (num_inputs < 2)  // lib/clXEngine_impl.cc:106-109
             throw std::out_of_range("Please specify at least 2 inputs to correlate.");
-        chk(mi355_xengine_create(d_ctx, data_type, polarization, num_inputs, num_channels, integration, &d_h), "mi355_xengine_create");
+        created(mi355_xengine_create(d_ctx, data_type, polarization, num_inputs, num_channels, integration, d_h.adopt()), "mi355_xengine_create", ArgIs::runtime_error);
         d_in_items = (long)num_inputs * num_channels * d_npol * integration;
         d_in_bytes = mi355_xengine_input_bytes(d_h);
         d_matrix_len = mi355_xengine_output_items(d_h);
@@ -396,9 +345,8 @@ public:
                 // ranks do not divide -- keeps its one device and says so; only the explicit call throws
                 try { set_shard_devices(ids); }
                 catch (const std::exception &ex) {
-                    mi355_xengine_shard_destroy(d_shard);
-                    mi355_xengine_shard_destroy(d_shard_stream);
-                    d_shard = d_shard_stream = nullptr;
+                    d_shard.reset();
+                    d_shard_stream.reset();
                     d_sharded = false;
                     log_sink(nullptr, MI355_LOG_WARN, (std::string("MI355_XENGINE_DEVICES ignored for this clXEngine block: ") + ex.what()).c_str());
                 }
@@ -408,9 +356,6 @@ public:
     ~clXEngine_impl() override
     {
         try { stop(); } catch (...) {}
-        mi355_xengine_shard_destroy(d_shard_stream);
-        mi355_xengine_shard_destroy(d_shard);
-        mi355_xengine_destroy(d_h);
     }
     void set_shard_devices(const std::vector<int> &device_ids, int windows_per_exchange = 4) override
     {
@@ -420,18 +365,16 @@ public:
         if (d_batch_fill != 0 || (d_shard_stream && mi355_xengine_shard_pending(d_shard_stream) > 0))
             throw std::runtime_error("[X-Engine] set_shard_devices: an exchange is in progress (stop() first)");
         if (windows_per_exchange < 1) throw std::invalid_argument("[X-Engine] set_shard_devices: windows_per_exchange must be >= 1");
-        mi355_xengine_shard_destroy(d_shard_stream);
-        d_shard_stream = nullptr;
-        mi355_xengine_shard_destroy(d_shard);
-        d_shard = nullptr;
+        d_shard_stream.reset();
+        d_shard.reset();
         d_shard_ids = device_ids;
         d_shard_windows = windows_per_exchange;
         if (const char *e = getenv("MI355_XENGINE_SHARD_WINDOWS")) d_shard_windows = atoi(e) > 0 ? atoi(e) : d_shard_windows;
         d_sharded = false;
         if (device_ids.size() < 2) return;  // back to the one device of make()
         // (the streaming handle is created here: it validates devices and geometry -- 64 inputs x 2 polarisations need enough windows per exchange)
-        chk(mi355_xengine_shard_create((int)device_ids.size(), device_ids.data(), d_npol, d_num_inputs, d_num_channels, d_integration, d_shard_windows,
-                                       &d_shard_stream), "mi355_xengine_shard_create");
+        chk_runtime(mi355_xengine_shard_create((int)device_ids.size(), device_ids.data(), d_npol, d_num_inputs, d_num_channels, d_integration, d_shard_windows,
+                                               d_shard_stream.adopt()), "mi355_xengine_shard_create");
         d_result_batch.resize((size_t)d_shard_windows * d_matrix_len);
         d_sharded = true;
         d_frames_sync.resize(d_in_bytes);
@@ -446,7 +389,7 @@ public:
             while (mi355_xengine_shard_pending(d_shard_stream) > 0) collect_shard();
             // whole windows of a batch that did not fill up: through the block's one device, from the pinned buffer they were gathered into
             for (int w = 0; w < d_batch_fill; w++) {
-                chk(mi355_xengine_xcorrelate(d_h, d_batch_base + (size_t)w * d_in_bytes, d_result.data(), 0), "mi355_xengine_xcorrelate");
+                chk_runtime(mi355_xengine_xcorrelate(d_h, d_batch_base + (size_t)w * d_in_bytes, d_result.data(), 0), "mi355_xengine_xcorrelate");
                 deliver(d_result.data(), d_batch_first[(size_t)w]);
             }
             d_batch_fill = 0;
@@ -517,13 +460,13 @@ public:
             if (shard_streaming()) {
                 if (d_batch_fill == 0) {  // ... and a new exchange: the next pinned frame slot of the sharded handle
                     if (!d_shard_stream) {
-                        chk(mi355_xengine_shard_create((int)d_shard_ids.size(), d_shard_ids.data(), d_npol, d_num_inputs, d_num_channels, d_integration,
-                                                       d_shard_windows, &d_shard_stream), "mi355_xengine_shard_create");
+                        chk_runtime(mi355_xengine_shard_create((int)d_shard_ids.size(), d_shard_ids.data(), d_npol, d_num_inputs, d_num_channels, d_integration,
+                                                               d_shard_windows, d_shard_stream.adopt()), "mi355_xengine_shard_create");
                         d_result_batch.resize((size_t)d_shard_windows * d_matrix_len);
                     }
                     if (mi355_xengine_shard_pending(d_shard_stream) == 2) collect_shard();
                     void *fb = nullptr;
-                    chk(mi355_xengine_shard_acquire(d_shard_stream, &fb), "mi355_xengine_shard_acquire");
+                    chk_runtime(mi355_xengine_shard_acquire(d_shard_stream, &fb), "mi355_xengine_shard_acquire");
                     d_batch_base = (char *)fb;
                     d_batch_first.clear();
                 }
@@ -532,11 +475,11 @@ public:
             else {
                 if (mi355_xengine_pending(d_h) == 2) collect_one();  // previous result goes out before the swap (:1070-1094)
                 void *fb = nullptr;
-                chk(mi355_xengine_acquire(d_h, &fb), "mi355_xengine_acquire");
+                chk_runtime(mi355_xengine_acquire(d_h, &fb), "mi355_xengine_acquire");
                 d_frames = (char *)fb;
             }
         }
-        chk(mi355_xengine_gather(d_h, n, d_tracker, in.data(), d_frames), "mi355_xengine_gather");
+        chk_runtime(mi355_xengine_gather(d_h, n, d_tracker, in.data(), d_frames), "mi355_xengine_gather");
         d_tracker += n;
         d_frame_counter += n;
         if (d_tracker == d_integration) {
@@ -547,23 +490,23 @@ public:
                 // under the gather of the next (the reference overlaps with a worker thread, lib/clXEngine_impl.cc:1234-1299)
                 d_batch_first.push_back(first);
                 if (++d_batch_fill == d_shard_windows) {
-                    chk(mi355_xengine_shard_submit_acquired(d_shard_stream), "mi355_xengine_shard_submit_acquired");
+                    chk_runtime(mi355_xengine_shard_submit_acquired(d_shard_stream), "mi355_xengine_shard_submit_acquired");
                     d_shard_pending_first.push_back(d_batch_first);
                     d_batch_fill = 0;
                     if (mi355_xengine_shard_pending(d_shard_stream) == 2) collect_shard();
                 }
             } else if (d_pipeline_integration > 1) {
                 // device "+=" into the running matrix, read back every pipeline_integration windows (:785-796,1250-1285)
-                if (d_sharded) chk(mi355_xengine_shard_xcorrelate(sync_shard(), d_frames, d_accum.data(), 1), "mi355_xengine_shard_xcorrelate");
+                if (d_sharded) chk_runtime(mi355_xengine_shard_xcorrelate(sync_shard(), d_frames, d_accum.data(), 1), "mi355_xengine_shard_xcorrelate");
                 else
-                chk(mi355_xengine_xcorrelate(d_h, d_frames, d_accum.data(), 1), "mi355_xengine_xcorrelate");
+                chk_runtime(mi355_xengine_xcorrelate(d_h, d_frames, d_accum.data(), 1), "mi355_xengine_xcorrelate");
                 if (++d_pipe_count >= d_pipeline_integration) {
                     deliver(d_accum.data(), first - (long)d_integration * (d_pipeline_integration - 1));
                     d_accum.assign(d_matrix_len, XComplex());
                     d_pipe_count = 0;
                 }
             } else {
-                chk(mi355_xengine_submit_acquired(d_h, nullptr), "mi355_xengine_submit_acquired");
+                chk_runtime(mi355_xengine_submit_acquired(d_h, nullptr), "mi355_xengine_submit_acquired");
                 d_pending_first.push_back(first);
                 if (mi355_xengine_pending(d_h) == 2) collect_one();  // keep one in flight: overlap with the next window's gather
             }
@@ -577,27 +520,26 @@ public:
     long get_output_buffer_size() override { return (long)d_matrix_len; }
     void xcorrelate(XComplex *in, XComplex *out) override
     {
-        chk(mi355_xengine_xcorrelate(d_h, in, out, d_pipeline_integration > 1), "mi355_xengine_xcorrelate");
+        chk_runtime(mi355_xengine_xcorrelate(d_h, in, out, d_pipeline_integration > 1), "mi355_xengine_xcorrelate");
     }
     void xcorrelate(char *in, XComplex *out) override
     {
-        if (d_sharded) chk(mi355_xengine_shard_xcorrelate(sync_shard(), in, out, d_pipeline_integration > 1), "mi355_xengine_shard_xcorrelate");
+        if (d_sharded) chk_runtime(mi355_xengine_shard_xcorrelate(sync_shard(), in, out, d_pipeline_integration > 1), "mi355_xengine_shard_xcorrelate");
         else
-        chk(mi355_xengine_xcorrelate(d_h, in, out, d_pipeline_integration > 1), "mi355_xengine_xcorrelate");
+        chk_runtime(mi355_xengine_xcorrelate(d_h, in, out, d_pipeline_integration > 1), "mi355_xengine_xcorrelate");
     }
-    void submit(const void *in, const XComplex *acc) override { chk(mi355_xengine_submit(d_h, in, acc), "mi355_xengine_submit"); }
-    void wait(XComplex *out) override { chk(mi355_xengine_wait(d_h, out), "mi355_xengine_wait"); }
+    void submit(const void *in, const XComplex *acc) override { chk_runtime(mi355_xengine_submit(d_h, in, acc), "mi355_xengine_submit"); }
+    void wait(XComplex *out) override { chk_runtime(mi355_xengine_wait(d_h, out), "mi355_xengine_wait"); }
     int gather_frames(int nframes, int frame0, gr_vector_const_void_star &in, void *fb) override
     {
-        chk(mi355_xengine_gather(d_h, nframes, frame0, in.data(), fb), "mi355_xengine_gather");
+        chk_runtime(mi355_xengine_gather(d_h, nframes, frame0, in.data(), fb), "mi355_xengine_gather");
         return nframes;
     }
 };
 
 // remaining elementwise family: one implementation over mi355_elem_* (kind selects the block)
 template <class Base>
-class elem_impl_t : public Base, public MI355Base {
-    mi355_elem *d_h = nullptr;
+class elem_impl_t : public Base, BlockBase<mi355_elem, mi355_elem_destroy> {
     int d_nin, d_nout;
 public:
     // item sizes as in the reference's constructors (e.g. lib/clComplexToMagPhase_impl.cc:49-50: complex in, two floats out)
@@ -609,16 +551,16 @@ public:
     elem_impl_t(const char *name, int kind, int nin, int nout, float p0, float p1, int openCLPlatformType, int devSelector,
                 int platformId, int devId, bool setDebug)
         : gr::sync_block(name, gr::io_signature::make(nin, nin, in_size(kind)), gr::io_signature::make(nout, nout, out_size(kind))),
-          MI355Base(openCLPlatformType, devSelector, platformId, devId, setDebug), d_nin(nin), d_nout(nout)
+          d_nin(nin), d_nout(nout)
     {
-        chk(mi355_elem_create(d_ctx, kind, p0, p1, &d_h), "mi355_elem_create");
+        d_ctx.open(openCLPlatformType, devSelector, platformId, devId, setDebug);
+        created(mi355_elem_create(d_ctx, kind, p0, p1, d_h.adopt()), "mi355_elem_create", ArgIs::runtime_error);
         this->set_history((unsigned)mi355_elem_history(d_h));  // clQuadratureDemod: 2 (lib/clQuadratureDemod_impl.cc:81)
     }
-    ~elem_impl_t() override { mi355_elem_destroy(d_h); }
     int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
     {
-        chk(mi355_elem_work(d_h, (size_t)noutput_items, in[0], d_nin > 1 ? in[1] : nullptr, out[0], d_nout > 1 ? out[1] : nullptr),
-            "mi355_elem_work");
+        chk_runtime(mi355_elem_work(d_h, (size_t)noutput_items, in[0], d_nin > 1 ? in[1] : nullptr, out[0], d_nout > 1 ? out[1] : nullptr),
+                    "mi355_elem_work");
         return noutput_items;
     }
     int testOpenCL(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
@@ -627,21 +569,19 @@ public:
     }
 };
 
-class clxcorrelate_fft_vcf_impl : public clxcorrelate_fft_vcf, public MI355Base {
-    mi355_xcorr_fft *d_h = nullptr;
+class clxcorrelate_fft_vcf_impl : public clxcorrelate_fft_vcf, BlockBase<mi355_xcorr_fft, mi355_xcorr_fft_destroy> {
 public:
     clxcorrelate_fft_vcf_impl(int fftSize, int num_inputs, int openCLPlatformType, int devSelector, int platformId, int devId,
                               int input_type)
         : gr::sync_block("clxcorrelate_fft_vcf", gr::io_signature::make(2, num_inputs, (int)sizeof(gr_complex) * fftSize),
-                         gr::io_signature::make(1, num_inputs - 1, (int)sizeof(float) * fftSize)),  // lib/clxcorrelate_fft_vcf_impl.cc:701-702
-          MI355Base(openCLPlatformType, devSelector, platformId, devId, false)
+                         gr::io_signature::make(1, num_inputs - 1, (int)sizeof(float) * fftSize))  // lib/clxcorrelate_fft_vcf_impl.cc:701-702
     {
-        chk(mi355_xcorr_fft_create(d_ctx, fftSize, num_inputs, input_type, &d_h), "mi355_xcorr_fft_create");
+        d_ctx.open(openCLPlatformType, devSelector, platformId, devId, false);
+        created(mi355_xcorr_fft_create(d_ctx, fftSize, num_inputs, input_type, d_h.adopt()), "mi355_xcorr_fft_create", ArgIs::runtime_error);
     }
-    ~clxcorrelate_fft_vcf_impl() override { mi355_xcorr_fft_destroy(d_h); }
     int work(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override
     {
-        chk(mi355_xcorr_fft_work(d_h, noutput_items, in.data(), out.data()), "mi355_xcorr_fft_work");  // vectors (:1058-1143)
+        chk_runtime(mi355_xcorr_fft_work(d_h, noutput_items, in.data(), out.data()), "mi355_xcorr_fft_work");  // vectors (:1058-1143)
         return noutput_items;
     }
     int work_test(int noutput_items, gr_vector_const_void_star &in, gr_vector_void_star &out) override

@@ -3,23 +3,15 @@
 // writes every output byte (nunits * out_bytes_per_unit) -- the test hands it heap buffers of exactly that size, so under
 // -fsanitize=address,undefined a work() that passes a frame too few or the wrong unit count is caught -- and records what it was handed.
 #include <clenabled/clenabled.h>
-#include <mi355_clenabled.h>
+#include "host_stub.h"
 
-#include <cstdio>
-#include <cstring>
-#include <stdexcept>
-#include <string>
 #include <vector>
 
-struct mi355_ctx { int dev; };
 struct mi355_beamform {
     int mode, npol, S, F, B, Ti, stokes, generic;
     long long calls, last_units;
     std::vector<int8_t> w;
 };
-
-static std::string g_err;
-static int g_live_ctx = 0, g_live_handles = 0;
 
 static int stub_plan(int mode, int npol, int S, int F, int B, int Ti, int stokes, long long *fb, int *fpu, long long *ob)
 {
@@ -35,16 +27,6 @@ static int stub_plan(int mode, int npol, int S, int F, int B, int Ti, int stokes
 }
 
 extern "C" {
-const char *mi355_strerror(int code) { return code == MI355_ERR_INVALID_ARG ? "invalid argument" : code == MI355_ERR_NO_DEVICE ? "no device" : "error"; }
-const char *mi355_last_error(void) { return g_err.c_str(); }
-int mi355_ctx_create(int, int, int, int dev_id, int, mi355_ctx **out)
-{
-    if (dev_id == 99) { g_err = "no such device"; return MI355_ERR_NO_DEVICE; }
-    *out = new mi355_ctx{dev_id};
-    g_live_ctx++;
-    return MI355_OK;
-}
-int mi355_ctx_destroy(mi355_ctx *ctx) { delete ctx; g_live_ctx--; return MI355_OK; }
 int mi355_beamform_plan(int mode, int npol, int S, int F, int B, int Ti, int stokes, long long *fb, int *fpu, long long *ob)
 {
     return stub_plan(mode, npol, S, F, B, Ti, stokes, fb, fpu, ob);
@@ -99,14 +81,6 @@ int mi355_beamform_work(mi355_beamform *h, long long nunits, const void *in, voi
 }
 }
 
-#define CHECK(c)                                                      \
-    do {                                                              \
-        if (!(c)) {                                                   \
-            fprintf(stderr, "line %d: %s\n", __LINE__, #c);           \
-            return 1;                                                 \
-        }                                                             \
-    } while (0)
-
 using gr::clenabled::clBeamformer;
 
 // one work() call on exact-size heap buffers; returns what work() returned, or -1 when a byte of the output is not the stub's
@@ -148,16 +122,11 @@ static int run(int mode, int npol, int S, int F, int B, int Ti, bool stokes)
     std::vector<int8_t> w2(nw, 5);
     bf->set_weights(w2);
     CHECK(bf->weights() == w2);
-    for (size_t bad : {(size_t)0, nw - 1, nw + 1, 2 * nw}) {
-        bool threw = false;
-        try { bf->set_weights(std::vector<int8_t>(bad, 1)); } catch (const std::invalid_argument &) { threw = true; }
-        CHECK(threw && bf->weights() == w2);
-    }
-    bool threw = false;
+    for (size_t bad : {(size_t)0, nw - 1, nw + 1, 2 * nw})
+        CHECK(throws<std::invalid_argument>([&] { bf->set_weights(std::vector<int8_t>(bad, 1)); }) && bf->weights() == w2);
     std::vector<int8_t> w3(nw, 1);
     w3[nw / 2] = -128;
-    try { bf->set_weights(w3); } catch (const std::invalid_argument &) { threw = true; }
-    CHECK(threw && bf->weights() == w2);
+    CHECK(throws<std::invalid_argument>([&] { bf->set_weights(w3); }) && bf->weights() == w2);
     // set_beam_weights: [f][p][s], one beam of every (f, p)
     const size_t nb = (size_t)2 * F * npol * S;
     std::vector<int8_t> wb(nb, -7);
@@ -168,13 +137,9 @@ static int run(int mode, int npol, int S, int F, int B, int Ti, bool stokes)
             for (int i = 0; i < 2 * S; i++) CHECK(w4[((size_t)c * B + b) * 2 * S + i] == (b == B - 1 ? -7 : 5));
     for (size_t bad : {(size_t)0, nb - 1, nb + 1, nw}) {
         if (bad == nb) continue;
-        threw = false;
-        try { bf->set_beam_weights(0, std::vector<int8_t>(bad, 1)); } catch (const std::invalid_argument &) { threw = true; }
-        CHECK(threw && bf->weights() == w4);
+        CHECK(throws<std::invalid_argument>([&] { bf->set_beam_weights(0, std::vector<int8_t>(bad, 1)); }) && bf->weights() == w4);
     }
-    threw = false;
-    try { bf->set_beam_weights(B, wb); } catch (const std::invalid_argument &) { threw = true; }
-    CHECK(threw);
+    CHECK(throws<std::invalid_argument>([&] { bf->set_beam_weights(B, wb); }));
     CHECK(call(*bf, 5, ++calls) == 5);
     // no weights at make(): all zero
     auto z = clBeamformer::make(1, 2, 0, 0, mode, npol, S, F, B, Ti, stokes);
@@ -193,20 +158,14 @@ int main()
     const std::vector<std::vector<int>> bad = {{2, 1, 4, 8, 2, 1, 0}, {0, 3, 4, 8, 2, 1, 0}, {0, 1, 0, 8, 2, 1, 0},   {0, 1, 513, 8, 2, 1, 0},
                                                {0, 1, 4, 0, 2, 1, 0}, {0, 1, 4, 8, 0, 1, 0}, {0, 1, 4, 8, 1025, 1, 0}, {1, 1, 4, 8, 2, 4097, 0},
                                                {0, 1, 4, 8, 2, 2, 0}, {1, 1, 4, 8, 2, 4, 1}, {0, 2, 4, 8, 2, 1, 1}};
-    for (const auto &s : bad) {
-        bool threw = false;
-        try { clBeamformer::make(1, 2, 0, 99, s[0], s[1], s[2], s[3], s[4], s[5], s[6] != 0); } catch (const std::invalid_argument &) { threw = true; }
-        CHECK(threw);
-    }
-    bool threw = false;
-    try { clBeamformer::make(1, 2, 0, 99, 0, 1, 4, 8, 2, 1, false, std::vector<int8_t>(7, 0)); } catch (const std::invalid_argument &) { threw = true; }
-    CHECK(threw);  // a weight vector of the wrong size, before the device is looked for
-    threw = false;
-    try { clBeamformer::make(1, 2, 0, 0, 0, 1, 4, 8, 2, 1, false, std::vector<int8_t>(2 * 8 * 2 * 4, -128)); } catch (const std::invalid_argument &) { threw = true; }
-    CHECK(threw && g_live_ctx == 0);  // refused by the library: the context is given back
-    threw = false;
-    try { clBeamformer::make(1, 2, 0, 99, 0, 1, 4, 8, 2); } catch (const std::invalid_argument &) { } catch (const std::runtime_error &e) { threw = strstr(e.what(), "no such device") != nullptr; }
-    CHECK(threw);
+    for (const auto &s : bad)
+        CHECK(throws<std::invalid_argument>([&] { clBeamformer::make(1, 2, 0, 99, s[0], s[1], s[2], s[3], s[4], s[5], s[6] != 0); }));
+    // a weight vector of the wrong size, before the device is looked for
+    CHECK(throws<std::invalid_argument>([] { clBeamformer::make(1, 2, 0, 99, 0, 1, 4, 8, 2, 1, false, std::vector<int8_t>(7, 0)); }));
+    // refused by the library: the context is given back
+    CHECK(throws<std::invalid_argument>([] { clBeamformer::make(1, 2, 0, 0, 0, 1, 4, 8, 2, 1, false, std::vector<int8_t>(2 * 8 * 2 * 4, -128)); }) &&
+          g_live_ctx == 0);
+    CHECK(throws<std::runtime_error>([] { clBeamformer::make(1, 2, 0, 99, 0, 1, 4, 8, 2); }, "no such device"));
     printf("beamform host ok\n");
     return 0;
 }

@@ -3,23 +3,15 @@
 // float (n R D) -- the test hands it heap buffers of exactly that size, so under -fsanitize=address,undefined a work() that passes a
 // sample too few or the wrong count is caught -- and records what it was handed.
 #include <clenabled/clenabled.h>
-#include <mi355_clenabled.h>
+#include "host_stub.h"
 
-#include <cstdio>
-#include <cstring>
-#include <stdexcept>
-#include <string>
 #include <vector>
 
-struct mi355_ctx { int dev; };
 struct mi355_dedisp {
     int R, F, D, H, order, generic;
     long long calls, last_n, last_pitch;
     std::vector<int32_t> tab;
 };
-
-static std::string g_err;
-static int g_live_ctx = 0, g_live_handles = 0;
 
 static int stub_plan(int R, int F, int D, int H, int order, long long *fi, long long *hi, long long *fo)
 {
@@ -41,16 +33,6 @@ static bool stub_table_ok(const int32_t *t, size_t n, int H)
 }
 
 extern "C" {
-const char *mi355_strerror(int code) { return code == MI355_ERR_INVALID_ARG ? "invalid argument" : code == MI355_ERR_NO_DEVICE ? "no device" : "error"; }
-const char *mi355_last_error(void) { return g_err.c_str(); }
-int mi355_ctx_create(int, int, int, int dev_id, int, mi355_ctx **out)
-{
-    if (dev_id == 99) { g_err = "no such device"; return MI355_ERR_NO_DEVICE; }
-    *out = new mi355_ctx{dev_id};
-    g_live_ctx++;
-    return MI355_OK;
-}
-int mi355_ctx_destroy(mi355_ctx *ctx) { delete ctx; g_live_ctx--; return MI355_OK; }
 int mi355_dedisp_plan(int R, int F, int D, int H, int order, long long *fi, long long *hi, long long *fo) { return stub_plan(R, F, D, H, order, fi, hi, fo); }
 int mi355_dedisp_create(mi355_ctx *ctx, int R, int F, int D, int H, int order, const int32_t *delays, mi355_dedisp **out)
 {
@@ -89,14 +71,6 @@ int mi355_dedisp_work(mi355_dedisp *h, long long n, const void *in, void *out, l
     return MI355_OK;
 }
 }
-
-#define CHECK(c)                                                      \
-    do {                                                              \
-        if (!(c)) {                                                   \
-            fprintf(stderr, "line %d: %s\n", __LINE__, #c);           \
-            return 1;                                                 \
-        }                                                             \
-    } while (0)
 
 using gr::clenabled::clDedisperser;
 
@@ -137,17 +111,12 @@ static int run(int R, int F, int D, int H)
     std::vector<int32_t> t2(nt, H);
     dd->set_delays(t2);
     CHECK(dd->delays() == t2);
-    for (size_t bad : {(size_t)0, nt - 1, nt + 1, 2 * nt}) {
-        bool threw = false;
-        try { dd->set_delays(std::vector<int32_t>(bad, 0)); } catch (const std::invalid_argument &) { threw = true; }
-        CHECK(threw && dd->delays() == t2);
-    }
+    for (size_t bad : {(size_t)0, nt - 1, nt + 1, 2 * nt})
+        CHECK(throws<std::invalid_argument>([&] { dd->set_delays(std::vector<int32_t>(bad, 0)); }) && dd->delays() == t2);
     for (int32_t v : {-2, H + 1}) {
-        bool threw = false;
         std::vector<int32_t> t3(nt, 0);
         t3[nt / 2] = v;
-        try { dd->set_delays(t3); } catch (const std::invalid_argument &) { threw = true; }
-        CHECK(threw && dd->delays() == t2);
+        CHECK(throws<std::invalid_argument>([&] { dd->set_delays(t3); }) && dd->delays() == t2);
     }
     CHECK(call(*dd, 5, ++calls) == 5);
     // no table at make(): all zero
@@ -166,20 +135,12 @@ int main()
     // argument errors throw std::invalid_argument before any device work (device 99 does not exist); a missing device is a runtime error
     const std::vector<std::vector<int>> bad = {{0, 8, 4, 5}, {4097, 8, 4, 5}, {2, 0, 4, 5}, {2, 16385, 4, 5}, {2, 8, 0, 5}, {2, 8, 4097, 5}, {2, 8, 4, -1},
                                                {2, 8, 4, (1 << 20) + 1}};
-    for (const auto &s : bad) {
-        bool threw = false;
-        try { clDedisperser::make(1, 2, 0, 99, s[0], s[1], s[2], s[3]); } catch (const std::invalid_argument &) { threw = true; }
-        CHECK(threw);
-    }
-    bool threw = false;
-    try { clDedisperser::make(1, 2, 0, 99, 2, 8, 4, 5, std::vector<int32_t>(7, 0)); } catch (const std::invalid_argument &) { threw = true; }
-    CHECK(threw);  // a table of the wrong size, before the device is looked for
-    threw = false;
-    try { clDedisperser::make(1, 2, 0, 0, 2, 8, 4, 5, std::vector<int32_t>(32, 6)); } catch (const std::invalid_argument &) { threw = true; }
-    CHECK(threw && g_live_ctx == 0);  // refused by the library: the context is given back
-    threw = false;
-    try { clDedisperser::make(1, 2, 0, 99, 2, 8, 4, 5); } catch (const std::invalid_argument &) { } catch (const std::runtime_error &e) { threw = strstr(e.what(), "no such device") != nullptr; }
-    CHECK(threw);
+    for (const auto &s : bad) CHECK(throws<std::invalid_argument>([&] { clDedisperser::make(1, 2, 0, 99, s[0], s[1], s[2], s[3]); }));
+    // a table of the wrong size, before the device is looked for
+    CHECK(throws<std::invalid_argument>([] { clDedisperser::make(1, 2, 0, 99, 2, 8, 4, 5, std::vector<int32_t>(7, 0)); }));
+    // refused by the library: the context is given back
+    CHECK(throws<std::invalid_argument>([] { clDedisperser::make(1, 2, 0, 0, 2, 8, 4, 5, std::vector<int32_t>(32, 6)); }) && g_live_ctx == 0);
+    CHECK(throws<std::runtime_error>([] { clDedisperser::make(1, 2, 0, 99, 2, 8, 4, 5); }, "no such device"));
     printf("dedisp host ok\n");
     return 0;
 }

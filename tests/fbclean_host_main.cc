@@ -4,16 +4,11 @@
 // sizes, so under -fsanitize=address,undefined a work() that passes a wrong count or a short buffer is caught -- and records what it
 // was handed.
 #include <clenabled/clenabled.h>
-#include <mi355_clenabled.h>
+#include "host_stub.h"
 
 #include <cmath>
-#include <cstdio>
-#include <cstring>
-#include <stdexcept>
-#include <string>
 #include <vector>
 
-struct mi355_ctx { int dev; };
 struct mi355_fbclean {
     int R, F, Tb, generic;
     double nd, lo, hi, td;
@@ -22,9 +17,6 @@ struct mi355_fbclean {
     bool had_cflags, had_tflags, had_stats;
     std::vector<uint8_t> mask;
 };
-
-static std::string g_err;
-static int g_live_ctx = 0, g_live_handles = 0;
 
 static int stub_plan(int R, int F, int Tb, long long *a, long long *b, long long *c)
 {
@@ -41,16 +33,6 @@ static int stub_plan(int R, int F, int Tb, long long *a, long long *b, long long
 static bool stub_limits_ok(double nd, double lo, double hi, double td, int z) { return std::isfinite(nd) && nd > 0 && lo <= hi && td >= 0 && (z == 0 || z == 1); }
 
 extern "C" {
-const char *mi355_strerror(int code) { return code == MI355_ERR_INVALID_ARG ? "invalid argument" : code == MI355_ERR_NO_DEVICE ? "no device" : "error"; }
-const char *mi355_last_error(void) { return g_err.c_str(); }
-int mi355_ctx_create(int, int, int, int dev_id, int, mi355_ctx **out)
-{
-    if (dev_id == 99) { g_err = "no such device"; return MI355_ERR_NO_DEVICE; }
-    *out = new mi355_ctx{dev_id};
-    g_live_ctx++;
-    return MI355_OK;
-}
-int mi355_ctx_destroy(mi355_ctx *ctx) { delete ctx; g_live_ctx--; return MI355_OK; }
 int mi355_fbclean_plan(int R, int F, int Tb, long long *a, long long *b, long long *c) { return stub_plan(R, F, Tb, a, b, c); }
 int mi355_fbclean_create(mi355_ctx *ctx, int R, int F, int Tb, double nd, double lo, double hi, double td, int z, const uint8_t *mask, mi355_fbclean **out)
 {
@@ -109,14 +91,6 @@ int mi355_fbclean_work(mi355_fbclean *h, long long n, const void *in, void *out,
 }
 }
 
-#define CHECK(c)                                                      \
-    do {                                                              \
-        if (!(c)) {                                                   \
-            fprintf(stderr, "line %d: %s\n", __LINE__, #c);           \
-            return 1;                                                 \
-        }                                                             \
-    } while (0)
-
 using gr::clenabled::clFilterbankCleaner;
 
 // one work() call on exact-size heap buffers, as the scheduler makes it, with `nout` output streams; returns what work() returned, or
@@ -166,18 +140,14 @@ static int run(int R, int F, int Tb)
     // set_limits: a refused update keeps the old values
     fc->set_limits(8.0, 0.25, 2.0, 3.0, false);
     CHECK(fc->limits() == (std::vector<double>{8.0, 0.25, 2.0, 3.0, 0.0}));
-    bool threw = false;
-    try { fc->set_limits(0.0, 0.25, 2.0, 3.0, false); } catch (const std::invalid_argument &) { threw = true; }
-    CHECK(threw && fc->limits() == (std::vector<double>{8.0, 0.25, 2.0, 3.0, 0.0}));
+    CHECK(throws<std::invalid_argument>([&] { fc->set_limits(0.0, 0.25, 2.0, 3.0, false); }));
+    CHECK(fc->limits() == (std::vector<double>{8.0, 0.25, 2.0, 3.0, 0.0}));
     // set_mask: the size is checked by the block
     std::vector<uint8_t> m2((size_t)F, 1);
     fc->set_mask(m2);
     CHECK(fc->mask() == m2);
-    for (size_t bad : {(size_t)0, (size_t)F - 1, (size_t)F + 1}) {
-        threw = false;
-        try { fc->set_mask(std::vector<uint8_t>(bad, 0)); } catch (const std::invalid_argument &) { threw = true; }
-        CHECK(threw && fc->mask() == m2);
-    }
+    for (size_t bad : {(size_t)0, (size_t)F - 1, (size_t)F + 1})
+        CHECK(throws<std::invalid_argument>([&] { fc->set_mask(std::vector<uint8_t>(bad, 0)); }) && fc->mask() == m2);
     // no mask and no limits at make(): nothing masked, every test disabled
     auto z = clFilterbankCleaner::make(1, 2, 0, 0, R, F, Tb);
     CHECK(z->mask() == std::vector<uint8_t>((size_t)F, 0));
@@ -195,20 +165,12 @@ int main()
     CHECK(g_live_ctx == 0 && g_live_handles == 0);
     // argument errors throw std::invalid_argument before any device work (device 99 does not exist); a missing device is a runtime error
     const std::vector<std::vector<int>> bad = {{0, 8, 16}, {4097, 8, 16}, {2, 0, 16}, {2, 16385, 16}, {2, 8, 0}, {2, 8, 24}, {2, 8, 4112}};
-    for (const auto &s : bad) {
-        bool threw = false;
-        try { clFilterbankCleaner::make(1, 2, 0, 99, s[0], s[1], s[2]); } catch (const std::invalid_argument &) { threw = true; }
-        CHECK(threw);
-    }
-    bool threw = false;
-    try { clFilterbankCleaner::make(1, 2, 0, 99, 2, 8, 16, 1.0, 0.0, 2.0, 1.0, false, std::vector<uint8_t>(7, 0)); } catch (const std::invalid_argument &) { threw = true; }
-    CHECK(threw);  // a mask of the wrong size, before the device is looked for
-    threw = false;
-    try { clFilterbankCleaner::make(1, 2, 0, 99, 2, 8, 16); } catch (const std::invalid_argument &) { } catch (const std::runtime_error &e) { threw = strstr(e.what(), "no such device") != nullptr; }
-    CHECK(threw && g_live_ctx == 0);
-    threw = false;
-    try { clFilterbankCleaner::make(1, 2, 0, 0, 2, 8, 16, -1.0); } catch (const std::invalid_argument &) { threw = true; }
-    CHECK(threw && g_live_ctx == 0 && g_live_handles == 0);  // a refused create gives the context back
+    for (const auto &s : bad) CHECK(throws<std::invalid_argument>([&] { clFilterbankCleaner::make(1, 2, 0, 99, s[0], s[1], s[2]); }));
+    // a mask of the wrong size, before the device is looked for
+    CHECK(throws<std::invalid_argument>([] { clFilterbankCleaner::make(1, 2, 0, 99, 2, 8, 16, 1.0, 0.0, 2.0, 1.0, false, std::vector<uint8_t>(7, 0)); }));
+    CHECK(throws<std::runtime_error>([] { clFilterbankCleaner::make(1, 2, 0, 99, 2, 8, 16); }, "no such device") && g_live_ctx == 0);
+    // a refused create gives the context back
+    CHECK(throws<std::invalid_argument>([] { clFilterbankCleaner::make(1, 2, 0, 0, 2, 8, 16, -1.0); }) && g_live_ctx == 0 && g_live_handles == 0);
     printf("fbclean host ok\n");
     return 0;
 }

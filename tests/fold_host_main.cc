@@ -4,15 +4,10 @@
 // sizes, so under -fsanitize=address,undefined a work() that passes a wrong count or a short buffer is caught -- and records what it
 // was handed.
 #include <clenabled/clenabled.h>
-#include <mi355_clenabled.h>
+#include "host_stub.h"
 
-#include <cstdio>
-#include <cstring>
-#include <stdexcept>
-#include <string>
 #include <vector>
 
-struct mi355_ctx { int dev; };
 struct mi355_fold {
     int R, F, nbin, Ts, generic;
     unsigned long long T0;
@@ -20,9 +15,6 @@ struct mi355_fold {
     bool had_tflags, had_hits;
     std::vector<uint64_t> models;
 };
-
-static std::string g_err;
-static int g_live_ctx = 0, g_live_handles = 0;
 
 static int stub_plan(int R, int F, int nbin, int Ts, long long *a, long long *b, long long *c)
 {
@@ -37,16 +29,6 @@ static int stub_plan(int R, int F, int nbin, int Ts, long long *a, long long *b,
 }
 
 extern "C" {
-const char *mi355_strerror(int code) { return code == MI355_ERR_INVALID_ARG ? "invalid argument" : code == MI355_ERR_NO_DEVICE ? "no device" : "error"; }
-const char *mi355_last_error(void) { return g_err.c_str(); }
-int mi355_ctx_create(int, int, int, int dev_id, int, mi355_ctx **out)
-{
-    if (dev_id == 99) { g_err = "no such device"; return MI355_ERR_NO_DEVICE; }
-    *out = new mi355_ctx{dev_id};
-    g_live_ctx++;
-    return MI355_OK;
-}
-int mi355_ctx_destroy(mi355_ctx *ctx) { delete ctx; g_live_ctx--; return MI355_OK; }
 int mi355_fold_plan(int R, int F, int nbin, int Ts, long long *a, long long *b, long long *c) { return stub_plan(R, F, nbin, Ts, a, b, c); }
 int mi355_fold_create(mi355_ctx *ctx, int R, int F, int nbin, int Ts, const uint64_t *models, mi355_fold **out)
 {
@@ -105,14 +87,6 @@ int mi355_fold_work(mi355_fold *h, long long n, const void *in, const void *tfla
 }
 }
 
-#define CHECK(c)                                                      \
-    do {                                                              \
-        if (!(c)) {                                                   \
-            fprintf(stderr, "line %d: %s\n", __LINE__, #c);           \
-            return 1;                                                 \
-        }                                                             \
-    } while (0)
-
 using gr::clenabled::clFolder;
 
 // one work() call for ns output items on exact-size heap buffers, as the scheduler makes it, with `nin` input and `nout` output streams;
@@ -166,9 +140,7 @@ static int run(int R, int F, int nbin, int Ts)
     fo->set_sample(UINT64_MAX - 5);
     fo->skip(10);
     CHECK(fo->sample() == 4);  // the counter wraps
-    bool threw = false;
-    try { fo->skip(-1); } catch (const std::invalid_argument &) { threw = true; }
-    CHECK(threw && fo->sample() == 4);
+    CHECK(throws<std::invalid_argument>([&] { fo->skip(-1); }) && fo->sample() == 4);
     fo->set_generic(true);
     CHECK(fo->route() == "generic stub");
     // set_models: the size is checked by the block, and a refused update keeps the old table
@@ -176,13 +148,9 @@ static int run(int R, int F, int nbin, int Ts)
     fo->set_models(m2);
     CHECK(fo->models() == m2);
     for (size_t bad : {(size_t)0, models.size() - 1, models.size() + 1}) {
-        threw = false;
-        try { fo->set_models(std::vector<uint64_t>(bad, 0)); } catch (const std::invalid_argument &) { threw = true; }
-        CHECK(threw && fo->models() == m2);
+        CHECK(throws<std::invalid_argument>([&] { fo->set_models(std::vector<uint64_t>(bad, 0)); }) && fo->models() == m2);
     }
-    threw = false;
-    try { fo->set_models(std::vector<uint64_t>(models.size(), UINT64_MAX)); } catch (const std::invalid_argument &) { threw = true; }
-    CHECK(threw && fo->models() == m2);  // the library refused it
+    CHECK(throws<std::invalid_argument>([&] { fo->set_models(std::vector<uint64_t>(models.size(), UINT64_MAX)); }) && fo->models() == m2);  // the library refused it
     // the message port: a table of the right size is installed, any other message is dropped without a throw
     CHECK(fo->post_u64vector("models", models) && fo->models() == models);
     CHECK(fo->post_u64vector("models", std::vector<uint64_t>(models.size() + 3, 1)) && fo->models() == models);
@@ -201,20 +169,13 @@ int main()
     const std::vector<uint64_t> m(6, 0);
     const std::vector<std::vector<int>> bad = {{0, 8, 4, 16}, {4097, 8, 4, 16}, {2, 0, 4, 16}, {2, 16385, 4, 16}, {2, 8, 1, 16}, {2, 8, 4097, 16},
                                                {2, 8, 4, 0}, {2, 8, 4, 24}, {2, 8, 4, 16400}};
-    for (const auto &s : bad) {
-        bool threw = false;
-        try { clFolder::make(1, 2, 0, 99, s[0], s[1], s[2], s[3], m); } catch (const std::invalid_argument &) { threw = true; }
-        CHECK(threw);
-    }
-    bool threw = false;
-    try { clFolder::make(1, 2, 0, 99, 2, 8, 4, 16, std::vector<uint64_t>(5, 0)); } catch (const std::invalid_argument &) { threw = true; }
-    CHECK(threw);  // models of the wrong size, before the device is looked for
-    threw = false;
-    try { clFolder::make(1, 2, 0, 99, 2, 8, 4, 16, m); } catch (const std::invalid_argument &) { } catch (const std::runtime_error &e) { threw = strstr(e.what(), "no such device") != nullptr; }
-    CHECK(threw && g_live_ctx == 0);
-    threw = false;
-    try { clFolder::make(1, 2, 0, 0, 4096, 16384, 4096, 16, std::vector<uint64_t>(3 * 4096, 0)); } catch (const std::invalid_argument &) { threw = true; }
-    CHECK(threw && g_live_ctx == 0 && g_live_handles == 0);  // an output item of 2 GiB or more is no stream item
+    for (const auto &s : bad) CHECK(throws<std::invalid_argument>([&] { clFolder::make(1, 2, 0, 99, s[0], s[1], s[2], s[3], m); }));
+    // models of the wrong size, before the device is looked for
+    CHECK(throws<std::invalid_argument>([&] { clFolder::make(1, 2, 0, 99, 2, 8, 4, 16, std::vector<uint64_t>(5, 0)); }));
+    CHECK(throws<std::runtime_error>([&] { clFolder::make(1, 2, 0, 99, 2, 8, 4, 16, m); }, "no such device") && g_live_ctx == 0);
+    // an output item of 2 GiB or more is no stream item
+    CHECK(throws<std::invalid_argument>([&] { clFolder::make(1, 2, 0, 0, 4096, 16384, 4096, 16, std::vector<uint64_t>(3 * 4096, 0)); }));
+    CHECK(g_live_ctx == 0 && g_live_handles == 0);
     printf("fold host ok\n");
     return 0;
 }

@@ -3,6 +3,7 @@
 #include <gnuradio/logger.h>
 #include <gnuradio/types.h>
 #include <pmt/pmt.h>
+#include <functional>
 #include <memory>
 #include <string>
 namespace gr {
@@ -20,6 +21,7 @@ public:
     void message_port_register_in(pmt::pmt_t port_id);
     void message_port_register_out(pmt::pmt_t port_id);
     void message_port_pub(pmt::pmt_t port_id, pmt::pmt_t msg);
+    void set_msg_handler(pmt::pmt_t which_port, std::function<void(pmt::pmt_t)> msg_handler);
     virtual void setup_rpc() {}
 };
 typedef std::shared_ptr<basic_block> basic_block_sptr;

@@ -16,6 +16,7 @@ public:
     virtual bool stop();
     void set_output_multiple(int multiple);
     int output_multiple() const;
+    void set_relative_rate(uint64_t interpolation, uint64_t decimation);
     void consume(int which_input, int how_many_items);
     void consume_each(int how_many_items);
     void produce(int which_output, int how_many_items);

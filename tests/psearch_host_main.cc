@@ -3,23 +3,15 @@
 // (n / Tb x R D) -- the test hands it heap buffers of exactly that size, so under -fsanitize=address,undefined a work() that passes a
 // sample too few or the wrong count is caught -- and records what it was handed.
 #include <clenabled/clenabled.h>
-#include <mi355_clenabled.h>
+#include "host_stub.h"
 
-#include <cstdio>
-#include <cstring>
-#include <stdexcept>
-#include <string>
 #include <vector>
 
-struct mi355_ctx { int dev; };
 struct mi355_psearch {
     int R, D, K, Tb, order, generic;
     long long calls, last_n, last_pitch;
     std::vector<float> mean, isg;
 };
-
-static std::string g_err;
-static int g_live_ctx = 0, g_live_handles = 0;
 
 static int stub_plan(int R, int D, int K, int Tb, int order, long long *fi, long long *hi, long long *pb)
 {
@@ -34,16 +26,6 @@ static int stub_plan(int R, int D, int K, int Tb, int order, long long *fi, long
 }
 
 extern "C" {
-const char *mi355_strerror(int code) { return code == MI355_ERR_INVALID_ARG ? "invalid argument" : code == MI355_ERR_NO_DEVICE ? "no device" : "error"; }
-const char *mi355_last_error(void) { return g_err.c_str(); }
-int mi355_ctx_create(int, int, int, int dev_id, int, mi355_ctx **out)
-{
-    if (dev_id == 99) { g_err = "no such device"; return MI355_ERR_NO_DEVICE; }
-    *out = new mi355_ctx{dev_id};
-    g_live_ctx++;
-    return MI355_OK;
-}
-int mi355_ctx_destroy(mi355_ctx *ctx) { delete ctx; g_live_ctx--; return MI355_OK; }
 int mi355_psearch_plan(int R, int D, int K, int Tb, int order, long long *fi, long long *hi, long long *pb) { return stub_plan(R, D, K, Tb, order, fi, hi, pb); }
 int mi355_psearch_create(mi355_ctx *ctx, int R, int D, int K, int Tb, int order, const float *mean, const float *isg, mi355_psearch **out)
 {
@@ -87,14 +69,6 @@ int mi355_psearch_work(mi355_psearch *h, long long n, const void *in, long long 
 }
 }
 
-#define CHECK(c)                                                      \
-    do {                                                              \
-        if (!(c)) {                                                   \
-            fprintf(stderr, "line %d: %s\n", __LINE__, #c);           \
-            return 1;                                                 \
-        }                                                             \
-    } while (0)
-
 using gr::clenabled::clPulseSearch;
 
 // one work() call on exact-size heap buffers, as the scheduler makes it: n decimation + history() - 1 input items; returns what
@@ -137,12 +111,8 @@ static int run(int R, int D, int K, int Tb)
     ps->set_stats(m2, g2);
     CHECK(ps->mean() == m2 && ps->inv_sigma() == g2);
     for (size_t bad : {(size_t)0, S - 1, S + 1, 2 * S}) {
-        bool threw = false;
-        try { ps->set_stats(std::vector<float>(bad, 0.f), g2); } catch (const std::invalid_argument &) { threw = true; }
-        CHECK(threw && ps->mean() == m2 && ps->inv_sigma() == g2);
-        threw = false;
-        try { ps->set_stats(m2, std::vector<float>(bad, 0.f)); } catch (const std::invalid_argument &) { threw = true; }
-        CHECK(threw && ps->mean() == m2 && ps->inv_sigma() == g2);
+        CHECK(throws<std::invalid_argument>([&] { ps->set_stats(std::vector<float>(bad, 0.f), g2); }) && ps->mean() == m2 && ps->inv_sigma() == g2);
+        CHECK(throws<std::invalid_argument>([&] { ps->set_stats(m2, std::vector<float>(bad, 0.f)); }) && ps->mean() == m2 && ps->inv_sigma() == g2);
     }
     CHECK(call(*ps, 3, ++calls) == 3);
     // no statistics at make(): mean 0, inv_sigma 1
@@ -161,17 +131,10 @@ int main()
     // argument errors throw std::invalid_argument before any device work (device 99 does not exist); a missing device is a runtime error
     const std::vector<std::vector<int>> bad = {{0, 8, 4, 16}, {4097, 8, 4, 16}, {2, 0, 4, 16}, {2, 4097, 4, 16}, {2, 8, 0, 16}, {2, 8, 14, 16}, {2, 8, 4, 15},
                                                {2, 8, 4, 1 << 24}};
-    for (const auto &s : bad) {
-        bool threw = false;
-        try { clPulseSearch::make(1, 2, 0, 99, s[0], s[1], s[2], s[3]); } catch (const std::invalid_argument &) { threw = true; }
-        CHECK(threw);
-    }
-    bool threw = false;
-    try { clPulseSearch::make(1, 2, 0, 99, 2, 8, 4, 16, std::vector<float>(7, 0.f)); } catch (const std::invalid_argument &) { threw = true; }
-    CHECK(threw);  // statistics of the wrong size, before the device is looked for
-    threw = false;
-    try { clPulseSearch::make(1, 2, 0, 99, 2, 8, 4, 16); } catch (const std::invalid_argument &) { } catch (const std::runtime_error &e) { threw = strstr(e.what(), "no such device") != nullptr; }
-    CHECK(threw && g_live_ctx == 0);
+    for (const auto &s : bad) CHECK(throws<std::invalid_argument>([&] { clPulseSearch::make(1, 2, 0, 99, s[0], s[1], s[2], s[3]); }));
+    // statistics of the wrong size, before the device is looked for
+    CHECK(throws<std::invalid_argument>([] { clPulseSearch::make(1, 2, 0, 99, 2, 8, 4, 16, std::vector<float>(7, 0.f)); }));
+    CHECK(throws<std::runtime_error>([] { clPulseSearch::make(1, 2, 0, 99, 2, 8, 4, 16); }, "no such device") && g_live_ctx == 0);
     printf("psearch host ok\n");
     return 0;
 }

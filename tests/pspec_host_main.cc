@@ -4,30 +4,14 @@
 // spectrum too many is caught -- and returns P[s][b] = s + b / 1024 so that the caller can tell which spectra were made.  The caller
 // declares what it offers (set_offered): a consume of more than that throws, as GNU Radio's buffer accounting would break.
 #include <clenabled/clenabled.h>
-#include <mi355_clenabled.h>
+#include "host_stub.h"
 
 #include <algorithm>
-#include <cstdio>
-#include <cstring>
-#include <stdexcept>
-#include <string>
 #include <vector>
 
-struct mi355_ctx { int dev; };
 struct mi355_pspec { int N, K, H; float scale; int generic; long long calls; std::vector<float> window; };
 
-static std::string g_err;
-
 extern "C" {
-const char *mi355_strerror(int code) { return code == MI355_ERR_INVALID_ARG ? "invalid argument" : code == MI355_ERR_NO_DEVICE ? "no device" : "error"; }
-const char *mi355_last_error(void) { return g_err.c_str(); }
-int mi355_ctx_create(int, int, int, int dev_id, int, mi355_ctx **out)
-{
-    if (dev_id == 99) { g_err = "no such device"; return MI355_ERR_NO_DEVICE; }
-    *out = new mi355_ctx{dev_id};
-    return MI355_OK;
-}
-int mi355_ctx_destroy(mi355_ctx *ctx) { delete ctx; return MI355_OK; }
 int mi355_pspec_plan(int N, int K, int H, long long S, long long *nin, long long *nout)
 {
     if (N < 1 || K < 1 || H < 1 || S < 0) { g_err = "invalid argument: stub"; return MI355_ERR_INVALID_ARG; }
@@ -67,14 +51,6 @@ int mi355_pspec_work(mi355_pspec *h, long long S, const void *in, void *out)
 }
 }
 
-#define CHECK(c)                                                      \
-    do {                                                              \
-        if (!(c)) {                                                   \
-            fprintf(stderr, "line %d: %s\n", __LINE__, #c);           \
-            return 1;                                                 \
-        }                                                             \
-    } while (0)
-
 using gr::clenabled::clPowerSpectrum;
 
 static int run(int N, int K, int H)
@@ -87,9 +63,7 @@ static int run(int N, int K, int H)
     ps->set_scale(3.0f);
     ps->set_window(std::vector<float>());
     ps->set_window(std::vector<float>((size_t)N, 1.0f));
-    bool threw = false;
-    try { ps->set_window(std::vector<float>((size_t)N + 1, 1.0f)); } catch (const std::invalid_argument &) { threw = true; }
-    CHECK(threw);
+    CHECK(throws<std::invalid_argument>([&] { ps->set_window(std::vector<float>((size_t)N + 1, 1.0f)); }));
     gr_vector_int req(1, -1);
     ps->forecast(3, req);
     CHECK(req[0] == std::max((3 * K - 1) * H + N, 3 * K * H));
@@ -140,9 +114,7 @@ static int run(int N, int K, int H)
     {
         ps->reset_consumed();
         ps->set_offered(gr_vector_int(1, K * H - 1));
-        bool refused = false;
-        try { ps->consume_each(K * H); } catch (const std::logic_error &) { refused = true; }
-        CHECK(refused);
+        CHECK(throws<std::logic_error>([&] { ps->consume_each(K * H); }));
         ps->reset_consumed();
     }
     return 0;
@@ -155,20 +127,11 @@ int main()
         if (rc) return rc;
     }
     // argument errors throw std::invalid_argument before any device work; what clFFT refuses and a missing device are runtime errors
-    for (auto bad : {std::vector<int>{0, 4, 4}, {64, 0, 64}, {64, 4, -1}}) {
-        bool threw = false;
-        try { clPowerSpectrum::make(1, 2, 0, 99, bad[0], bad[1], std::vector<float>(), bad[2]); } catch (const std::invalid_argument &) { threw = true; }
-        CHECK(threw);
-    }
-    bool threw = false;
-    try { clPowerSpectrum::make(1, 2, 0, 0, 64, 4, std::vector<float>(63, 1.f)); } catch (const std::invalid_argument &) { threw = true; }
-    CHECK(threw);
-    threw = false;
-    try { clPowerSpectrum::make(1, 2, 0, 0, 1, 4); } catch (const std::invalid_argument &) { } catch (const std::runtime_error &e) { threw = strstr(e.what(), "fft size 1") != nullptr; }
-    CHECK(threw);
-    threw = false;
-    try { clPowerSpectrum::make(1, 2, 0, 99, 64, 4); } catch (const std::invalid_argument &) { } catch (const std::runtime_error &e) { threw = strstr(e.what(), "no such device") != nullptr; }
-    CHECK(threw);
+    for (auto bad : {std::vector<int>{0, 4, 4}, {64, 0, 64}, {64, 4, -1}})
+        CHECK(throws<std::invalid_argument>([&] { clPowerSpectrum::make(1, 2, 0, 99, bad[0], bad[1], std::vector<float>(), bad[2]); }));
+    CHECK(throws<std::invalid_argument>([] { clPowerSpectrum::make(1, 2, 0, 0, 64, 4, std::vector<float>(63, 1.f)); }));
+    CHECK(throws<std::runtime_error>([] { clPowerSpectrum::make(1, 2, 0, 0, 1, 4); }, "fft size 1"));
+    CHECK(throws<std::runtime_error>([] { clPowerSpectrum::make(1, 2, 0, 99, 64, 4); }, "no such device"));
     printf("pspec host ok\n");
     return 0;
 }

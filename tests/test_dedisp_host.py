@@ -2,42 +2,24 @@
 bookkeeping (io signature, item sizes, history, what work() hands the library, set_delays size checks, a refused update keeping the old
 table) runs on the CPU over a stub of the C ABI under AddressSanitizer and UBSan (tests/dedisp_host_main.cc): a program of its own,
 nothing loaded into python.  The pybind class and the CLI row run on the GPU in tests/test_dedisp_gpu.py."""
-import os
-import subprocess
-
-from conftest import ROOT
-
-HOST = os.path.join(ROOT, "gr-clenabled_amd", "host")
-INCLUDE = os.path.join(HOST, "include")
-UNIT = os.path.join(HOST, "lib", "clDedisperser_impl.cc")
+import host_layer
 
 
 def test_unit_compiles_alone():
-    r = subprocess.run(["g++", "-std=c++17", "-Wall", "-Wextra", "-fsyntax-only", "-I", INCLUDE, "-I", os.path.join(ROOT, "include"), UNIT],
-                       capture_output=True, text=True)
-    assert r.returncode == 0 and "warning" not in r.stderr, r.stderr
+    host_layer.unit_compiles_alone("clDedisperser")
 
 
 def test_make_signature(tmp_path):
-    src = tmp_path / "probe.cc"
-    src.write_text("#include <clenabled/clenabled.h>\n"
-                   "using namespace gr::clenabled;\n"
-                   "clDedisperser::sptr (*f)(int, int, int, int, int, int, int, int, const std::vector<int32_t> &, int) = &clDedisperser::make;\n"
-                   "clDedisperser::sptr eight() { return clDedisperser::make(1, 2, 0, 0, 64, 1024, 1024, 1000); }\n"
-                   "std::string probe(clDedisperser &p) { p.set_delays(p.delays()); p.set_generic(false);\n"
-                   "  gr::sync_block &b = p; return p.route() + std::to_string(p.max_delay() + b.history()); }\n"
-                   "int main() { return 0; }\n")
-    r = subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-Wno-unused-variable", "-fsyntax-only", "-I", INCLUDE,
-                        "-I", os.path.join(ROOT, "include"), str(src)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    host_layer.probe_compiles(tmp_path,
+                              "#include <clenabled/clenabled.h>\n"
+                              "using namespace gr::clenabled;\n"
+                              "clDedisperser::sptr (*f)(int, int, int, int, int, int, int, int, const std::vector<int32_t> &, int) = &clDedisperser::make;\n"
+                              "clDedisperser::sptr eight() { return clDedisperser::make(1, 2, 0, 0, 64, 1024, 1024, 1000); }\n"
+                              "std::string probe(clDedisperser &p) { p.set_delays(p.delays()); p.set_generic(false);\n"
+                              "  gr::sync_block &b = p; return p.route() + std::to_string(p.max_delay() + b.history()); }\n"
+                              "int main() { return 0; }\n")
 
 
 def test_block_bookkeeping_under_sanitizers(tmp_path):
     """host code only, a program of its own: no device, nothing loaded into python"""
-    exe = tmp_path / "dedisp_host"
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                        "-I", INCLUDE, "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "dedisp_host_main.cc"), UNIT,
-                        "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "dedisp host ok" in r.stdout, r.stdout + r.stderr
+    host_layer.runs_under_sanitizers(tmp_path, "dedisp", ["clDedisperser"])

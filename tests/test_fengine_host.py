@@ -3,46 +3,32 @@ clenabled.h declares, and a program of its own (tests/fengine_host_main.cc) call
 context, the NULL-handle forms and the argument errors of clFEngine::make under AddressSanitizer and UBSan -- linked against the built
 library, nothing loaded into python, no device.  The pybind class and the CLI row run on the GPU in tests/test_fengine_gpu.py."""
 import os
-import subprocess
 
+import host_layer
 from conftest import ROOT
 
 PKG = os.path.join(ROOT, "gr-clenabled_amd")
-HOST = os.path.join(PKG, "host")
-INCLUDE = os.path.join(HOST, "include")
-UNIT = os.path.join(HOST, "lib", "clFEngine_impl.cc")
 
 
 def test_unit_compiles_alone():
-    r = subprocess.run(["g++", "-std=c++17", "-Wall", "-Wextra", "-fsyntax-only", "-I", INCLUDE, "-I", os.path.join(ROOT, "include"), UNIT],
-                       capture_output=True, text=True)
-    assert r.returncode == 0 and "warning" not in r.stderr, r.stderr
+    host_layer.unit_compiles_alone("clFEngine")
 
 
 def test_make_signature(tmp_path):
-    src = tmp_path / "probe.cc"
-    src.write_text("#include <clenabled/clenabled.h>\n"
-                   "using namespace gr::clenabled;\n"
-                   "clFEngine::sptr (*f)(int, int, int, int, int, int, int, const std::vector<float> &, int, bool, const std::vector<float> &, int) = "
-                   "&clFEngine::make;\n"
-                   "clFEngine::sptr seven() { return clFEngine::make(1, 2, 0, 0, 2, 64, 1024); }\n"
-                   "std::string probe(clFEngine &p) { p.set_gains(p.gains()); p.set_input_gain(0, std::vector<float>()); p.set_generic(false);\n"
-                   "  gr::sync_decimator &d = p; std::vector<uint64_t> c = p.clips(true);\n"
-                   "  return p.route() + std::to_string(c.size() + p.frame_bytes() + d.decimation() + d.history()); }\n"
-                   "int main() { return 0; }\n")
-    r = subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-Wno-unused-variable", "-fsyntax-only", "-I", INCLUDE,
-                        "-I", os.path.join(ROOT, "include"), str(src)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    host_layer.probe_compiles(tmp_path,
+                              "#include <clenabled/clenabled.h>\n"
+                              "using namespace gr::clenabled;\n"
+                              "clFEngine::sptr (*f)(int, int, int, int, int, int, int, const std::vector<float> &, int, bool, const std::vector<float> &, int) = "
+                              "&clFEngine::make;\n"
+                              "clFEngine::sptr seven() { return clFEngine::make(1, 2, 0, 0, 2, 64, 1024); }\n"
+                              "std::string probe(clFEngine &p) { p.set_gains(p.gains()); p.set_input_gain(0, std::vector<float>()); p.set_generic(false);\n"
+                              "  gr::sync_decimator &d = p; std::vector<uint64_t> c = p.clips(true);\n"
+                              "  return p.route() + std::to_string(c.size() + p.frame_bytes() + d.decimation() + d.history()); }\n"
+                              "int main() { return 0; }\n")
 
 
 def test_device_free_entry_points_under_sanitizers(pkg, tmp_path):
     """host code only, a program of its own: no device, nothing loaded into python"""
     assert os.path.exists(pkg.LIB_PATH)
-    exe = tmp_path / "fengine_host"
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                        "-I", INCLUDE, "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "fengine_host_main.cc"), UNIT,
-                        "-L", PKG, "-lmi355_clenabled", "-Wl,-rpath," + PKG, "-Wl,-rpath,/opt/rocm/lib", "-o", str(exe)],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "fengine host ok" in r.stdout, r.stdout + r.stderr
+    host_layer.runs_under_sanitizers(tmp_path, "fengine", ["clFEngine"],
+                                     extra=["-L", PKG, "-lmi355_clenabled", "-Wl,-rpath," + PKG, "-Wl,-rpath,/opt/rocm/lib"])

@@ -78,11 +78,17 @@ def test_public_header_set_is_the_reference_set_for_the_path():
     assert set(PUBLIC_HEADERS) | {"clenabled.h", "gr_compat.h"} == have
 
 
-@pytest.mark.parametrize("unit", ["lib/clenabled_impl.cc", "python/bindings/python_bindings.cc", "apps/test_clenabled.cc"])
+BLOCK_UNITS = ["clXCorrelate", "clSignalSource", "clCostasLoop", "clRationalResampler", "clPolyphaseSynthesizer", "clPowerSpectrum",
+               "clFreqXlatingFIRFilter", "clBeamformer", "clFEngine", "clDedisperser", "clPulseSearch", "clFilterbankCleaner", "clFolder"]
+
+
+@pytest.mark.parametrize("unit", ["lib/clenabled_impl.cc", "python/bindings/python_bindings.cc", "apps/test_clenabled.cc"] +
+                         ["lib/%s_impl.cc" % b for b in BLOCK_UNITS])
 def test_gnuradio_branch_compiles_against_the_api_model(unit):
-    """-DMI355_WITH_GNURADIO: the code a GNU Radio installation would compile (real gr::block bases, pmt, logger, tags) is at least
-    type-checked here, against tests/gr_api_mock/ -- declarations of GNU Radio 3.10's documented block API with its access levels
-    (get_tags_in_window protected, block constructors protected ...).  Not a GNU Radio build; see tests/gr_api_mock/README.md."""
+    """-DMI355_WITH_GNURADIO: the code a GNU Radio installation would compile (real gr::block bases, pmt, logger, tags, message ports)
+    is at least type-checked here, every unit of host/lib/ included, against tests/gr_api_mock/ -- declarations of GNU Radio 3.10's
+    documented block API with its access levels (get_tags_in_window protected, block constructors protected ...).  Not a GNU Radio
+    build; see tests/gr_api_mock/README.md."""
     import sysconfig
     inc = ["-I", os.path.join(ROOT, "tests", "gr_api_mock"), "-I", INCLUDE, "-I", os.path.join(ROOT, "include")]
     if unit.startswith("python"):

@@ -9,46 +9,31 @@ import subprocess
 import numpy as np
 import pytest
 
+import host_layer
 from conftest import GPU_ARGS, ROOT, relerr
 import pspec_ref as ref
 
-HOST = os.path.join(ROOT, "gr-clenabled_amd", "host")
-INCLUDE = os.path.join(HOST, "include")
-UNIT = os.path.join(HOST, "lib", "clPowerSpectrum_impl.cc")
 CLI = os.path.join(ROOT, "gr-clenabled_amd", "test-clenabled-mi355")
 
 
 def test_unit_compiles_alone():
-    """(the stand-alone block layer of clenabled/gr_compat.h; the GNU Radio API model under tests/gr_api_mock declares no
-    set_relative_rate, which this block -- like clRationalResampler and clPolyphaseSynthesizer -- calls)"""
-    r = subprocess.run(["g++", "-std=c++17", "-Wall", "-Wextra", "-fsyntax-only", "-I", INCLUDE, "-I", os.path.join(ROOT, "include"), UNIT],
-                       capture_output=True, text=True)
-    assert r.returncode == 0 and "warning" not in r.stderr, r.stderr
+    host_layer.unit_compiles_alone("clPowerSpectrum")
 
 
 def test_make_signature(tmp_path):
-    src = tmp_path / "probe.cc"
-    src.write_text("#include <clenabled/clenabled.h>\n"
-                   "using namespace gr::clenabled;\n"
-                   "clPowerSpectrum::sptr (*f)(int, int, int, int, int, int, const std::vector<float> &, int, bool, bool, float, int) = &clPowerSpectrum::make;\n"
-                   "clPowerSpectrum::sptr six() { return clPowerSpectrum::make(1, 2, 0, 0, 1024, 16); }\n"
-                   "std::string probe(clPowerSpectrum &p) { p.set_scale(1.f); p.set_window({}); p.set_generic(false);\n"
-                   "  return p.route() + std::to_string(p.fft_size() + p.navg() + p.hop()); }\n"
-                   "int main() { return 0; }\n")
-    r = subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-Wno-unused-variable", "-fsyntax-only", "-I", INCLUDE,
-                        "-I", os.path.join(ROOT, "include"), str(src)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    host_layer.probe_compiles(tmp_path,
+                              "#include <clenabled/clenabled.h>\n"
+                              "using namespace gr::clenabled;\n"
+                              "clPowerSpectrum::sptr (*f)(int, int, int, int, int, int, const std::vector<float> &, int, bool, bool, float, int) = &clPowerSpectrum::make;\n"
+                              "clPowerSpectrum::sptr six() { return clPowerSpectrum::make(1, 2, 0, 0, 1024, 16); }\n"
+                              "std::string probe(clPowerSpectrum &p) { p.set_scale(1.f); p.set_window({}); p.set_generic(false);\n"
+                              "  return p.route() + std::to_string(p.fft_size() + p.navg() + p.hop()); }\n"
+                              "int main() { return 0; }\n")
 
 
 def test_block_bookkeeping_under_sanitizers(tmp_path):
     """host code only, a program of its own: no device, nothing loaded into python"""
-    exe = tmp_path / "pspec_host"
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                        "-I", INCLUDE, "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "pspec_host_main.cc"), UNIT,
-                        "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "pspec host ok" in r.stdout, r.stdout + r.stderr
+    host_layer.runs_under_sanitizers(tmp_path, "pspec", ["clPowerSpectrum"])
 
 
 def _pybind():

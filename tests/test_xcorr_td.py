@@ -74,9 +74,8 @@ def test_make_signature_compiles_against_clenabled_h(tmp_path):
 
 def test_gnuradio_branch_of_the_unit_compiles_against_the_api_model():
     """-DMI355_WITH_GNURADIO: the PDU is built with pmt::make_dict / dict_add / init_f32vector / init_s32vector (GNU Radio 3.10's pmt
-    API); tests/gr_api_mock/ does not declare those four, so their declarations are force-included from a file of this test."""
-    decls = os.path.join(ROOT, "tests", "gr_pmt_dict_decls.h")
-    r = subprocess.run(["g++", "-std=c++17", "-Wall", "-fsyntax-only", "-DMI355_WITH_GNURADIO", "-include", decls,
+    API, declared in tests/gr_api_mock/pmt/pmt.h) by sched::publish_corr_pdu of gr_compat.h."""
+    r = subprocess.run(["g++", "-std=c++17", "-Wall", "-fsyntax-only", "-DMI355_WITH_GNURADIO",
                         "-I", os.path.join(ROOT, "tests", "gr_api_mock"), "-I", INCLUDE, "-I", os.path.join(ROOT, "include"), UNIT],
                        capture_output=True, text=True)
     assert r.returncode == 0 and "warning" not in r.stderr, r.stderr

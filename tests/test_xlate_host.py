@@ -2,45 +2,27 @@
 block's bookkeeping (io signature, history, the "freq" message port, what work() hands the library, set_taps) runs on the CPU over a
 stub of the C ABI under AddressSanitizer and UBSan (tests/xlate_host_main.cc): a program of its own, nothing loaded into python.  The
 pybind class and the CLI rows run on the GPU in tests/test_xlate_gpu.py."""
-import os
-import subprocess
-
-from conftest import ROOT
-
-HOST = os.path.join(ROOT, "gr-clenabled_amd", "host")
-INCLUDE = os.path.join(HOST, "include")
-UNIT = os.path.join(HOST, "lib", "clFreqXlatingFIRFilter_impl.cc")
+import host_layer
 
 
 def test_unit_compiles_alone():
-    r = subprocess.run(["g++", "-std=c++17", "-Wall", "-Wextra", "-fsyntax-only", "-I", INCLUDE, "-I", os.path.join(ROOT, "include"), UNIT],
-                       capture_output=True, text=True)
-    assert r.returncode == 0 and "warning" not in r.stderr, r.stderr
+    host_layer.unit_compiles_alone("clFreqXlatingFIRFilter")
 
 
 def test_make_signature(tmp_path):
-    src = tmp_path / "probe.cc"
-    src.write_text("#include <clenabled/clenabled.h>\n"
-                   "using namespace gr::clenabled;\n"
-                   "clFreqXlatingFIRFilter::sptr (*f)(int, int, int, int, int, const std::vector<float> &, const std::vector<double> &, double, bool, int) = "
-                   "&clFreqXlatingFIRFilter::make;\n"
-                   "clFreqXlatingFIRFilter::sptr (*g)(int, int, int, int, int, const std::vector<gr_complex> &, const std::vector<double> &, double, bool, int) = "
-                   "&clFreqXlatingFIRFilter::make_ccc;\n"
-                   "clFreqXlatingFIRFilter::sptr eight() { return clFreqXlatingFIRFilter::make(1, 2, 0, 0, 16, {1.f, 2.f}, {1e3, -2e3}, 48e3); }\n"
-                   "std::string probe(clFreqXlatingFIRFilter &p) { p.set_center_freq(1.0); p.set_center_freq(2.0, 1); p.skip(5); p.set_generic(false);\n"
-                   "  p.set_taps(p.taps()); gr::sync_decimator &d = p; return p.route() + std::to_string(p.num_channels() + p.center_freq() + d.decimation()); }\n"
-                   "int main() { return 0; }\n")
-    r = subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-Wno-unused-variable", "-fsyntax-only", "-I", INCLUDE,
-                        "-I", os.path.join(ROOT, "include"), str(src)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    host_layer.probe_compiles(tmp_path,
+                              "#include <clenabled/clenabled.h>\n"
+                              "using namespace gr::clenabled;\n"
+                              "clFreqXlatingFIRFilter::sptr (*f)(int, int, int, int, int, const std::vector<float> &, const std::vector<double> &, double, bool, int) = "
+                              "&clFreqXlatingFIRFilter::make;\n"
+                              "clFreqXlatingFIRFilter::sptr (*g)(int, int, int, int, int, const std::vector<gr_complex> &, const std::vector<double> &, double, bool, int) = "
+                              "&clFreqXlatingFIRFilter::make_ccc;\n"
+                              "clFreqXlatingFIRFilter::sptr eight() { return clFreqXlatingFIRFilter::make(1, 2, 0, 0, 16, {1.f, 2.f}, {1e3, -2e3}, 48e3); }\n"
+                              "std::string probe(clFreqXlatingFIRFilter &p) { p.set_center_freq(1.0); p.set_center_freq(2.0, 1); p.skip(5); p.set_generic(false);\n"
+                              "  p.set_taps(p.taps()); gr::sync_decimator &d = p; return p.route() + std::to_string(p.num_channels() + p.center_freq() + d.decimation()); }\n"
+                              "int main() { return 0; }\n")
 
 
 def test_block_bookkeeping_under_sanitizers(tmp_path):
     """host code only, a program of its own: no device, nothing loaded into python"""
-    exe = tmp_path / "xlate_host"
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                        "-I", INCLUDE, "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "xlate_host_main.cc"), UNIT,
-                        "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "xlate host ok" in r.stdout, r.stdout + r.stderr
+    host_layer.runs_under_sanitizers(tmp_path, "xlate", ["clFreqXlatingFIRFilter"])

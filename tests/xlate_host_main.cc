@@ -4,16 +4,11 @@
 // passes one item too few, one output pointer too few or a stale history is caught -- and returns y_c[m] = (calls, c + m / 1024) so that
 // the caller can tell which call and channel wrote what.
 #include <clenabled/clenabled.h>
-#include <mi355_clenabled.h>
+#include "host_stub.h"
 
 #include <cmath>
-#include <cstdio>
-#include <cstring>
-#include <stdexcept>
-#include <string>
 #include <vector>
 
-struct mi355_ctx { int dev; };
 struct mi355_xlate {
     int D, K, C, complex_taps, generic;
     long long calls, skipped;
@@ -21,18 +16,7 @@ struct mi355_xlate {
     std::vector<double> freq;
 };
 
-static std::string g_err;
-
 extern "C" {
-const char *mi355_strerror(int code) { return code == MI355_ERR_INVALID_ARG ? "invalid argument" : code == MI355_ERR_NO_DEVICE ? "no device" : "error"; }
-const char *mi355_last_error(void) { return g_err.c_str(); }
-int mi355_ctx_create(int, int, int, int dev_id, int, mi355_ctx **out)
-{
-    if (dev_id == 99) { g_err = "no such device"; return MI355_ERR_NO_DEVICE; }
-    *out = new mi355_ctx{dev_id};
-    return MI355_OK;
-}
-int mi355_ctx_destroy(mi355_ctx *ctx) { delete ctx; return MI355_OK; }
 int mi355_xlate_plan(int D, int K, long long n, long long *nin, int *history)
 {
     if (D < 1 || K < 1 || n < 0) { g_err = "invalid argument: stub plan"; return MI355_ERR_INVALID_ARG; }
@@ -104,14 +88,6 @@ int mi355_xlate_work(mi355_xlate *h, long long n, const void *in, void *const *o
 }
 }
 
-#define CHECK(c)                                                      \
-    do {                                                              \
-        if (!(c)) {                                                   \
-            fprintf(stderr, "line %d: %s\n", __LINE__, #c);           \
-            return 1;                                                 \
-        }                                                             \
-    } while (0)
-
 using gr::clenabled::clFreqXlatingFIRFilter;
 
 // one work() call on exact-size heap buffers; returns what work() returned, or -1 when a written value is not the stub's
@@ -152,12 +128,8 @@ static int run(int D, int K, int C, bool cplx)
     CHECK(!fx->post_double("other", 1.0));
     fx->set_center_freq(-77.0, C - 1);
     CHECK(fx->center_freq(C - 1) == -77.0);
-    bool threw = false;
-    try { fx->set_center_freq(1.0, C); } catch (const std::invalid_argument &) { threw = true; }
-    CHECK(threw);
-    threw = false;
-    try { fx->set_center_freq(std::nan(""), 0); } catch (const std::invalid_argument &) { threw = true; }
-    CHECK(threw);
+    CHECK(throws<std::invalid_argument>([&] { fx->set_center_freq(1.0, C); }));
+    CHECK(throws<std::invalid_argument>([&] { fx->set_center_freq(std::nan(""), 0); }));
     fx->set_generic(true);
     CHECK(fx->route() == "generic stub");
     fx->skip(1ll << 40);
@@ -171,11 +143,7 @@ static int run(int D, int K, int C, bool cplx)
         CHECK(call(*fx, 3, calls) == 0 && (int)fx->history() == K2);
         CHECK(call(*fx, 33, calls++) == 33);
     }
-    if (!cplx) {
-        threw = false;
-        try { fx->set_taps(std::vector<gr_complex>(3, gr_complex(1.f, 1.f))); } catch (const std::invalid_argument &) { threw = true; }
-        CHECK(threw && (int)fx->history() == K);
-    }
+    if (!cplx) CHECK(throws<std::invalid_argument>([&] { fx->set_taps(std::vector<gr_complex>(3, gr_complex(1.f, 1.f))); }) && (int)fx->history() == K);
     return 0;
 }
 
@@ -187,24 +155,12 @@ int main()
     }
     // argument errors throw std::invalid_argument before any device work (device 99 does not exist); a missing device is a runtime error
     const std::vector<float> t(5, 1.f);
-    bool threw = false;
-    try { clFreqXlatingFIRFilter::make(1, 2, 0, 99, 0, t, {0.0}, 1e6); } catch (const std::invalid_argument &) { threw = true; }
-    CHECK(threw);
-    threw = false;
-    try { clFreqXlatingFIRFilter::make(1, 2, 0, 99, 4, std::vector<float>(), {0.0}, 1e6); } catch (const std::invalid_argument &) { threw = true; }
-    CHECK(threw);
-    threw = false;
-    try { clFreqXlatingFIRFilter::make(1, 2, 0, 99, 4, t, {}, 1e6); } catch (const std::invalid_argument &) { threw = true; }
-    CHECK(threw);
-    threw = false;
-    try { clFreqXlatingFIRFilter::make(1, 2, 0, 0, 4, t, {0.0}, 0.0); } catch (const std::invalid_argument &) { threw = true; }
-    CHECK(threw);
-    threw = false;
-    try { clFreqXlatingFIRFilter::make(1, 2, 0, 0, 4, t, {0.0, std::nan("")}, 1e6); } catch (const std::invalid_argument &) { threw = true; }
-    CHECK(threw);
-    threw = false;
-    try { clFreqXlatingFIRFilter::make(1, 2, 0, 99, 4, t, {0.0}, 1e6); } catch (const std::invalid_argument &) { } catch (const std::runtime_error &e) { threw = strstr(e.what(), "no such device") != nullptr; }
-    CHECK(threw);
+    CHECK(throws<std::invalid_argument>([&] { clFreqXlatingFIRFilter::make(1, 2, 0, 99, 0, t, {0.0}, 1e6); }));
+    CHECK(throws<std::invalid_argument>([&] { clFreqXlatingFIRFilter::make(1, 2, 0, 99, 4, std::vector<float>(), {0.0}, 1e6); }));
+    CHECK(throws<std::invalid_argument>([&] { clFreqXlatingFIRFilter::make(1, 2, 0, 99, 4, t, {}, 1e6); }));
+    CHECK(throws<std::invalid_argument>([&] { clFreqXlatingFIRFilter::make(1, 2, 0, 0, 4, t, {0.0}, 0.0); }));
+    CHECK(throws<std::invalid_argument>([&] { clFreqXlatingFIRFilter::make(1, 2, 0, 0, 4, t, {0.0, std::nan("")}, 1e6); }));
+    CHECK(throws<std::runtime_error>([&] { clFreqXlatingFIRFilter::make(1, 2, 0, 99, 4, t, {0.0}, 1e6); }, "no such device"));
     printf("xlate host ok\n");
     return 0;
 }
