@@ -302,6 +302,17 @@ def lib():
         "mi355_fold_work_dev": (i, [vp, ll, vp, vp, vp, vp, vp]),
         "mi355_fold_model": (i, [d, d, d, d, vp]),
         "mi355_fold_bins": (i, [vp, C.c_ulonglong, ll, i, vp]),
+        "mi355_ffa_plan": (i, [i, i, i, i, i, llp, llp, llp, llp]),
+        "mi355_ffa_create": (i, [vp, i, i, i, i, i, vp, vp, pp]),
+        "mi355_ffa_destroy": (i, [vp]),
+        "mi355_ffa_set_stats": (i, [vp, vp, vp]),
+        "mi355_ffa_get_stats": (i, [vp, vp, vp, ll]),
+        "mi355_ffa_set_generic": (i, [vp, i]),
+        "mi355_ffa_route": (C.c_char_p, [vp]),
+        "mi355_ffa_work": (i, [vp, vp, ll, vp, vp]),
+        "mi355_ffa_work_dev": (i, [vp, vp, ll, vp, vp, vp]),
+        "mi355_ffa_shift": (ll, [i, i, i]),
+        "mi355_ffa_period": (d, [i, i, i, d]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)  # AttributeError here = header/library mismatch: fail loudly

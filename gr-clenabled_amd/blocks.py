@@ -2053,3 +2053,142 @@ class clFolder(_Block):
         h = np.empty((ns, self.num_rows, self.nbin), np.uint32)
         self.work(ns, [x, tflags], [y, h])
         return y, h
+
+
+FFA_PEAK = PSEARCH_PEAK
+
+
+def ffa_shift(log2_rows, i, r):
+    """sh(i, r) of clPeriodSearch (mi355_ffa_shift, host only): the bins by which row r is read ahead in the profile of trial i"""
+    v = lib().mi355_ffa_shift(int(log2_rows), int(i), int(r))
+    if v < 0:
+        raise ValueError("ffa_shift: log2_rows is 1 .. 12 and i, r lie below 2^log2_rows")
+    return int(v)
+
+
+def ffa_period(p, log2_rows, i, tsamp_s):
+    """the period in seconds of trial (p, i) of clPeriodSearch (mi355_ffa_period, host only): (p + i / (2^log2_rows - 1)) tsamp_s, what
+    fold_model() takes"""
+    v = lib().mi355_ffa_period(int(p), int(log2_rows), int(i), float(tsamp_s))
+    if v != v:
+        raise ValueError("ffa_period: an argument outside the block's ranges")
+    return v
+
+
+class clPeriodSearch(_Block):
+    """Exact fast-folding search for unknown periods behind clDedisperser's per-trial output (beyond the reference module; the contract
+    is in include/mi355_clenabled.h).  For every series s and base period p_lo <= p <= p_hi the first 2^L p samples are 2^L rows of p
+    bins, combined by the FFA's fixed tree of binary32 additions into 2^L profiles, the trial periods p + i / (2^L - 1) samples.  Every
+    profile is searched with K circular dyadic boxcars, snr_k[j] = (b_k[j] - mean 2^(L+k)) (inv_sigma c_(L+k)), and gives the record
+    {snr, loc = (k << 24) | j} of its largest value (ties: smallest k, then smallest j; NaN never takes part): peaks[s][p - p_lo][i].
+    Optionally the profiles themselves, [s][p - p_lo][i][p_hi].  Bit-exact on either route and for any alignment and pitch."""
+    _destroy = "mi355_ffa_destroy"
+
+    def __init__(self, openCLPlatformType, devSelector, platformId, devId, num_series, p_lo, p_hi, log2_rows, num_widths, mean=None,
+                 inv_sigma=None, setDebug=0):
+        self.num_series, self.p_lo, self.p_hi = int(num_series), int(p_lo), int(p_hi)
+        self.log2_rows, self.num_widths = int(log2_rows), int(num_widths)
+        # argument errors before a context exists
+        self.N, self.records, self.profile_floats, self.scratch_bytes = self.plan(self.num_series, self.p_lo, self.p_hi, self.log2_rows,
+                                                                                  self.num_widths)
+        self.num_periods, self.num_rows = self.p_hi - self.p_lo + 1, 1 << self.log2_rows
+        m = None if mean is None else self._per_series(mean, "mean")
+        g = None if inv_sigma is None else self._per_series(inv_sigma, "inv_sigma")
+        super().__init__(openCLPlatformType, devSelector, platformId, devId, setDebug)
+        check(self._L.mi355_ffa_create(self._ctx, self.num_series, self.p_lo, self.p_hi, self.log2_rows, self.num_widths,
+                                       None if m is None else _hp(m), None if g is None else _hp(g), C.byref(self._h)), "mi355_ffa_create")
+
+    @staticmethod
+    def plan(num_series, p_lo, p_hi, log2_rows, num_widths):
+        """(N = input floats per series, records per series, profile floats per series, scratch bytes of a handle); no device"""
+        n, r, f, sb = C.c_longlong(), C.c_longlong(), C.c_longlong(), C.c_longlong()
+        check(lib().mi355_ffa_plan(int(num_series), int(p_lo), int(p_hi), int(log2_rows), int(num_widths), C.byref(n), C.byref(r), C.byref(f),
+                                   C.byref(sb)), "mi355_ffa_plan")
+        return n.value, r.value, f.value, sb.value
+
+    def _per_series(self, a, name):
+        a = np.ascontiguousarray(a)
+        if a.dtype != np.float32:
+            raise TypeError("%s is float32" % name)
+        if a.size != self.num_series:
+            raise ValueError("%s holds %d entries, the block has %d series" % (name, a.size, self.num_series))
+        return a
+
+    def route(self):
+        return self._L.mi355_ffa_route(self._h).decode()
+
+    def set_generic(self, on):
+        check(self._L.mi355_ffa_set_generic(self._h, 1 if on else 0), "mi355_ffa_set_generic")
+
+    def set_stats(self, mean, inv_sigma):
+        check(self._L.mi355_ffa_set_stats(self._h, _hp(self._per_series(mean, "mean")), _hp(self._per_series(inv_sigma, "inv_sigma"))),
+              "mi355_ffa_set_stats")
+
+    def stats(self):
+        m, g = np.empty(self.num_series, np.float32), np.empty(self.num_series, np.float32)
+        check(self._L.mi355_ffa_get_stats(self._h, _hp(m), _hp(g), self.num_series), "mi355_ffa_get_stats")
+        return m, g
+
+    shift = staticmethod(ffa_shift)
+
+    def period(self, p, i, tsamp_s=1.0):
+        return ffa_period(p, self.log2_rows, i, tsamp_s)
+
+    def in_floats(self, in_pitch=None):
+        """floats from the first to one past the last a call reads"""
+        return (self.num_series - 1) * (self.N if in_pitch is None else int(in_pitch)) + self.N
+
+    def work(self, input_items, output_items, in_pitch=None):
+        """host buffers: input_items[0] float32 x[s in_pitch + t]; output_items[0] an FFA_PEAK array of S x P x 2^L records;
+        output_items[1], optional or None: the profiles, float32 S x P x 2^L x p_hi (the floats j >= p of a row keep their content)"""
+        pitch = self.N if in_pitch is None else int(in_pitch)
+        x = _host(input_items[0], np.float32)
+        if pitch >= self.N:
+            _need("input", x, self.in_floats(pitch))
+        y = _host(output_items[0], FFA_PEAK, writable=True)
+        _need("output", y, self.num_series * self.records)
+        prof = None
+        if len(output_items) > 1 and output_items[1] is not None:
+            prof = _host(output_items[1], np.float32, writable=True)
+            _need("output 1", prof, self.num_series * self.profile_floats)
+        check(self._L.mi355_ffa_work(self._h, _hp(x), pitch, _hp(y), None if prof is None else _hp(prof)), "mi355_ffa_work")
+        return 1
+
+    def work_device(self, input_items, output_items, in_pitch=None):
+        """CUDA tensors, enqueue only on torch's current stream; the same buffers as work(), 8 bytes per record (see peaks_of)"""
+        pitch = self.N if in_pitch is None else int(in_pitch)
+        xin = _dp(input_items[0], self.in_floats(pitch) * 4 if pitch >= self.N else None, "input")
+        prof = None
+        if len(output_items) > 1 and output_items[1] is not None:
+            prof = _dp(output_items[1], 4 * self.num_series * self.profile_floats, "output 1")
+        check(self._L.mi355_ffa_work_dev(self._h, xin, pitch, _dp(output_items[0], 8 * self.num_series * self.records, "output"), prof,
+                                         _torch_stream(self.device)), "mi355_ffa_work_dev")
+        return 1
+
+    peaks_of = staticmethod(clPulseSearch.peaks_of)
+
+    def search(self, x, in_pitch=None, profiles=False):
+        """work() on a numpy input: the records as an FFA_PEAK array [S][P][2^L], or with profiles (records, float32 [S][P][2^L][p_hi],
+        NaN where j >= p)"""
+        y = np.empty((self.num_series, self.num_periods, self.num_rows), FFA_PEAK)
+        if not profiles:
+            self.work([x], [y], in_pitch)
+            return y
+        prof = np.full((self.num_series, self.num_periods, self.num_rows, self.p_hi), np.nan, np.float32)
+        self.work([x], [y, prof], in_pitch)
+        return y, prof
+
+    def best(self, peaks):
+        """(series, period in samples as a Fraction, k, j, snr) of the largest record of search()'s result: the greatest S/N, then the
+        smallest k, then the smallest j, then the first in the array's order; None where no record holds a value"""
+        from fractions import Fraction
+        y = np.asarray(peaks).reshape(self.num_series, self.num_periods, self.num_rows)
+        ok = y["loc"] != 0xFFFFFFFF
+        if not ok.any():
+            return None
+        snr = np.where(ok, y["snr"], -np.inf)
+        cand = np.flatnonzero((snr == snr.max()) & ok)
+        at = cand[np.argmin(y["loc"].reshape(-1)[cand])]
+        s, pi, i = np.unravel_index(at, y.shape)
+        loc = int(y["loc"][s, pi, i])
+        return int(s), self.p_lo + int(pi) + Fraction(int(i), max(self.num_rows - 1, 1)), loc >> 24, loc & 0xFFFFFF, float(y["snr"][s, pi, i])

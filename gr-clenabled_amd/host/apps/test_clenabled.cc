@@ -1154,11 +1154,67 @@ static int fold_test(size_t n)
     return g_fail ? 1 : 0;
 }
 
+// --ffa-only: clPeriodSearch at its smallest shape (S, p_lo..p_hi, L, K) = (1, 16..16, 1, 1) on the samples of --fbclean-only, with the
+// optional profile output.  Prints a "checksum" line that tests/test_ffa_gpu.py compares with the numpy reference: sum_i (i % 7 + 1)
+// (bits of snr_i) + sum_i (i % 7 + 1) loc_i + sum_j (j % 5 + 1) (bits of profile_j) modulo 2^64; then one timing row.
+static int ffa_test(size_t n)
+{
+    {
+        const int S = 1, P_LO = 16, P_HI = 16, L = 1, K = 1, M = 1 << L, N = M * P_HI;
+        uint32_t state = 12345u;
+        auto next = [&]() { state = state * 1664525u + 1013904223u; return (float)(state >> 24) + 1.0f; };
+        std::vector<float> x((size_t)S * N);
+        for (auto &v : x) v = next();
+        auto fs = clPeriodSearch::make(OCLTYPE_GPU, OCLDEVICESELECTOR_SPECIFIC, 0, g_dev, S, P_LO, P_HI, L, K);
+        bool ok = (int)fs->history() == 1 && fs->segment_len() == N && fs->records_per_series() == M && fs->route().compare(0, 6, "fused ") == 0 &&
+                  fs->period(16, 1, 0.5) == 8.5;
+        std::vector<clPeriodSearch::peak> y((size_t)S * M, clPeriodSearch::peak{-1e30f, 0u});
+        std::vector<float> prof((size_t)S * M * P_HI, -1e30f);
+        gr_vector_const_void_star in = {x.data()};
+        gr_vector_void_star out = {y.data(), prof.data()};
+        auto t0 = std::chrono::steady_clock::now();
+        ok = ok && fs->work(1, in, out) == 1;
+        std::chrono::duration<double> dt = std::chrono::steady_clock::now() - t0;
+        unsigned long long sum = 0;
+        for (size_t i = 0; i < y.size(); i++) {
+            uint32_t bits;
+            memcpy(&bits, &y[i].snr, 4);
+            ok = ok && y[i].snr != -1e30f && (y[i].loc >> 24) < (uint32_t)K && (y[i].loc & 0xFFFFFFu) < (uint32_t)P_HI;
+            sum += (unsigned long long)(i % 7 + 1) * bits + (unsigned long long)(i % 7 + 1) * y[i].loc;
+        }
+        for (size_t j = 0; j < prof.size(); j++) {
+            uint32_t bits;
+            memcpy(&bits, &prof[j], 4);
+            ok = ok && prof[j] >= 2.0f;
+            sum += (unsigned long long)(j % 5 + 1) * bits;
+        }
+        printf("clPeriodSearch checksum %llu\n", sum);
+        report("clPeriodSearch (1 series, base period 16, 2 rows, 1 width)", (size_t)N, dt.count(), ok);
+    }
+    {
+        const int St = 16, Pt = 250, Lt = 8, Kt = 5, Nt = Pt << Lt;
+        (void)n;
+        std::vector<float> xt((size_t)St * Nt, 0.5f);
+        auto fs = clPeriodSearch::make(OCLTYPE_GPU, OCLDEVICESELECTOR_SPECIFIC, 0, g_dev, St, Pt, Pt + 1, Lt, Kt);
+        std::vector<float> xin((size_t)St * fs->segment_len(), 0.5f);
+        std::vector<clPeriodSearch::peak> y((size_t)St * fs->records_per_series(), clPeriodSearch::peak{-1.0f, 0u});
+        gr_vector_const_void_star in = {xin.data()};
+        gr_vector_void_star out = {y.data()};
+        int got = 0;
+        const double t = time_calls([&] { got = fs->work(1, in, out); });
+        // a constant 1/2: every profile bin is 2^(L-1), snr_k = 2^(L+k-1) c_(L+k) grows with k, so every peak is the widest boxcar at bin 0
+        const uint32_t want = (uint32_t)(Kt - 1) << 24;
+        report("clPeriodSearch (16 series, base periods 250..251, 256 rows, 5 widths, timing)", (size_t)fs->segment_len() * St, t,
+               got == 1 && y[0].loc == want && y[y.size() / 2].loc == want && y.back().loc == want && y.back().snr == 32.0f);
+    }
+    return g_fail ? 1 : 0;
+}
+
 int main(int argc, char **argv)
 {
     size_t n = 8192;  // the reference's default block size
     int fft_size = 4096, ntaps = 65;
-    bool only_fft = false, only_xcorrelate = false, xc_complex = false, only_loops = false, only_resampler = false, only_synth = false, only_pspec = false, only_xlate = false, only_beamform = false, only_fengine = false, only_dedisp = false, only_psearch = false, only_fbclean = false, only_fold = false;
+    bool only_fft = false, only_xcorrelate = false, xc_complex = false, only_loops = false, only_resampler = false, only_synth = false, only_pspec = false, only_xlate = false, only_beamform = false, only_fengine = false, only_dedisp = false, only_psearch = false, only_fbclean = false, only_fold = false, only_ffa = false;
     int xc_inputs = 2, xc_maxsearch = 512;
     for (int i = 1; i < argc; i++) {
         if (!strncmp(argv[i], "--device=", 9)) g_dev = atoi(argv[i] + 9);
@@ -1179,6 +1235,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--psearch-only")) only_psearch = true;
         else if (!strcmp(argv[i], "--fbclean-only")) only_fbclean = true;
         else if (!strcmp(argv[i], "--fold-only")) only_fold = true;
+        else if (!strcmp(argv[i], "--ffa-only")) only_ffa = true;
         else if (!strncmp(argv[i], "--num_inputs=", 13)) xc_inputs = atoi(argv[i] + 13);
         else if (!strncmp(argv[i], "--maxsearch=", 12)) xc_maxsearch = atoi(argv[i] + 12);
         else if (!strcmp(argv[i], "--input_complex")) xc_complex = true;
@@ -1207,8 +1264,9 @@ int main(int argc, char **argv)
                    "       %s --dedisp-only [--iterations N] [block size]\n"
                    "       %s --psearch-only [--iterations N] [block size]\n"
                    "       %s --fbclean-only [--iterations N] [block size]\n"
-                   "       %s --fold-only [--iterations N] [block size]\n",
-                   argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
+                   "       %s --fold-only [--iterations N] [block size]\n"
+                   "       %s --ffa-only [--iterations N]\n",
+                   argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
             return 0;
         } else n = strtoull(argv[i], nullptr, 10);
     }
@@ -1254,6 +1312,10 @@ int main(int argc, char **argv)
     }
     if (only_fold) {
         try { return fold_test(n); }
+        catch (const std::exception &e) { std::cerr << "error: " << e.what() << std::endl; return 2; }
+    }
+    if (only_ffa) {
+        try { return ffa_test(n); }
         catch (const std::exception &e) { std::cerr << "error: " << e.what() << std::endl; return 2; }
     }
     if (only_xcorrelate) {

@@ -299,5 +299,34 @@ public:
     virtual std::string route() const = 0;
 };
 
+// gr::clenabled::clPeriodSearch -- exact fast-folding search (FFA) for pulsars of unknown period behind clDedisperser's per-trial output:
+// per series and base period p_lo <= p <= p_hi the first 2^log2_rows p samples as 2^log2_rows rows of p bins, combined by the FFA's fixed
+// tree of binary32 additions into the profiles of the trial periods p + i / (2^log2_rows - 1), each searched with num_widths circular
+// dyadic boxcars normalised to S/N.  Beyond the reference module; the contract is in mi355_clenabled.h.  A sync_block: an input item is
+// one whole segment of num_series series of segment_len() = 2^log2_rows p_hi floats (series-major), an output item the num_series
+// records_per_series() peak records of 8 bytes ({float snr; uint32 loc = (k << 24) | j}, [series][p - p_lo][i]); the optional output 1
+// carries the profiles, p_hi floats per record, of which the floats j >= p are not written.  mean / inv_sigma: num_series floats each
+// (what mi355_psearch_measure returns); empty vectors at make() are mean 0 and inv_sigma 1.
+// (No per-block header of this name is installed by this build yet.)
+class CLENABLED_API clPeriodSearch : virtual public gr::sync_block {
+public:
+    typedef std::shared_ptr<clPeriodSearch> sptr;
+    struct peak {
+        float snr;
+        uint32_t loc;
+    };
+    static sptr make(int openCLPlatformType, int devSelector, int platformId, int devId, int num_series, int p_lo, int p_hi, int log2_rows,
+                     int num_widths, const std::vector<float> &mean = std::vector<float>(), const std::vector<float> &inv_sigma = std::vector<float>(),
+                     int setDebug = 0);
+    virtual void set_stats(const std::vector<float> &mean, const std::vector<float> &inv_sigma) = 0;  // num_series entries each, anything else throws
+    virtual std::vector<float> mean() const = 0;
+    virtual std::vector<float> inv_sigma() const = 0;
+    virtual long long segment_len() const = 0;         // samples per series of an input item: 2^log2_rows p_hi
+    virtual long long records_per_series() const = 0;  // (p_hi - p_lo + 1) 2^log2_rows
+    virtual double period(int p, int i, double tsamp_s) const = 0;  // seconds, what mi355_fold_model takes; NaN outside the ranges
+    virtual void set_generic(bool on) = 0;  // the generic route for every later call
+    virtual std::string route() const = 0;
+};
+
 }  // namespace clenabled
 }  // namespace gr

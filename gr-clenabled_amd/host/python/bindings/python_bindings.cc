@@ -568,4 +568,40 @@ PYBIND11_MODULE(clenabled_python, m)
         .def("decimation", [](clFolder &b) { return b.decimation(); })
         .def("history", [](clFolder &b) { return b.history(); })
         .def("work", &call_work<clFolder>, py::arg("noutput_items"), py::arg("input_items"), py::arg("output_items"));
+
+    // period search (lib/clPeriodSearch_impl.cc): an input item is one segment of S series of 2^L p_hi floats, an output item its S P 2^L
+    // peak records of 8 bytes (output_items[1], optional: the S P 2^L p_hi profile floats)
+    py::class_<clPeriodSearch SYNC_BASES, std::shared_ptr<clPeriodSearch>>(m, "clPeriodSearch")
+        .def(py::init([](int openCLPlatformType, int devSelector, int platformId, int devId, int num_series, int p_lo, int p_hi, int log2_rows,
+                         int num_widths, const f32array &mean, const f32array &inv_sigma, int setDebug) {
+                 return clPeriodSearch::make(openCLPlatformType, devSelector, platformId, devId, num_series, p_lo, p_hi, log2_rows, num_widths,
+                                             std::vector<float>(mean.data(), mean.data() + mean.size()),
+                                             std::vector<float>(inv_sigma.data(), inv_sigma.data() + inv_sigma.size()), setDebug);
+             }),
+             py::arg("openCLPlatformType"), py::arg("devSelector"), py::arg("platformId"), py::arg("devId"), py::arg("num_series"), py::arg("p_lo"),
+             py::arg("p_hi"), py::arg("log2_rows"), py::arg("num_widths"), py::arg("mean") = f32array(0), py::arg("inv_sigma") = f32array(0),
+             py::arg("setDebug") = 0)
+        .def("set_stats",
+             [](clPeriodSearch &b, const f32array &mean, const f32array &inv_sigma) {
+                 b.set_stats(std::vector<float>(mean.data(), mean.data() + mean.size()),
+                             std::vector<float>(inv_sigma.data(), inv_sigma.data() + inv_sigma.size()));
+             },
+             py::arg("mean"), py::arg("inv_sigma"))
+        .def("mean",
+             [](clPeriodSearch &b) {
+                 const std::vector<float> t = b.mean();
+                 return f32array(t.size(), t.data());
+             })
+        .def("inv_sigma",
+             [](clPeriodSearch &b) {
+                 const std::vector<float> t = b.inv_sigma();
+                 return f32array(t.size(), t.data());
+             })
+        .def("segment_len", &clPeriodSearch::segment_len)
+        .def("records_per_series", &clPeriodSearch::records_per_series)
+        .def("period", &clPeriodSearch::period, py::arg("p"), py::arg("i"), py::arg("tsamp_s") = 1.0)
+        .def("set_generic", &clPeriodSearch::set_generic, py::arg("on"))
+        .def("route", &clPeriodSearch::route)
+        .def("history", [](clPeriodSearch &b) { return b.history(); })
+        .def("work", &call_work<clPeriodSearch>, py::arg("noutput_items"), py::arg("input_items"), py::arg("output_items"));
 }

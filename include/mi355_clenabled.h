@@ -1180,6 +1180,74 @@ int mi355_fold_work_dev(mi355_fold *h, long long n, const void *in, const void *
 int mi355_fold_model(double period_s, double pdot, double tsamp_s, double phase0_turns, uint64_t out[3]);
 int mi355_fold_bins(const uint64_t model[3], uint64_t T0, long long n, int nbin, int32_t *bins);
 
+/* ------------------------------------------------------------------------------------------------
+ * Period search: clPeriodSearch, an exact fast-folding search (FFA, Staelin 1969) for pulsars of unknown period over the dedispersed
+ * time series that clDedisperser delivers per trial.  Its output, a period and a phase, is what mi355_fold_model takes.  Beyond the
+ * reference module, which has no such block (this comment is the contract).  The arithmetic is pinned, so there is no tolerance.
+ *     S = num_series 1 .. 2^20;  base periods p_lo <= p <= p_hi in samples, 16 <= p_lo <= p_hi <= 4096, P = p_hi - p_lo + 1;
+ *     L = log2_rows 1 .. 12, m = 2^L;  K = num_widths 1 .. 11 with 2^(K-1) <= p_lo.
+ * Input: float32, x[s in_pitch + t], t < N = m p_hi, in_pitch >= N in floats; the floats between N and in_pitch are never read.
+ * Base period p uses the first m p samples of a series as m rows of p bins, row r = x[r p .. r p + p).
+ * The transform, for every (s, p): a_0[r] = row r; for stage sg = 1 .. L with g = 2^sg, h = g / 2, inside every group of g consecutive
+ * rows with base row B, for i < g and j < p
+ *     a_sg[B + i][j] = a_(sg-1)[B + (i >> 1)][j] + a_(sg-1)[B + h + (i >> 1)][(j + ((i + 1) >> 1)) mod p]
+ * each one IEEE binary32 addition, round to nearest even, the head operand on the left.  y[i] = a_L[i] is the profile of the trial
+ * period p + i / (m - 1) samples: the sum over rows r of row r read at (j + sh(i, r)) mod p with
+ *     sh(i, r) = sum over sg = 1 .. L of bit_(sg-1)(r) (((i >> (L - sg)) + 1) >> 1),      sh(i, m - 1) = i.
+ * The tree is the contract: a left-to-right sum over rows gives other bits and does not conform.  Subnormal operands or results are
+ * unspecified, as in clDedisperser.
+ * Evaluation: circular dyadic boxcars per profile,
+ *     b_0[j] = y[i][j];   b_k[j] = b_(k-1)[j] + b_(k-1)[(j + 2^(k-1)) mod p], k < K
+ *     snr_k[j] = (b_k[j] - mean[s] 2^(L+k)) (inv_sigma[s] c_(L+k)),   c_e = (e odd ? 0x3F3504F3 : 1.0f) 2^(-floor(e/2))
+ * one subtraction and one multiplication, each rounded once.  mean and inv_sigma: two float32 per series, set at _create (NULL: 0
+ * and 1) and by _set_stats; the values are what mi355_psearch_measure returns.
+ * peaks[s][p - p_lo][i]: one 8-byte record {float snr; uint32 loc} per trial, loc = (k << 24) | j: the maximum over k < K and j < p in
+ * clPulseSearch's 64-bit key order: the greatest S/N, +0 above -0, then the smallest k, then the smallest j.  A NaN never takes
+ * part; a trial without a non-NaN value gives {-Inf, 0xFFFFFFFF}.
+ * profiles[s][p - p_lo][i][j] (NULL skips them): the bits of y, row pitch p_hi floats; the floats j >= p of a row are never written.
+ * Invariance: either route, any partition of the stages into passes, any in_pitch, any 4-byte alignment of `in` and `profiles` and any
+ * 8-byte alignment of `peaks` give identical record bits and identical profile bits wherever the formula gives no NaN; where it gives
+ * a NaN the device gives a NaN (payload unspecified).  A NaN at x[r p + j0] reaches exactly the bins the formula gives for base period
+ * p, and nothing of another series.
+ * Routes, named by _route():
+ *   "fused S=64 p=250..251 L=12 K=7 q=6,6 t=1024" -- every shape.  The stages run in passes of q stages; a workgroup of t threads
+ *       gathers the 2^q rows of one independent unit into LDS, runs the q stages there and writes 2^q rows; the last pass evaluates
+ *       the boxcars and reduces the keys in LDS and writes the records (and the profiles).  q is the largest with 2^q p_hi <= 32768
+ *       floats, at most 8; L is split as evenly as that allows.
+ *   "generic S=64 p=250..251 L=12 K=7" -- under _set_generic(h, 1): one launch per stage between two scratch planes, then one
+ *       evaluation launch with a wave per trial; base periods one after another.
+ * Statistics updates: a call enqueued before _set_stats returns uses the old version entirely, a later call the new one entirely
+ * (versioned device buffers; nothing on the work path waits for the device).  A refused update changes nothing.
+ * Errors (nothing launched): NULL `in` or `peaks`, a misaligned buffer, `in` overlapping an output or the outputs overlapping,
+ * in_pitch < N, a parameter outside the ranges above: MI355_ERR_INVALID_ARG.  More than 2^40 bytes per buffer: MI355_ERR_UNSUPPORTED.
+ *   _plan         N, records per series (P m), profile floats per series (P m p_hi) and the scratch bytes of a handle; no device; any
+ *                 output pointer may be NULL
+ *   _create       everything that can be told without a device is checked before ctx is touched; the scratch is allocated here;
+ *                 mean / inv_sigma: S floats or NULL
+ *   _set_stats    replaces both arrays whole (S floats each, neither NULL);  _get_stats copies them, cap_entries is the size of each
+ *   _set_generic  on != 0: the generic route for every later call of the handle; 0: back
+ *   _route        valid until the next _set_generic / _destroy of the handle; "" for NULL
+ *   _work         host pointers, blocking: pieces of whole series through device scratch of the handle
+ *   _work_dev     device pointers, enqueue only: allocates nothing and waits for nothing
+ * Host-only helpers, no context:
+ *   mi355_ffa_shift   sh(i, r) for i, r < 2^log2_rows; MI355_ERR_INVALID_ARG (negative) outside the ranges
+ *   mi355_ffa_period  (p + i / (2^log2_rows - 1)) tsamp_s in double seconds, the argument of mi355_fold_model; NaN outside the ranges
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct mi355_ffa mi355_ffa;
+int mi355_ffa_plan(int num_series, int p_lo, int p_hi, int log2_rows, int num_widths, long long *in_floats_per_series,
+                   long long *records_per_series, long long *profile_floats_per_series, long long *scratch_bytes);
+int mi355_ffa_create(mi355_ctx *ctx, int num_series, int p_lo, int p_hi, int log2_rows, int num_widths, const float *mean,
+                     const float *inv_sigma, mi355_ffa **out);
+int mi355_ffa_destroy(mi355_ffa *h);
+int mi355_ffa_set_stats(mi355_ffa *h, const float *mean, const float *inv_sigma);
+int mi355_ffa_get_stats(const mi355_ffa *h, float *mean, float *inv_sigma, long long cap_entries);
+int mi355_ffa_set_generic(mi355_ffa *h, int on);
+const char *mi355_ffa_route(const mi355_ffa *h);
+int mi355_ffa_work(mi355_ffa *h, const void *in, long long in_pitch, void *peaks, void *profiles);
+int mi355_ffa_work_dev(mi355_ffa *h, const void *in, long long in_pitch, void *peaks, void *profiles, void *stream);
+long long mi355_ffa_shift(int log2_rows, int i, int r);
+double mi355_ffa_period(int p, int log2_rows, int i, double tsamp_s);
+
 #ifdef __cplusplus
 }
 #endif
