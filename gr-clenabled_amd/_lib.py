@@ -313,6 +313,18 @@ def lib():
         "mi355_ffa_work_dev": (i, [vp, vp, ll, vp, vp, vp]),
         "mi355_ffa_shift": (ll, [i, i, i]),
         "mi355_ffa_period": (d, [i, i, i, d]),
+        "mi355_ssearch_plan": (i, [i, i, i, i, i, i, llp, llp, llp]),
+        "mi355_ssearch_create": (i, [vp, i, i, i, i, i, i, vp, pp]),
+        "mi355_ssearch_destroy": (i, [vp]),
+        "mi355_ssearch_set_stats": (i, [vp, vp]),
+        "mi355_ssearch_get_stats": (i, [vp, vp, ll]),
+        "mi355_ssearch_set_threshold": (i, [vp, f]),
+        "mi355_ssearch_set_generic": (i, [vp, i]),
+        "mi355_ssearch_route": (C.c_char_p, [vp]),
+        "mi355_ssearch_fft_route": (C.c_char_p, [vp]),
+        "mi355_ssearch_work": (i, [vp, vp, ll, vp, vp, vp, ll, vp]),
+        "mi355_ssearch_work_dev": (i, [vp, vp, ll, vp, vp, vp, ll, vp, vp]),
+        "mi355_ssearch_freq": (d, [i, d, i, i]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)  # AttributeError here = header/library mismatch: fail loudly

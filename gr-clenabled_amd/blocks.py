@@ -2192,3 +2192,161 @@ class clPeriodSearch(_Block):
         s, pi, i = np.unravel_index(at, y.shape)
         loc = int(y["loc"][s, pi, i])
         return int(s), self.p_lo + int(pi) + Fraction(int(i), max(self.num_rows - 1, 1)), loc >> 24, loc & 0xFFFFFF, float(y["snr"][s, pi, i])
+
+
+SSEARCH_SERIES, SSEARCH_SPECTRUM = 0, 1
+SSEARCH_PEAK, SSEARCH_CAND = PSEARCH_PEAK, PSEARCH_CAND
+
+
+def ssearch_freq(n, tsamp_s, h, k):
+    """the fundamental in Hz of bin k of harmonic-sum level h of clSpectralSearch (mi355_ssearch_freq, host only): k / (2^h n tsamp_s);
+    its reciprocal is the period fold_model() takes"""
+    v = lib().mi355_ssearch_freq(int(n), float(tsamp_s), int(h), int(k))
+    if v != v:
+        raise ValueError("ssearch_freq: an argument outside the block's ranges")
+    return v
+
+
+class clSpectralSearch(_Block):
+    """FFT periodicity search with exact harmonic sums behind clDedisperser's per-trial output (beyond the reference module; the
+    contract is in include/mi355_clenabled.h).  SERIES input: every series of n samples is transformed (an internal clFFT of n / 2
+    points, untangled) into the normalised power spectrum w[k] = |X[k]|^2 inv_sigma^2 / n, k < n / 2, +0 below k_lo -- floating point,
+    held to a derived bound.  Then, bit-exact: level h <= num_folds adds the 2^h - 1 lower harmonics w[(k j + 2^(h-1)) >> h] to w[k] in
+    a pinned order, snr_h[k] = (s_h[k] - 2^h) c_h, and every (series, block of block_bins bins) gives the record {snr, loc = (h << 24) |
+    k_in_block} of its largest value (ties: smallest h, then smallest k; NaN never takes part): peaks[s][b].  SPECTRUM input runs the
+    sums on a given w.  With max_cands > 0 every peak at or above the threshold is also listed: candidates()."""
+    _destroy = "mi355_ssearch_destroy"
+
+    def __init__(self, openCLPlatformType, devSelector, platformId, devId, num_series, n, num_folds, block_bins, k_lo=1,
+                 input_kind=SSEARCH_SERIES, inv_sigma=None, max_cands=0, setDebug=0):
+        self.num_series, self.n, self.num_folds, self.block_bins = int(num_series), int(n), int(num_folds), int(block_bins)
+        self.k_lo, self.input_kind, self.max_cands = int(k_lo), int(input_kind), int(max_cands)
+        # argument errors before a context exists
+        self.num_bins, self.records, self.scratch_bytes = self.plan(self.num_series, self.n, self.num_folds, self.block_bins, self.k_lo,
+                                                                    self.input_kind)
+        if self.max_cands < 0:
+            raise ValueError("max_cands is negative")
+        self.row = self.n if self.input_kind == SSEARCH_SERIES else self.num_bins  # floats of a series of the input
+        g = None if inv_sigma is None else self._per_series(inv_sigma)
+        super().__init__(openCLPlatformType, devSelector, platformId, devId, setDebug)
+        check(self._L.mi355_ssearch_create(self._ctx, self.num_series, self.n, self.num_folds, self.block_bins, self.k_lo, self.input_kind,
+                                           None if g is None else _hp(g), C.byref(self._h)), "mi355_ssearch_create")
+        self._cands = self._counts = None  # the candidate buffers of the last call: numpy (work) or CUDA tensors (work_device)
+
+    @staticmethod
+    def plan(num_series, n, num_folds, block_bins, k_lo=1, input_kind=SSEARCH_SERIES):
+        """(spectrum floats per series = n / 2, records per series, scratch bytes of a handle); no device"""
+        a, r, sb = C.c_longlong(), C.c_longlong(), C.c_longlong()
+        check(lib().mi355_ssearch_plan(int(num_series), int(n), int(num_folds), int(block_bins), int(k_lo), int(input_kind), C.byref(a),
+                                       C.byref(r), C.byref(sb)), "mi355_ssearch_plan")
+        return a.value, r.value, sb.value
+
+    def _per_series(self, a):
+        a = np.ascontiguousarray(a)
+        if a.dtype != np.float32:
+            raise TypeError("inv_sigma is float32")
+        if a.size != self.num_series:
+            raise ValueError("inv_sigma holds %d entries, the block has %d series" % (a.size, self.num_series))
+        return a
+
+    def route(self):
+        return self._L.mi355_ssearch_route(self._h).decode()
+
+    def fft_route(self):
+        """clFFT.last_route() of the internal transform's last call ('' with SPECTRUM input or before the first call)"""
+        return self._L.mi355_ssearch_fft_route(self._h).decode()
+
+    def set_generic(self, on):
+        check(self._L.mi355_ssearch_set_generic(self._h, 1 if on else 0), "mi355_ssearch_set_generic")
+
+    def set_threshold(self, threshold):
+        check(self._L.mi355_ssearch_set_threshold(self._h, float(threshold)), "mi355_ssearch_set_threshold")
+
+    def set_stats(self, inv_sigma):
+        check(self._L.mi355_ssearch_set_stats(self._h, _hp(self._per_series(inv_sigma))), "mi355_ssearch_set_stats")
+
+    def stats(self):
+        g = np.empty(self.num_series, np.float32)
+        check(self._L.mi355_ssearch_get_stats(self._h, _hp(g), self.num_series), "mi355_ssearch_get_stats")
+        return g
+
+    def freq(self, h, k, tsamp_s=1.0):
+        return ssearch_freq(self.n, tsamp_s, h, k)
+
+    def in_floats(self, in_pitch=None):
+        """floats from the first to one past the last a call reads"""
+        return (self.num_series - 1) * (self.row if in_pitch is None else int(in_pitch)) + self.row
+
+    def work(self, input_items, output_items, in_pitch=None):
+        """host buffers: input_items[0] float32, x[s in_pitch + t] (SERIES) or w[s in_pitch + k] (SPECTRUM); output_items[0] an
+        SSEARCH_PEAK array of S x (n / 2 / block_bins) records; output_items[1], optional or None: the spectrum, float32 S x n / 2"""
+        pitch = self.row if in_pitch is None else int(in_pitch)
+        x = _host(input_items[0], np.float32)
+        if pitch >= self.row:
+            _need("input", x, self.in_floats(pitch))
+        y = _host(output_items[0], SSEARCH_PEAK, writable=True)
+        _need("output", y, self.num_series * self.records)
+        spec = None
+        if len(output_items) > 1 and output_items[1] is not None:
+            spec = _host(output_items[1], np.float32, writable=True)
+            _need("output 1", spec, self.num_series * self.num_bins)
+        cands = counts = None
+        if self.max_cands:
+            cands, counts = np.zeros(self.max_cands, SSEARCH_CAND), np.zeros(2, np.uint32)
+        check(self._L.mi355_ssearch_work(self._h, _hp(x), pitch, _hp(y), None if spec is None else _hp(spec),
+                                         None if cands is None else _hp(cands), self.max_cands, None if counts is None else _hp(counts)),
+              "mi355_ssearch_work")
+        self._cands, self._counts = cands, counts
+        return 1
+
+    def work_device(self, input_items, output_items, in_pitch=None, cands=None, counts=None):
+        """CUDA tensors, enqueue only on torch's current stream; the same buffers as work(), 8 bytes per record (see peaks_of).  cands
+        and counts, if given, are the candidate buffer (16 max_cands bytes) and the two 32-bit counters, otherwise the block keeps its own"""
+        pitch = self.row if in_pitch is None else int(in_pitch)
+        xin = _dp(input_items[0], self.in_floats(pitch) * 4 if pitch >= self.row else None, "input")
+        spec = None
+        if len(output_items) > 1 and output_items[1] is not None:
+            spec = _dp(output_items[1], 4 * self.num_series * self.num_bins, "output 1")
+        if self.max_cands and cands is None:
+            import torch
+            cands = torch.empty(self.max_cands * 4, dtype=torch.int32, device=input_items[0].device)
+            counts = torch.empty(2, dtype=torch.int32, device=input_items[0].device)
+        if not self.max_cands:
+            cands = counts = None
+        check(self._L.mi355_ssearch_work_dev(self._h, xin, pitch, _dp(output_items[0], 8 * self.num_series * self.records, "output"), spec,
+                                             None if cands is None else _dp(cands, self.max_cands * 16, "candidates"), self.max_cands,
+                                             None if counts is None else _dp(counts, 8, "counts"), _torch_stream(self.device)),
+              "mi355_ssearch_work_dev")
+        self._cands, self._counts = cands, counts
+        return 1
+
+    peaks_of = staticmethod(clPulseSearch.peaks_of)
+    candidates = clPulseSearch.candidates
+
+    def search(self, x, in_pitch=None, spectrum=False):
+        """work() on a numpy input: the records as an SSEARCH_PEAK array [S][n / 2 / block_bins], or with spectrum=True (records, w
+        float32 [S][n / 2])"""
+        y = np.empty((self.num_series, self.records), SSEARCH_PEAK)
+        if not spectrum:
+            self.work([x], [y], in_pitch)
+            return y
+        w = np.empty((self.num_series, self.num_bins), np.float32)
+        self.work([x], [y, w], in_pitch)
+        return y, w
+
+    def best(self, peaks):
+        """(series, h, k, snr) of the largest record of search()'s result, k the bin in the spectrum: the greatest S/N, then the smallest
+        h, then the smallest k, then the first in the array's order; None where no record holds a value.  The fundamental is
+        freq(h, k, tsamp_s)"""
+        y = np.asarray(peaks).reshape(self.num_series, self.records)
+        ok = y["loc"] != 0xFFFFFFFF
+        if not ok.any():
+            return None
+        snr = np.where(ok, y["snr"], -np.inf)
+        full = (y["loc"] & np.uint32(0xFF000000)).astype(np.uint64) << np.uint64(8) | (
+            np.arange(self.records, dtype=np.uint64)[None, :] * np.uint64(self.block_bins) + (y["loc"] & np.uint32(0xFFFFFF)))
+        cand = np.flatnonzero((snr == snr.max()) & ok)
+        at = cand[np.argmin(full.reshape(-1)[cand])]
+        s, b = np.unravel_index(at, y.shape)
+        loc = int(y["loc"][s, b])
+        return int(s), loc >> 24, int(b) * self.block_bins + (loc & 0xFFFFFF), float(y["snr"][s, b])

@@ -1210,11 +1210,82 @@ static int ffa_test(size_t n)
     return g_fail ? 1 : 0;
 }
 
+// --ssearch-only: clSpectralSearch at its smallest shape (S, n, H, Bb, k_lo) = (1, 256, 5, 16, 1) on the samples of --fbclean-only, with
+// the optional spectrum output.  Prints a "checksum" line of the records, sum_i (i % 7 + 1) (bits of snr_i) + sum_i (i % 7 + 1) loc_i
+// modulo 2^64 (tests/test_ssearch_gpu.py recomputes it from the spectrum the row prints beside it, "spectrum" = sum_j (j % 5 + 1) (bits of
+// w_j): the spectrum stage is floating point, the sums over it are exact); then one timing row.
+static int ssearch_test(size_t n)
+{
+    {
+        const int S = 1, N = 256, H = 5, BB = 16, K_LO = 1, NB = N / 2;
+        uint32_t state = 12345u;
+        auto next = [&]() { state = state * 1664525u + 1013904223u; return (float)(state >> 24) + 1.0f; };
+        std::vector<float> x((size_t)S * N);
+        for (auto &v : x) v = next();
+        auto ss = clSpectralSearch::make(OCLTYPE_GPU, OCLDEVICESELECTOR_SPECIFIC, 0, g_dev, S, N, H, BB, K_LO, std::vector<float>(1, 1.0f / 64.0f));
+        bool ok = (int)ss->history() == 1 && ss->segment_len() == N && ss->num_bins() == NB && ss->records_per_series() == NB / BB &&
+                  ss->route().compare(0, 6, "tiled ") == 0 && ss->freq(2, 64, 0.5) == 0.125;
+        std::vector<clSpectralSearch::peak> y((size_t)S * NB / BB, clSpectralSearch::peak{-1e30f, 0u});
+        std::vector<float> w((size_t)S * NB, -1e30f);
+        gr_vector_const_void_star in = {x.data()};
+        gr_vector_void_star out = {y.data(), w.data()};
+        auto t0 = std::chrono::steady_clock::now();
+        ok = ok && ss->work(1, in, out) == 1;
+        std::chrono::duration<double> dt = std::chrono::steady_clock::now() - t0;
+        unsigned long long sum = 0, wsum = 0;
+        for (size_t i = 0; i < y.size(); i++) {
+            uint32_t bits;
+            memcpy(&bits, &y[i].snr, 4);
+            ok = ok && y[i].snr != -1e30f && (y[i].loc >> 24) <= (uint32_t)H && (y[i].loc & 0xFFFFFFu) < (uint32_t)BB;
+            sum += (unsigned long long)(i % 7 + 1) * bits + (unsigned long long)(i % 7 + 1) * y[i].loc;
+        }
+        for (size_t j = 0; j < w.size(); j++) {
+            uint32_t bits;
+            memcpy(&bits, &w[j], 4);
+            ok = ok && w[j] >= 0.0f;
+            wsum += (unsigned long long)(j % 5 + 1) * bits;
+        }
+        printf("clSpectralSearch checksum %llu spectrum %llu\n", sum, wsum);
+        for (size_t j = 0; j < w.size(); j++) {
+            uint32_t bits;
+            memcpy(&bits, &w[j], 4);
+            printf("%s%08x", j % 16 ? " " : "w ", bits);
+            if (j % 16 == 15) printf("\n");
+        }
+        report("clSpectralSearch (1 series, 256 samples, 5 folds, blocks of 16 bins)", (size_t)N, dt.count(), ok);
+    }
+    {
+        const int St = 16, Nt = 1 << 16, Ht = 4, Bt = 256;
+        (void)n;
+        std::vector<float> xt((size_t)St * Nt, 0.0f);
+        for (int s = 0; s < St; s++)
+            for (int t = 0; t < Nt; t += 16) xt[(size_t)s * Nt + t] = 1.0f;  // a train of period 16: the spectrum is zero but for the multiples of bin 4096
+        auto ss = clSpectralSearch::make(OCLTYPE_GPU, OCLDEVICESELECTOR_SPECIFIC, 0, g_dev, St, Nt, Ht, Bt, 1);
+        std::vector<clSpectralSearch::peak> y((size_t)St * ss->records_per_series(), clSpectralSearch::peak{-1.0f, 0u});
+        gr_vector_const_void_star in = {xt.data()};
+        gr_vector_void_star out = {y.data()};
+        int got = 0;
+        const double t = time_calls([&] { got = ss->work(1, in, out); });
+        // the seven harmonics 4096 m, m = 1 .. 7, hold 4096^2 / 65536 = 256 each: level 2 at bin 16384 = block 64 sums four of them,
+        // snr = (1024 - 4) / 2 = 510, the largest of the series
+        bool ok = got == 1;
+        for (int s = 0; s < St; s++) {
+            float best = -1.0f;
+            size_t at = 0;
+            for (size_t b = 0; b < (size_t)ss->records_per_series(); b++)
+                if (y[(size_t)s * ss->records_per_series() + b].snr > best) { best = y[(size_t)s * ss->records_per_series() + b].snr; at = b; }
+            ok = ok && at == 64 && best > 509.99f && best < 510.01f && y[(size_t)s * ss->records_per_series() + at].loc == (2u << 24);
+        }
+        report("clSpectralSearch (16 series, 65536 samples, 4 folds, blocks of 256 bins, timing)", (size_t)Nt * St, t, ok);
+    }
+    return g_fail ? 1 : 0;
+}
+
 int main(int argc, char **argv)
 {
     size_t n = 8192;  // the reference's default block size
     int fft_size = 4096, ntaps = 65;
-    bool only_fft = false, only_xcorrelate = false, xc_complex = false, only_loops = false, only_resampler = false, only_synth = false, only_pspec = false, only_xlate = false, only_beamform = false, only_fengine = false, only_dedisp = false, only_psearch = false, only_fbclean = false, only_fold = false, only_ffa = false;
+    bool only_fft = false, only_xcorrelate = false, xc_complex = false, only_loops = false, only_resampler = false, only_synth = false, only_pspec = false, only_xlate = false, only_beamform = false, only_fengine = false, only_dedisp = false, only_psearch = false, only_fbclean = false, only_fold = false, only_ffa = false, only_ssearch = false;
     int xc_inputs = 2, xc_maxsearch = 512;
     for (int i = 1; i < argc; i++) {
         if (!strncmp(argv[i], "--device=", 9)) g_dev = atoi(argv[i] + 9);
@@ -1236,6 +1307,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--fbclean-only")) only_fbclean = true;
         else if (!strcmp(argv[i], "--fold-only")) only_fold = true;
         else if (!strcmp(argv[i], "--ffa-only")) only_ffa = true;
+        else if (!strcmp(argv[i], "--ssearch-only")) only_ssearch = true;
         else if (!strncmp(argv[i], "--num_inputs=", 13)) xc_inputs = atoi(argv[i] + 13);
         else if (!strncmp(argv[i], "--maxsearch=", 12)) xc_maxsearch = atoi(argv[i] + 12);
         else if (!strcmp(argv[i], "--input_complex")) xc_complex = true;
@@ -1265,8 +1337,9 @@ int main(int argc, char **argv)
                    "       %s --psearch-only [--iterations N] [block size]\n"
                    "       %s --fbclean-only [--iterations N] [block size]\n"
                    "       %s --fold-only [--iterations N] [block size]\n"
-                   "       %s --ffa-only [--iterations N]\n",
-                   argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
+                   "       %s --ffa-only [--iterations N]\n"
+                   "       %s --ssearch-only [--iterations N]\n",
+                   argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
             return 0;
         } else n = strtoull(argv[i], nullptr, 10);
     }
@@ -1316,6 +1389,10 @@ int main(int argc, char **argv)
     }
     if (only_ffa) {
         try { return ffa_test(n); }
+        catch (const std::exception &e) { std::cerr << "error: " << e.what() << std::endl; return 2; }
+    }
+    if (only_ssearch) {
+        try { return ssearch_test(n); }
         catch (const std::exception &e) { std::cerr << "error: " << e.what() << std::endl; return 2; }
     }
     if (only_xcorrelate) {

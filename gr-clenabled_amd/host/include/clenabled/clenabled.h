@@ -328,5 +328,33 @@ public:
     virtual std::string route() const = 0;
 };
 
+// gr::clenabled::clSpectralSearch -- FFT periodicity search with exact harmonic sums behind clDedisperser's per-trial output: every
+// series of n samples (a power of two, 2^8 .. 2^22) is transformed into its normalised power spectrum of n / 2 bins (zero below k_lo),
+// level h <= num_folds adds the 2^h - 1 lower harmonics of every bin in a pinned order of binary32 additions, and every block of
+// block_bins bins gives the record of its largest S/N over the levels.  Beyond the reference module; the contract is in
+// mi355_clenabled.h.  A sync_block: an input item is one whole segment of num_series series of n floats (series-major), an output item
+// the num_series records_per_series() peak records of 8 bytes ({float snr; uint32 loc = (h << 24) | k_in_block}, [series][block]); the
+// optional output 1 carries the spectra, n / 2 floats per series.  inv_sigma: num_series floats (what mi355_psearch_measure returns);
+// an empty vector at make() is 1.  Candidates are not exposed here: there is no message port.
+// (No per-block header of this name is installed by this build yet.)
+class CLENABLED_API clSpectralSearch : virtual public gr::sync_block {
+public:
+    typedef std::shared_ptr<clSpectralSearch> sptr;
+    struct peak {
+        float snr;
+        uint32_t loc;
+    };
+    static sptr make(int openCLPlatformType, int devSelector, int platformId, int devId, int num_series, int n, int num_folds, int block_bins,
+                     int k_lo = 1, const std::vector<float> &inv_sigma = std::vector<float>(), int setDebug = 0);
+    virtual void set_stats(const std::vector<float> &inv_sigma) = 0;  // num_series entries, anything else throws
+    virtual std::vector<float> inv_sigma() const = 0;
+    virtual long long segment_len() const = 0;         // samples per series of an input item: n
+    virtual long long num_bins() const = 0;            // n / 2
+    virtual long long records_per_series() const = 0;  // n / 2 / block_bins
+    virtual double freq(int h, int k, double tsamp_s) const = 0;  // Hz, the fundamental of bin k of level h; NaN outside the ranges
+    virtual void set_generic(bool on) = 0;  // the generic route for every later call
+    virtual std::string route() const = 0;
+};
+
 }  // namespace clenabled
 }  // namespace gr

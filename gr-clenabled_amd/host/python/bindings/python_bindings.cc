@@ -604,4 +604,33 @@ PYBIND11_MODULE(clenabled_python, m)
         .def("route", &clPeriodSearch::route)
         .def("history", [](clPeriodSearch &b) { return b.history(); })
         .def("work", &call_work<clPeriodSearch>, py::arg("noutput_items"), py::arg("input_items"), py::arg("output_items"));
+
+    // spectral search (lib/clSpectralSearch_impl.cc): an input item is one segment of S series of n floats, an output item its
+    // S n / 2 / block_bins peak records of 8 bytes (output_items[1], optional: the S n / 2 spectrum floats)
+    py::class_<clSpectralSearch SYNC_BASES, std::shared_ptr<clSpectralSearch>>(m, "clSpectralSearch")
+        .def(py::init([](int openCLPlatformType, int devSelector, int platformId, int devId, int num_series, int n, int num_folds, int block_bins,
+                         int k_lo, const f32array &inv_sigma, int setDebug) {
+                 return clSpectralSearch::make(openCLPlatformType, devSelector, platformId, devId, num_series, n, num_folds, block_bins, k_lo,
+                                               std::vector<float>(inv_sigma.data(), inv_sigma.data() + inv_sigma.size()), setDebug);
+             }),
+             py::arg("openCLPlatformType"), py::arg("devSelector"), py::arg("platformId"), py::arg("devId"), py::arg("num_series"), py::arg("n"),
+             py::arg("num_folds"), py::arg("block_bins"), py::arg("k_lo") = 1, py::arg("inv_sigma") = f32array(0), py::arg("setDebug") = 0)
+        .def("set_stats",
+             [](clSpectralSearch &b, const f32array &inv_sigma) {
+                 b.set_stats(std::vector<float>(inv_sigma.data(), inv_sigma.data() + inv_sigma.size()));
+             },
+             py::arg("inv_sigma"))
+        .def("inv_sigma",
+             [](clSpectralSearch &b) {
+                 const std::vector<float> t = b.inv_sigma();
+                 return f32array(t.size(), t.data());
+             })
+        .def("segment_len", &clSpectralSearch::segment_len)
+        .def("num_bins", &clSpectralSearch::num_bins)
+        .def("records_per_series", &clSpectralSearch::records_per_series)
+        .def("freq", &clSpectralSearch::freq, py::arg("h"), py::arg("k"), py::arg("tsamp_s") = 1.0)
+        .def("set_generic", &clSpectralSearch::set_generic, py::arg("on"))
+        .def("route", &clSpectralSearch::route)
+        .def("history", [](clSpectralSearch &b) { return b.history(); })
+        .def("work", &call_work<clSpectralSearch>, py::arg("noutput_items"), py::arg("input_items"), py::arg("output_items"));
 }

@@ -1248,6 +1248,95 @@ int mi355_ffa_work_dev(mi355_ffa *h, const void *in, long long in_pitch, void *p
 long long mi355_ffa_shift(int log2_rows, int i, int r);
 double mi355_ffa_period(int p, int log2_rows, int i, double tsamp_s);
 
+/* ------------------------------------------------------------------------------------------------
+ * Spectral search: clSpectralSearch, the Fourier-domain periodicity search over the dedispersed time series that clDedisperser delivers
+ * per trial: transform, normalised power spectrum, incoherent harmonic sums of 1, 2, 4 .. 32 harmonics, peaks.  The one step that sees
+ * periods below clPeriodSearch's 16 samples, O(N log N) per series.  Beyond the reference module, which has no such block (this
+ * comment is the contract).  Two stages: the spectrum is floating point and held to a derived bound against float64
+ * (tests/ssearch_ref.py); the harmonic sums are pinned arithmetic, compared bit for bit.
+ *     S = num_series 1 .. 2^20;  N = n, a power of two 2^8 .. 2^22 samples per series, Nb = N / 2 bins;  H = num_folds 0 .. 5 (level h
+ *     sums 2^h harmonics);  Bb = block_bins, a power of two 16 .. Nb;  k_lo 1 .. Nb - 1;  input_kind SERIES (0) or SPECTRUM (1).
+ * Spectrum stage (SERIES input): x[s in_pitch + t] float32, t < N, in_pitch >= N and even, `in` 8-byte aligned; the floats between N and
+ * in_pitch are never read.  The series is read as Nb complex items z[n] = x[2n] + i x[2n+1] and transformed by an internal clFFT handle
+ * of Nb points (no copy when in_pitch == N and the transform can take the input as it lies; otherwise rows of N floats are packed
+ * through scratch first -- a frame of clFFT depends on its own input alone, so the bits are the same).  One kernel untangles and detects:
+ *     X[k] = (Z[k] + conj Z[Nb-k]) / 2 - i e^(-2 pi i k / N) (Z[k] - conj Z[Nb-k]) / 2,   0 <= k < Nb,  Z[Nb] = Z[0]
+ *     w[s][k] = (Re X^2 + Im X^2) g[s],  g[s] = inv_sigma[s]^2 / N;   w[s][k] = +0 for k < k_lo;   the Nyquist bin is dropped
+ * with twiddles rounded once from double (exact 0 and 1 at the ends).  White noise of variance sigma^2 gives w a mean of 1.
+ * inv_sigma: one float32 per series, what mi355_psearch_measure returns, set at _create (NULL: 1) and by _set_stats; no mean is needed
+ * (it lands in bin 0, below k_lo).  `spectrum` (NULL skips it): spectrum[s Nb + k] holds the bits of w.  The bits of w do not depend on
+ * in_pitch, on the alignment, on which other series share the call or on a split of the series into calls.
+ * Harmonic-sum stage (SPECTRUM input runs it on w[s in_pitch + k] from `in` directly, in_pitch >= Nb, 4-byte aligned): with the integer
+ * index r(k, j, h) = (k j + 2^(h-1)) >> h, which is never above k,
+ *     s_0[k] = w[k]
+ *     s_h[k] = (...((s_(h-1)[k] + w[r(k,1,h)]) + w[r(k,3,h)]) + ...) + w[r(k,2^h-1,h)]                 h = 1 .. H
+ *     snr_h[k] = (s_h[k] - 2^h) c_h,   c_h = (h odd ? 0x3F3504F3 : 1.0f) 2^(-floor(h/2))   (clPulseSearch's constant)
+ * every + one binary32 addition, round to nearest even, the accumulator on the left, odd j ascending, level after level; the S/N one
+ * subtraction and one multiplication, each rounded once.  Bin k of level h is the 2^h-th harmonic: the fundamental is k / 2^h bins.
+ * The order is the contract: descending j, or summing a level first and adding it after, gives other bits and does not conform.
+ * Subnormal operands or results are unspecified, as in clDedisperser.
+ * Peaks: one 8-byte record {float snr; uint32 loc} per (series, block), peaks[s][b], b < Nb / Bb, loc = (h << 24) | k_in_block: the
+ * maximum over h <= H and the block's Bb bins in clPulseSearch's 64-bit key order -- the greatest S/N, +0 above -0, then the smallest h,
+ * then the smallest k.  A NaN never takes part; a block without a non-NaN value gives {-Inf, 0xFFFFFFFF}.  A NaN at w[m] removes exactly
+ * the (h, k) whose sum reads m, and nothing of another series.  The key maximum does not depend on the order of the reduction, so
+ * 64-bit integer atomicMax across workgroups gives the same bits; there are no float atomics.  (While a call runs, `peaks` holds its
+ * keys: initialised, reduced into and decoded in place, all in the call's stream.)
+ * Candidates (cands == NULL skips them), as clPulseSearch: every record with snr >= threshold becomes {float snr; uint32 loc; uint32
+ * series; uint32 block}; _set_threshold, +Inf by default, NaN refused; counts[0] = found, counted in full, counts[1] = stored =
+ * min(found, max_cands); the order of the list is unspecified (an integer counter, zeroed in the stream by the call).
+ * Invariance: either route, any in_pitch, any legal alignment and any split of the series into calls give identical peak bits, an
+ * identical candidate set and identical spectrum bits.
+ * Routes, named by _route() and forced by _set_generic only (no environment switch):
+ *   "tiled S=2 N=16384 H=5 Bb=256 tk=1024 ..." -- the default: a workgroup owns (series, tile of tk = min(Nb, 1024) bins), stages per
+ *       level the contiguous window of every odd j in LDS (at most 8 tk + 128 floats at h = 5, 33 KiB), a thread keeps the running sums
+ *       of its four bins in registers across the levels; keys by DPP, LDS and one 64-bit atomicMax per (tile, block);
+ *   "generic S=2 N=16384 H=5 Bb=256 ..." -- under _set_generic(h, 1): one thread per bin gathers from global memory.
+ *   The tail names the input: "spectrum", or "series k_lo=.. chunk=.. fft=.." (series per chunk of the spectrum stage, the length of
+ *   the internal transform) and the packing policy: rows are packed through scratch when in_pitch != N, or when the transform has more
+ *   than 4096 points and `in` is not 16-byte aligned.
+ * Statistics updates: a call enqueued before _set_stats returns uses the old version entirely, a later call the new one entirely.
+ * Errors (nothing launched): NULL `in` or `peaks`, cands without counts, a misaligned buffer (`in` 8-byte with SERIES and 4-byte with
+ * SPECTRUM input, spectrum 4-byte, peaks, cands and counts 8-byte), `in` overlapping an output or two outputs overlapping, in_pitch too
+ * small or, with SERIES input, odd, max_cands < 0, a parameter outside the ranges above, a NaN threshold, a `spectrum` output with
+ * SPECTRUM input: MI355_ERR_INVALID_ARG.  More than 2^40 bytes per buffer: MI355_ERR_UNSUPPORTED.
+ *   _plan           spectrum floats per series (Nb), records per series (Nb / Bb) and the scratch bytes of a handle (SERIES: a chunk's
+ *                   packed input, Z and w; SPECTRUM: 0); no device; any output pointer may be NULL
+ *   _create         everything that can be told without a device is checked before ctx is touched; the scratch is allocated here and
+ *                   the internal transform has run once on a chunk of zeros, so its workspace exists; inv_sigma: S floats or NULL
+ *   _set_stats      replaces the array whole (S floats);  _get_stats copies it, cap_entries is its size
+ *   _set_threshold  the candidate threshold of every later call
+ *   _set_generic    on != 0: the generic route for every later call of the handle; 0: back
+ *   _route          valid until the next _set_generic / _destroy of the handle; "" for NULL
+ *   _fft_route      mi355_fft_last_route of the internal transform's last call, which selects the multiple of the spectrum bound; ""
+ *                   for NULL, with SPECTRUM input and before the first call.  Valid until the handle's next _work / _work_dev /
+ *                   _destroy; read without the handle's lock, so a caller that works on the handle from another thread at the
+ *                   same time gets either call's route
+ *   _work           host pointers, blocking: pieces of whole series through device scratch of the handle
+ *   _work_dev       device pointers, enqueue only: allocates nothing and waits for nothing
+ * Host-only helper, no context:
+ *   mi355_ssearch_freq  the fundamental k / (2^h N tsamp_s) in Hz of bin k of level h, as a double; its reciprocal is the period
+ *                       mi355_fold_model takes; NaN outside the ranges (N as above, tsamp_s > 0 and finite, h 0 .. 5, k 0 .. Nb - 1)
+ * ------------------------------------------------------------------------------------------------ */
+#define MI355_SSEARCH_SERIES 0
+#define MI355_SSEARCH_SPECTRUM 1
+typedef struct mi355_ssearch mi355_ssearch;
+int mi355_ssearch_plan(int num_series, int n, int num_folds, int block_bins, int k_lo, int input_kind, long long *spectrum_floats_per_series,
+                       long long *records_per_series, long long *scratch_bytes);
+int mi355_ssearch_create(mi355_ctx *ctx, int num_series, int n, int num_folds, int block_bins, int k_lo, int input_kind, const float *inv_sigma,
+                         mi355_ssearch **out);
+int mi355_ssearch_destroy(mi355_ssearch *h);
+int mi355_ssearch_set_stats(mi355_ssearch *h, const float *inv_sigma);
+int mi355_ssearch_get_stats(const mi355_ssearch *h, float *inv_sigma, long long cap_entries);
+int mi355_ssearch_set_threshold(mi355_ssearch *h, float threshold);
+int mi355_ssearch_set_generic(mi355_ssearch *h, int on);
+const char *mi355_ssearch_route(const mi355_ssearch *h);
+const char *mi355_ssearch_fft_route(const mi355_ssearch *h);
+int mi355_ssearch_work(mi355_ssearch *h, const void *in, long long in_pitch, void *peaks, void *spectrum, void *cands, long long max_cands,
+                       void *counts);
+int mi355_ssearch_work_dev(mi355_ssearch *h, const void *in, long long in_pitch, void *peaks, void *spectrum, void *cands, long long max_cands,
+                           void *counts, void *stream);
+double mi355_ssearch_freq(int n, double tsamp_s, int h, int k);
+
 #ifdef __cplusplus
 }
 #endif
