@@ -325,6 +325,18 @@ def lib():
         "mi355_ssearch_work": (i, [vp, vp, ll, vp, vp, vp, ll, vp]),
         "mi355_ssearch_work_dev": (i, [vp, vp, ll, vp, vp, vp, ll, vp, vp]),
         "mi355_ssearch_freq": (d, [i, d, i, i]),
+        "mi355_accel_plan": (i, [i, i, i, llp, llp, llp]),
+        "mi355_accel_create": (i, [vp, i, i, i, vp, pp]),
+        "mi355_accel_destroy": (i, [vp]),
+        "mi355_accel_set_trials": (i, [vp, vp]),
+        "mi355_accel_get_trials": (i, [vp, vp, ll]),
+        "mi355_accel_set_generic": (i, [vp, i]),
+        "mi355_accel_route": (C.c_char_p, [vp]),
+        "mi355_accel_work": (i, [vp, vp, ll, vp, ll, i, i]),
+        "mi355_accel_work_dev": (i, [vp, vp, ll, vp, ll, i, i, vp]),
+        "mi355_accel_coeff": (i, [i, d, d, llp]),
+        "mi355_accel_index": (i, [i, ll, ll, ll, vp]),
+        "mi355_accel_trials": (i, [i, d, d, d, d, vp, ll, llp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)  # AttributeError here = header/library mismatch: fail loudly

@@ -2350,3 +2350,138 @@ class clSpectralSearch(_Block):
         s, b = np.unravel_index(at, y.shape)
         loc = int(y["loc"][s, b])
         return int(s), loc >> 24, int(b) * self.block_bins + (loc & 0xFFFFFF), float(y["snr"][s, b])
+
+
+ACCEL_LIGHT_M_S = 299792458.0
+
+
+def accel_coeff(n, tsamp_s, accel_m_s2):
+    """the coefficient c of clAccelResampler's index map for a line-of-sight acceleration in m/s^2 (mi355_accel_coeff, host only, computed
+    in long double): round(-2^64 accel tsamp / (2 x 299792458)), a Python int"""
+    c = C.c_longlong()
+    check(lib().mi355_accel_coeff(int(n), float(tsamp_s), float(accel_m_s2), C.byref(c)), "mi355_accel_coeff")
+    return c.value
+
+
+def accel_index(n, c, i0=0, count=None):
+    """src(i) of i = i0 .. i0 + count - 1 (to the end of the series by default) for one coefficient, bit for bit as clAccelResampler
+    computes it (mi355_accel_index, host only): int64 [count]"""
+    count = int(n) - int(i0) if count is None else int(count)
+    out = np.empty(max(count, 0), np.int64)
+    check(lib().mi355_accel_index(int(n), int(c), int(i0), count, _hp(out)), "mi355_accel_index")
+    return out
+
+
+def accel_trials(n, tsamp_s, a_lo, a_hi, tol_samples=1.0, cap=None):
+    """the ladder of coefficients whose neighbours differ by tol_samples samples at mid-observation, accelerations j da inside
+    [a_lo, a_hi] (mi355_accel_trials, host only): (int64 [min(count, cap)], count); cap None stores the whole ladder"""
+    cnt = C.c_longlong()
+    if cap is None:
+        check(lib().mi355_accel_trials(int(n), float(tsamp_s), float(a_lo), float(a_hi), float(tol_samples), None, 0, C.byref(cnt)),
+              "mi355_accel_trials")
+        cap = cnt.value
+    out = np.zeros(int(cap), np.int64)
+    check(lib().mi355_accel_trials(int(n), float(tsamp_s), float(a_lo), float(a_hi), float(tol_samples), _hp(out), int(cap), C.byref(cnt)),
+          "mi355_accel_trials")
+    return out[:min(int(cap), cnt.value)], cnt.value
+
+
+class clAccelResampler(_Block):
+    """Exact acceleration trials behind clDedisperser's per-trial output (beyond the reference module; the contract is in
+    include/mi355_clenabled.h).  Every series of n 32-bit words is stretched quadratically once per trial a, with the integer index
+    src_a(i) = i + floor((c[a] i (n - i) + 2^63) / 2^64): out[(s na + (a - a0)) out_pitch + i] = in[s in_pitch + src_a(i)].  The
+    words are moved, never computed on; the num_series x na output rows are series for clSpectralSearch, clPeriodSearch and
+    clPulseSearch.measure() as they lie.  `trials`: num_trials signed 64-bit coefficients (accel_coeff(), accel_trials())."""
+    _destroy = "mi355_accel_destroy"
+
+    def __init__(self, openCLPlatformType, devSelector, platformId, devId, num_series, n, trials, setDebug=0):
+        self.num_series, self.n = int(num_series), int(n)
+        t = self._table(trials, None)
+        self.num_trials = int(t.size)
+        # argument errors before a context exists
+        self.rows, self.tile, self.table_bytes = self.plan(self.num_series, self.n, self.num_trials)
+        super().__init__(openCLPlatformType, devSelector, platformId, devId, setDebug)
+        check(self._L.mi355_accel_create(self._ctx, self.num_series, self.n, self.num_trials, _hp(t), C.byref(self._h)), "mi355_accel_create")
+
+    @staticmethod
+    def plan(num_series, n, num_trials):
+        """(output rows of the whole ladder = num_series x num_trials, outputs per tile, bytes of the device table); no device"""
+        r, t, b = C.c_longlong(), C.c_longlong(), C.c_longlong()
+        check(lib().mi355_accel_plan(int(num_series), int(n), int(num_trials), C.byref(r), C.byref(t), C.byref(b)), "mi355_accel_plan")
+        return r.value, t.value, b.value
+
+    @staticmethod
+    def _table(trials, size):
+        t = np.ascontiguousarray(trials).reshape(-1)
+        if t.dtype != np.int64:
+            if t.dtype.kind not in "iu" and t.dtype != object:
+                raise TypeError("trials are signed 64-bit integers")
+            t = np.array([int(v) for v in t], np.int64)  # OverflowError for a value that is no int64
+        if size is not None and t.size != size:
+            raise ValueError("trials hold %d entries, the block has %d trials" % (t.size, size))
+        return t
+
+    def route(self):
+        return self._L.mi355_accel_route(self._h).decode()
+
+    def set_generic(self, on):
+        check(self._L.mi355_accel_set_generic(self._h, 1 if on else 0), "mi355_accel_set_generic")
+
+    def set_trials(self, trials):
+        check(self._L.mi355_accel_set_trials(self._h, _hp(self._table(trials, self.num_trials))), "mi355_accel_set_trials")
+
+    def trials(self):
+        c = np.empty(self.num_trials, np.int64)
+        check(self._L.mi355_accel_get_trials(self._h, _hp(c), self.num_trials), "mi355_accel_get_trials")
+        return c
+
+    def _range(self, a0, na):
+        a0 = int(a0)
+        return a0, self.num_trials - a0 if na is None else int(na)
+
+    def in_words(self, in_pitch=None):
+        """words from the first to one past the last a call reads"""
+        return (self.num_series - 1) * (self.n if in_pitch is None else int(in_pitch)) + self.n
+
+    def out_words(self, na, out_pitch=None):
+        """words from the first to one past the last a call of na trials writes"""
+        return (self.num_series * int(na) - 1) * (self.n if out_pitch is None else int(out_pitch)) + self.n
+
+    def series_to_trial(self, row, a0=0, na=None):
+        """(series, trial) of output row `row` of a call over the trial range [a0, a0 + na)"""
+        a0, na = self._range(a0, na)
+        if not 0 <= int(row) < self.num_series * na:
+            raise ValueError("row %d is outside the %d rows of the call" % (row, self.num_series * na))
+        return int(row) // na, a0 + int(row) % na
+
+    def work(self, input_items, output_items, a0=0, na=None, in_pitch=None, out_pitch=None):
+        """host buffers of 4-byte items (float32, int32 or uint32): input_items[0] x[s in_pitch + i]; output_items[0]
+        y[(s na + (a - a0)) out_pitch + i]"""
+        a0, na = self._range(a0, na)
+        ip, op = self.n if in_pitch is None else int(in_pitch), self.n if out_pitch is None else int(out_pitch)
+        x, y = _host(input_items[0]), _host(output_items[0], writable=True)
+        if x.dtype.itemsize != 4 or y.dtype.itemsize != 4:
+            raise TypeError("clAccelResampler moves 4-byte items")
+        if ip >= self.n:
+            _need("input", x, self.in_words(ip))
+        if op >= self.n and 1 <= na <= self.num_trials:
+            _need("output", y, self.out_words(na, op))
+        check(self._L.mi355_accel_work(self._h, _hp(x), ip, _hp(y), op, a0, na), "mi355_accel_work")
+        return 1
+
+    def work_device(self, input_items, output_items, a0=0, na=None, in_pitch=None, out_pitch=None):
+        """CUDA tensors of 4-byte items, enqueue only on torch's current stream; the same buffers as work()"""
+        a0, na = self._range(a0, na)
+        ip, op = self.n if in_pitch is None else int(in_pitch), self.n if out_pitch is None else int(out_pitch)
+        xin = _dp(input_items[0], self.in_words(ip) * 4 if ip >= self.n else None, "input")
+        yout = _dp(output_items[0], self.out_words(na, op) * 4 if op >= self.n and 1 <= na <= self.num_trials else None, "output")
+        check(self._L.mi355_accel_work_dev(self._h, xin, ip, yout, op, a0, na, _torch_stream(self.device)), "mi355_accel_work_dev")
+        return 1
+
+    def resample(self, x, a0=0, na=None, in_pitch=None):
+        """work() on a numpy input: the output [num_series][na][n] of the input's dtype"""
+        a0, na = self._range(a0, na)
+        x = _host(x)
+        y = np.empty((self.num_series, na, self.n), x.dtype)
+        self.work([x], [y], a0, na, in_pitch)
+        return y

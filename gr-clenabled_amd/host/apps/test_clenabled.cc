@@ -1281,11 +1281,72 @@ static int ssearch_test(size_t n)
     return g_fail ? 1 : 0;
 }
 
+// --accel-only: clAccelResampler at (S, n, A) = (2, 4099, 3) -- an odd length, so the 4-byte head and tail stores run -- with the trials
+// {0, 2^63 / n, -apex}, apex the smallest c whose shift at mid-series reaches 2, on the 32-bit words of the generator of --fbclean-only.
+// Prints a "checksum" line of the output, sum_j (j % 7 + 1) word_j modulo 2^64 (tests/test_accel_gpu.py recomputes it from
+// tests/accel_ref.py); then one timing row.
+static int accel_test(size_t n)
+{
+    {
+        const int S = 2, N = 4099;
+        uint32_t state = 12345u;
+        std::vector<uint32_t> x((size_t)S * N);
+        for (auto &v : x) { state = state * 1664525u + 1013904223u; v = state; }
+        const long long top = (long long)((1ull << 63) / (unsigned)N);
+        const unsigned __int128 dmax = (unsigned __int128)(N / 2) * (unsigned)(N - N / 2);
+        const long long apex = (long long)((((unsigned __int128)3 << 63) + dmax - 1) / dmax);
+        const std::vector<long long> trials = {0, top, -apex};
+        auto ar = clAccelResampler::make(OCLTYPE_GPU, OCLDEVICESELECTOR_SPECIFIC, 0, g_dev, S, N, trials);
+        bool ok = (int)ar->history() == 1 && ar->segment_len() == N && ar->num_trials() == 3 && ar->rows() == 6 &&
+                  ar->route().compare(0, 6, "tiled ") == 0 && ar->trials() == trials;
+        std::vector<uint32_t> y((size_t)S * 3 * N, 0xFFFFFFFFu);
+        gr_vector_const_void_star in = {x.data()};
+        gr_vector_void_star out = {y.data()};
+        auto t0 = std::chrono::steady_clock::now();
+        ok = ok && ar->work(1, in, out) == 1;
+        std::chrono::duration<double> dt = std::chrono::steady_clock::now() - t0;
+        unsigned long long sum = 0;
+        for (size_t j = 0; j < y.size(); j++) sum += (unsigned long long)(j % 7 + 1) * y[j];
+        for (int s = 0; s < S; s++) {
+            ok = ok && !memcmp(&y[(size_t)s * 3 * N], &x[(size_t)s * N], (size_t)N * 4);  // c = 0 is the identity
+            for (int t = 0; t < 3; t++)  // the end points stay
+                ok = ok && y[((size_t)s * 3 + t) * N] == x[(size_t)s * N] && y[((size_t)s * 3 + t) * N + N - 1] == x[(size_t)s * N + N - 1];
+        }
+        printf("clAccelResampler checksum %llu\n", sum);
+        report("clAccelResampler (2 series, 4099 samples, 3 trials)", (size_t)N, dt.count(), ok);
+    }
+    {
+        const int St = 16, Nt = 1 << 16, At = 8;
+        (void)n;
+        std::vector<float> xt((size_t)St * Nt);
+        for (size_t i = 0; i < xt.size(); i++) xt[i] = (float)(i % (size_t)Nt);  // a ramp: an output sample is its own source index
+        const long long step = (long long)(((unsigned __int128)1 << 66) / ((unsigned __int128)Nt * Nt));  // one sample at mid-series
+        std::vector<long long> ladder;
+        for (int j = -4; j < 4; j++) ladder.push_back(j * step);
+        auto ar = clAccelResampler::make(OCLTYPE_GPU, OCLDEVICESELECTOR_SPECIFIC, 0, g_dev, St, Nt, ladder);
+        std::vector<float> y((size_t)St * At * Nt, -1.0f);
+        gr_vector_const_void_star in = {xt.data()};
+        gr_vector_void_star out = {y.data()};
+        int got = 0;
+        const double t = time_calls([&] { got = ar->work(1, in, out); });
+        // trial j shifts the middle sample by j and leaves the ends; the sources never decrease
+        bool ok = got == 1;
+        for (int s = 0; s < St; s++)
+            for (int a = 0; a < At; a++) {
+                const float *r = &y[((size_t)s * At + a) * Nt];
+                ok = ok && r[0] == 0.0f && r[Nt - 1] == (float)(Nt - 1) && r[Nt / 2] == (float)(Nt / 2 + a - 4);
+                for (int i = 1; i < Nt && ok; i++) ok = r[i] >= r[i - 1];
+            }
+        report("clAccelResampler (16 series, 65536 samples, 8 trials, timing)", (size_t)Nt * St, t, ok);
+    }
+    return g_fail ? 1 : 0;
+}
+
 int main(int argc, char **argv)
 {
     size_t n = 8192;  // the reference's default block size
     int fft_size = 4096, ntaps = 65;
-    bool only_fft = false, only_xcorrelate = false, xc_complex = false, only_loops = false, only_resampler = false, only_synth = false, only_pspec = false, only_xlate = false, only_beamform = false, only_fengine = false, only_dedisp = false, only_psearch = false, only_fbclean = false, only_fold = false, only_ffa = false, only_ssearch = false;
+    bool only_fft = false, only_xcorrelate = false, xc_complex = false, only_loops = false, only_resampler = false, only_synth = false, only_pspec = false, only_xlate = false, only_beamform = false, only_fengine = false, only_dedisp = false, only_psearch = false, only_fbclean = false, only_fold = false, only_ffa = false, only_ssearch = false, only_accel = false;
     int xc_inputs = 2, xc_maxsearch = 512;
     for (int i = 1; i < argc; i++) {
         if (!strncmp(argv[i], "--device=", 9)) g_dev = atoi(argv[i] + 9);
@@ -1308,6 +1369,7 @@ int main(int argc, char **argv)
         else if (!strcmp(argv[i], "--fold-only")) only_fold = true;
         else if (!strcmp(argv[i], "--ffa-only")) only_ffa = true;
         else if (!strcmp(argv[i], "--ssearch-only")) only_ssearch = true;
+        else if (!strcmp(argv[i], "--accel-only")) only_accel = true;
         else if (!strncmp(argv[i], "--num_inputs=", 13)) xc_inputs = atoi(argv[i] + 13);
         else if (!strncmp(argv[i], "--maxsearch=", 12)) xc_maxsearch = atoi(argv[i] + 12);
         else if (!strcmp(argv[i], "--input_complex")) xc_complex = true;
@@ -1338,8 +1400,9 @@ int main(int argc, char **argv)
                    "       %s --fbclean-only [--iterations N] [block size]\n"
                    "       %s --fold-only [--iterations N] [block size]\n"
                    "       %s --ffa-only [--iterations N]\n"
-                   "       %s --ssearch-only [--iterations N]\n",
-                   argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
+                   "       %s --ssearch-only [--iterations N]\n"
+                   "       %s --accel-only [--iterations N]\n",
+                   argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
             return 0;
         } else n = strtoull(argv[i], nullptr, 10);
     }
@@ -1393,6 +1456,10 @@ int main(int argc, char **argv)
     }
     if (only_ssearch) {
         try { return ssearch_test(n); }
+        catch (const std::exception &e) { std::cerr << "error: " << e.what() << std::endl; return 2; }
+    }
+    if (only_accel) {
+        try { return accel_test(n); }
         catch (const std::exception &e) { std::cerr << "error: " << e.what() << std::endl; return 2; }
     }
     if (only_xcorrelate) {

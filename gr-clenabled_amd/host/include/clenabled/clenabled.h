@@ -356,5 +356,26 @@ public:
     virtual std::string route() const = 0;
 };
 
+// gr::clenabled::clAccelResampler -- exact acceleration trials behind clDedisperser's per-trial output: every series of n 32-bit words
+// (256 .. 2^22, any integer) is stretched quadratically once per trial with the integer index src_a(i) = i + floor((c[a] i (n - i) +
+// 2^63) / 2^64); the words are moved, never computed on.  Beyond the reference module; the contract is in mi355_clenabled.h.  A
+// sync_block: an input item is one whole segment of num_series series of n floats (series-major), an output item its rows()
+// = num_series x num_trials() series of n floats, [series][trial] -- what clSpectralSearch takes as rows() series.  trials: one signed
+// 64-bit coefficient per trial in 2^-64 sample per sample^2 (mi355_accel_coeff, mi355_accel_trials), at least one, |c| n <= 2^63.
+// (No per-block header of this name is installed by this build yet.)
+class CLENABLED_API clAccelResampler : virtual public gr::sync_block {
+public:
+    typedef std::shared_ptr<clAccelResampler> sptr;
+    static sptr make(int openCLPlatformType, int devSelector, int platformId, int devId, int num_series, int n,
+                     const std::vector<long long> &trials, int setDebug = 0);
+    virtual void set_trials(const std::vector<long long> &trials) = 0;  // num_trials() entries, anything else throws
+    virtual std::vector<long long> trials() const = 0;
+    virtual long long segment_len() const = 0;  // samples per series of an input item: n
+    virtual long long num_trials() const = 0;
+    virtual long long rows() const = 0;         // series of an output item: num_series x num_trials()
+    virtual void set_generic(bool on) = 0;      // the generic route for every later call
+    virtual std::string route() const = 0;
+};
+
 }  // namespace clenabled
 }  // namespace gr

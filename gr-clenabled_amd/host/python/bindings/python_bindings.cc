@@ -633,4 +633,31 @@ PYBIND11_MODULE(clenabled_python, m)
         .def("route", &clSpectralSearch::route)
         .def("history", [](clSpectralSearch &b) { return b.history(); })
         .def("work", &call_work<clSpectralSearch>, py::arg("noutput_items"), py::arg("input_items"), py::arg("output_items"));
+
+    // acceleration trials (lib/clAccelResampler_impl.cc): an input item is one segment of S series of n floats, an output item its
+    // S A resampled series of n floats, [series][trial]
+    using i64array = py::array_t<long long, py::array::c_style | py::array::forcecast>;
+    py::class_<clAccelResampler SYNC_BASES, std::shared_ptr<clAccelResampler>>(m, "clAccelResampler")
+        .def(py::init([](int openCLPlatformType, int devSelector, int platformId, int devId, int num_series, int n, const i64array &trials,
+                         int setDebug) {
+                 return clAccelResampler::make(openCLPlatformType, devSelector, platformId, devId, num_series, n,
+                                               std::vector<long long>(trials.data(), trials.data() + trials.size()), setDebug);
+             }),
+             py::arg("openCLPlatformType"), py::arg("devSelector"), py::arg("platformId"), py::arg("devId"), py::arg("num_series"), py::arg("n"),
+             py::arg("trials"), py::arg("setDebug") = 0)
+        .def("set_trials",
+             [](clAccelResampler &b, const i64array &trials) { b.set_trials(std::vector<long long>(trials.data(), trials.data() + trials.size())); },
+             py::arg("trials"))
+        .def("trials",
+             [](clAccelResampler &b) {
+                 const std::vector<long long> t = b.trials();
+                 return i64array(t.size(), t.data());
+             })
+        .def("segment_len", &clAccelResampler::segment_len)
+        .def("num_trials", &clAccelResampler::num_trials)
+        .def("rows", &clAccelResampler::rows)
+        .def("set_generic", &clAccelResampler::set_generic, py::arg("on"))
+        .def("route", &clAccelResampler::route)
+        .def("history", [](clAccelResampler &b) { return b.history(); })
+        .def("work", &call_work<clAccelResampler>, py::arg("noutput_items"), py::arg("input_items"), py::arg("output_items"));
 }

@@ -1337,6 +1337,83 @@ int mi355_ssearch_work_dev(mi355_ssearch *h, const void *in, long long in_pitch,
                            void *counts, void *stream);
 double mi355_ssearch_freq(int n, double tsamp_s, int h, int k);
 
+/* ------------------------------------------------------------------------------------------------
+ * Acceleration trials: clAccelResampler, the time-domain resampling step that deployed acceleration searches (peasoup, SIGPROC's seek)
+ * run between dedispersion and the period search: every dedispersed series is stretched quadratically once per acceleration trial, and
+ * the unchanged clSpectralSearch (the S A output rows are its series as they lie), clPeriodSearch and mi355_psearch_measure run on every
+ * copy.  A pulsar in a binary drifts across spectral bins at constant period; at the right trial its peak is whole again.  Beyond the
+ * reference module, which has no such block (this comment is the contract).  A pure gather with an integer index: the block moves
+ * 32-bit words and does no arithmetic on them, so NaN payloads, -0 and subnormals arrive unchanged, and every output word is pinned.
+ *     S = num_series 1 .. 2^20;  N = n 256 .. 2^22, any integer;  A = num_trials 1 .. 4096;  one signed 64-bit coefficient c[a] per
+ *     trial in units of 2^-64 sample per sample^2, with |c[a]| N <= 2^63.
+ * The index map, in exact integers (a signed 128-bit product, floor division, so a tie rounds up):
+ *     d(i)     = i (N - i)
+ *     delta_a(i) = floor((c[a] d(i) + 2^63) / 2^64)
+ *     src_a(i) = i + delta_a(i)                                                        0 <= i < N
+ *     out[((s na) + (a - a0)) out_pitch + i] = in[s in_pitch + src_a(i)]               0 <= s < S,  a0 <= a < a0 + na
+ * No float touches the index: truncation toward zero instead of the floor, or an index computed in float64, is another function and
+ * does not conform.  For the ranges above (tests/test_accel.py proves them with Python integers): src_a(0) = 0, src_a(N-1) = N-1,
+ * src_a is non-decreasing in i (and, d being non-negative, in c), |delta_a(i)| <= N / 8 (reached at c = +-2^63 / N), and c = 0 is the
+ * identity.  So every source lies inside its own series and nothing outside it is read.
+ * A call takes the trial range [a0, a0 + na): a caller walks a ladder whose whole output would not fit in memory.  The output rows of
+ * a call are S na series of N samples at out_pitch, series-major, then trial.
+ * Buffers: `in` and `out` 4-byte aligned, both pitches at least N; the words between N and a pitch are neither read nor written.
+ * Invariance: either route, any split over series or trial ranges into calls, any legal in_pitch, out_pitch and alignment give
+ * identical bits.
+ * Routes, named by _route() and forced by _set_generic only (no environment switch):
+ *   "tiled S=64 N=1048576 A=16 tile=1024 group=16" -- the default at every shape: a workgroup owns (series, tile of 1024 outputs,
+ *       group of consecutive trials), stages the union of the group's source windows in LDS once (16-byte loads of whole aligned
+ *       pieces), and a wave writes one trial's tile at a time: a lane owns runs of four outputs that start at a 16-byte boundary of
+ *       `out` and leave as one 16-byte store; a trial's tiles meet on those boundaries, so only what lies in front of a row's first
+ *       boundary and behind its last leaves as 4-byte stores.
+ *       The index is carried along a run by its first and second differences in 128 bits and the shift is taken at every sample
+ *       (d is concave: equal shifts at the two ends of a run do not make it constant inside).  The series is read once per group.
+ *       group = the largest g <= 16 at which every run of g consecutive trials of the table fits the LDS budget of 4096 words: a
+ *       window holds at most 1544 + ceil((cmax - cmin) N^2 / 2^66) words (the map's slope is below 3/2, so one trial always fits; the
+ *       second term is the spread of the group's shifts at mid-series).  Recomputed by _set_trials; an unsorted, widely spread table
+ *       gives group = 1.
+ *   "generic S=64 N=1048576 A=16" -- under _set_generic(h, 1): one thread per output gathers from global memory.
+ *   Measured on an MI355X (tools/accel_probe.py, README.md): where a group shares its window (A >= 4) the tiled route takes 0.40 - 0.47x
+ *   the generic route's time; with a single trial the two tie (the generic route 1.5 % ahead at S = 1024, N = 2^20).  The tiled route is
+ *   the default at every shape.
+ * Trial updates: the table is a versioned device buffer, released behind its last launch's event; a call enqueued before _set_trials
+ * returns uses the old table (and its group size) entirely, a later call the new one entirely.
+ * Errors (nothing launched): NULL `in` or `out`, a misaligned buffer, `in` overlapping `out`, a trial range outside 0 .. A or empty,
+ * a pitch below N, a parameter outside the ranges above, a coefficient outside the bound: MI355_ERR_INVALID_ARG.  More than 2^40 bytes
+ * per buffer: MI355_ERR_UNSUPPORTED.
+ *   _plan        output rows of the whole ladder (S A), the tile and the bytes of the device table; no device; any output pointer
+ *                may be NULL
+ *   _create      everything that can be told without a device is checked before ctx is touched; c: A coefficients, NULL = all 0
+ *   _set_trials  replaces the table whole (A coefficients);  _get_trials copies it, cap_entries is its size
+ *   _set_generic on != 0: the generic route for every later call of the handle; 0: back
+ *   _route       valid until the next _set_trials / _set_generic / _destroy of the handle; "" for NULL
+ *   _work        host pointers, blocking: pieces of whole series, and per piece runs of whole trials, through device scratch of the
+ *                handle
+ *   _work_dev    device pointers, enqueue only: allocates nothing and waits for nothing
+ * Host-only helpers, no context:
+ *   mi355_accel_coeff   c = round(-2^64 accel tsamp / (2 x 299792458)) of a line-of-sight acceleration in m/s^2, computed in long double:
+ *                       within two units of the exact rational value of the double inputs; a result outside the bound, n outside its
+ *                       range, tsamp_s not positive and finite or accel not finite: MI355_ERR_INVALID_ARG (c = 0 then)
+ *   mi355_accel_index   src(i) for i0 <= i < i0 + count, the map on the host bit for bit
+ *   mi355_accel_trials  the ladder a_j = j da for the integers j with a_lo <= a_j <= a_hi, ascending, da = tol 8 x 299792458 /
+ *                       (tsamp N^2): neighbouring trials differ by tol samples at mid-observation; j = 0 gives c = 0 exactly, the
+ *                       identity.  count is always the full count of the ladder (it may be 0 and may exceed 4096); at most cap
+ *                       coefficients are stored.  A trial outside the bound is an error whatever cap is.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct mi355_accel mi355_accel;
+int mi355_accel_plan(int num_series, int n, int num_trials, long long *rows, long long *tile, long long *table_bytes);
+int mi355_accel_create(mi355_ctx *ctx, int num_series, int n, int num_trials, const long long *c, mi355_accel **out);
+int mi355_accel_destroy(mi355_accel *h);
+int mi355_accel_set_trials(mi355_accel *h, const long long *c);
+int mi355_accel_get_trials(const mi355_accel *h, long long *c, long long cap_entries);
+int mi355_accel_set_generic(mi355_accel *h, int on);
+const char *mi355_accel_route(const mi355_accel *h);
+int mi355_accel_work(mi355_accel *h, const void *in, long long in_pitch, void *out, long long out_pitch, int a0, int na);
+int mi355_accel_work_dev(mi355_accel *h, const void *in, long long in_pitch, void *out, long long out_pitch, int a0, int na, void *stream);
+int mi355_accel_coeff(int n, double tsamp_s, double accel_m_s2, long long *c);
+int mi355_accel_index(int n, long long c, long long i0, long long count, long long *src);
+int mi355_accel_trials(int n, double tsamp_s, double a_lo, double a_hi, double tol_samples, long long *c, long long cap, long long *count);
+
 #ifdef __cplusplus
 }
 #endif
