@@ -1638,7 +1638,49 @@ PSEARCH_PEAK = np.dtype([("snr", np.float32), ("loc", np.uint32)])
 PSEARCH_CAND = np.dtype([("snr", np.float32), ("loc", np.uint32), ("series", np.uint32), ("block", np.uint32)])
 
 
-class clPulseSearch(_Block):
+class _PeakSearch(_Block):
+    """what clPulseSearch, clPeriodSearch and clSpectralSearch share: the check of a per-series statistic, the view of the peak records
+    and the candidate buffers of the last call"""
+    _series_of = "block"     # "... the block has N series"
+    _cands = _counts = None  # the candidate buffers of the last call: numpy (work) or CUDA tensors (work_device)
+
+    def _per_series(self, a, name="inv_sigma"):
+        a = np.ascontiguousarray(a)
+        if a.dtype != np.float32:
+            raise TypeError("%s is float32" % name)
+        if a.size != self.num_series:
+            raise ValueError("%s holds %d entries, the %s has %d series" % (name, a.size, self._series_of, self.num_series))
+        return a
+
+    def _new_cands(self, like=None):
+        """(candidate buffer, counters) of the block's own for a call, (None, None) with max_cands = 0: numpy, or torch on like's device"""
+        if not self.max_cands:
+            return None, None
+        if like is None:
+            return np.zeros(self.max_cands, PSEARCH_CAND), np.zeros(2, np.uint32)
+        import torch
+        return (torch.empty(self.max_cands * 4, dtype=torch.int32, device=like.device),
+                torch.empty(2, dtype=torch.int32, device=like.device))
+
+    @staticmethod
+    def peaks_of(t):
+        """the records of a work_device output tensor as a flat PSEARCH_PEAK array on the host (waits for the tensor's device)"""
+        return np.ascontiguousarray(t.detach().cpu().numpy()).reshape(-1).view(np.uint8).view(PSEARCH_PEAK)
+
+    def candidates(self):
+        """(records, found) of the last work() / work_device() call: a PSEARCH_CAND array of the min(found, max_cands) stored records in
+        no particular order, and the number found; waits for the device after a work_device() call"""
+        if self._cands is None:
+            return np.zeros(0, PSEARCH_CAND), 0
+        if isinstance(self._cands, np.ndarray):
+            cands, counts = self._cands, self._counts
+        else:
+            counts = self._counts.detach().cpu().numpy().reshape(-1).view(np.uint8).view(np.uint32)
+            cands = np.ascontiguousarray(self._cands.detach().cpu().numpy()).reshape(-1).view(np.uint8).view(PSEARCH_CAND)
+        return cands[:int(counts[1])].copy(), int(counts[0])
+
+
+class clPulseSearch(_PeakSearch):
     """Exact boxcar single-pulse search behind clDedisperser (beyond the reference module; the contract is in
     include/mi355_clenabled.h): per series K boxcars of widths 2^0 .. 2^(K-1) summed as a fixed dyadic tree of binary32 additions,
     snr_k[t] = (b_k[t] - mean 2^k) (inv_sigma c_k), and per (block of block_len outputs, series) the record {snr, loc = (k << 24) | t}
@@ -1647,6 +1689,7 @@ class clPulseSearch(_Block):
     max_cands > 0 every peak at or above the threshold (set_threshold, +Inf at first) is also listed: candidates().  Bit-exact on
     either route, for any split into calls and any alignment."""
     _destroy = "mi355_psearch_destroy"
+    _series_of = "geometry"
 
     def __init__(self, openCLPlatformType, devSelector, platformId, devId, num_rows, num_trials, num_widths, block_len,
                  order=PSEARCH_TIME_MAJOR, mean=None, inv_sigma=None, max_cands=0, setDebug=0):
@@ -1666,15 +1709,6 @@ class clPulseSearch(_Block):
         check(self._L.mi355_psearch_create(self._ctx, self.num_rows, self.num_trials, self.num_widths, self.block_len, self.order,
                                            None if m is None else _hp(m), None if g is None else _hp(g), C.byref(self._h)),
               "mi355_psearch_create")
-        self._cands = self._counts = None  # the candidate buffers of the last call: numpy (work) or CUDA tensors (work_device)
-
-    def _per_series(self, a, name):
-        a = np.ascontiguousarray(a)
-        if a.dtype != np.float32:
-            raise TypeError("%s is float32" % name)
-        if a.size != self.num_series:
-            raise ValueError("%s holds %d entries, the geometry has %d series" % (name, a.size, self.num_series))
-        return a
 
     def history(self):
         """samples of look-ahead behind a call's last output: 2^(K-1) - 1 (the GR block's history() is this plus one)"""
@@ -1739,9 +1773,7 @@ class clPulseSearch(_Block):
             _need("input", x, self.in_floats(nb, pitch))
         y = _host(output_items[0], PSEARCH_PEAK, writable=True)
         _need("output", y, nb * self.num_series)
-        cands = counts = None
-        if self.max_cands:
-            cands, counts = np.zeros(self.max_cands, PSEARCH_CAND), np.zeros(2, np.uint32)
+        cands, counts = self._new_cands()
         check(self._L.mi355_psearch_work(self._h, nb * self.block_len, _hp(x), pitch, _hp(y), None if cands is None else _hp(cands),
                                          self.max_cands, None if counts is None else _hp(counts)), "mi355_psearch_work")
         self._cands, self._counts = cands, counts
@@ -1756,14 +1788,10 @@ class clPulseSearch(_Block):
         pitch = self._pitch(nb, in_pitch)
         ok = self.order == PSEARCH_TIME_MAJOR or pitch >= nb * self.block_len + self._history
         xin = _dp(input_items[0], self.in_floats(nb, pitch) * 4 if ok else None, "input")
-        cands = counts = None
-        if self.max_cands:
-            if len(output_items) >= 3:
-                cands, counts = output_items[1], output_items[2]
-            else:
-                import torch
-                cands = torch.empty(self.max_cands * 4, dtype=torch.int32, device=input_items[0].device)
-                counts = torch.empty(2, dtype=torch.int32, device=input_items[0].device)
+        if self.max_cands and len(output_items) >= 3:
+            cands, counts = output_items[1], output_items[2]
+        else:
+            cands, counts = self._new_cands(input_items[0])
         check(self._L.mi355_psearch_work_dev(self._h, nb * self.block_len, xin, pitch, _dp(output_items[0], nb * self.num_series * 8, "output"),
                                              None if cands is None else _dp(cands, self.max_cands * 16, "candidates"), self.max_cands,
                                              None if counts is None else _dp(counts, 8, "counts"), _torch_stream(self.device)),
@@ -1776,24 +1804,6 @@ class clPulseSearch(_Block):
         y = np.empty((int(nblocks), self.num_rows, self.num_trials), PSEARCH_PEAK)
         self.work(nblocks, [x], [y], in_pitch)
         return y
-
-    @staticmethod
-    def peaks_of(t):
-        """the records of a work_device output tensor as a flat PSEARCH_PEAK array on the host (waits for the tensor's device)"""
-        return np.ascontiguousarray(t.detach().cpu().numpy()).reshape(-1).view(np.uint8).view(PSEARCH_PEAK)
-
-    def candidates(self):
-        """(records, found) of the last work() / work_device() call: a PSEARCH_CAND array of the min(found, max_cands) stored records in
-        no particular order, and the number found; waits for the device after a work_device() call"""
-        if self._cands is None:
-            return np.zeros(0, PSEARCH_CAND), 0
-        if isinstance(self._cands, np.ndarray):
-            cands, counts = self._cands, self._counts
-        else:
-            counts = self._counts.detach().cpu().numpy().reshape(-1).view(np.uint8).view(np.uint32)
-            cands = np.ascontiguousarray(self._cands.detach().cpu().numpy()).reshape(-1).view(np.uint8).view(PSEARCH_CAND)
-        return cands[:int(counts[1])].copy(), int(counts[0])
-
 
 def sk_estimate(x, nd, stride=1):
     """the spectral-kurtosis estimator of clFilterbankCleaner (mi355_fbclean_sk_estimate, host only) on one column of float32 samples
@@ -2075,7 +2085,7 @@ def ffa_period(p, log2_rows, i, tsamp_s):
     return v
 
 
-class clPeriodSearch(_Block):
+class clPeriodSearch(_PeakSearch):
     """Exact fast-folding search for unknown periods behind clDedisperser's per-trial output (beyond the reference module; the contract
     is in include/mi355_clenabled.h).  For every series s and base period p_lo <= p <= p_hi the first 2^L p samples are 2^L rows of p
     bins, combined by the FFA's fixed tree of binary32 additions into 2^L profiles, the trial periods p + i / (2^L - 1) samples.  Every
@@ -2105,14 +2115,6 @@ class clPeriodSearch(_Block):
         check(lib().mi355_ffa_plan(int(num_series), int(p_lo), int(p_hi), int(log2_rows), int(num_widths), C.byref(n), C.byref(r), C.byref(f),
                                    C.byref(sb)), "mi355_ffa_plan")
         return n.value, r.value, f.value, sb.value
-
-    def _per_series(self, a, name):
-        a = np.ascontiguousarray(a)
-        if a.dtype != np.float32:
-            raise TypeError("%s is float32" % name)
-        if a.size != self.num_series:
-            raise ValueError("%s holds %d entries, the block has %d series" % (name, a.size, self.num_series))
-        return a
 
     def route(self):
         return self._L.mi355_ffa_route(self._h).decode()
@@ -2165,8 +2167,6 @@ class clPeriodSearch(_Block):
                                          _torch_stream(self.device)), "mi355_ffa_work_dev")
         return 1
 
-    peaks_of = staticmethod(clPulseSearch.peaks_of)
-
     def search(self, x, in_pitch=None, profiles=False):
         """work() on a numpy input: the records as an FFA_PEAK array [S][P][2^L], or with profiles (records, float32 [S][P][2^L][p_hi],
         NaN where j >= p)"""
@@ -2207,7 +2207,7 @@ def ssearch_freq(n, tsamp_s, h, k):
     return v
 
 
-class clSpectralSearch(_Block):
+class clSpectralSearch(_PeakSearch):
     """FFT periodicity search with exact harmonic sums behind clDedisperser's per-trial output (beyond the reference module; the
     contract is in include/mi355_clenabled.h).  SERIES input: every series of n samples is transformed (an internal clFFT of n / 2
     points, untangled) into the normalised power spectrum w[k] = |X[k]|^2 inv_sigma^2 / n, k < n / 2, +0 below k_lo -- floating point,
@@ -2231,7 +2231,6 @@ class clSpectralSearch(_Block):
         super().__init__(openCLPlatformType, devSelector, platformId, devId, setDebug)
         check(self._L.mi355_ssearch_create(self._ctx, self.num_series, self.n, self.num_folds, self.block_bins, self.k_lo, self.input_kind,
                                            None if g is None else _hp(g), C.byref(self._h)), "mi355_ssearch_create")
-        self._cands = self._counts = None  # the candidate buffers of the last call: numpy (work) or CUDA tensors (work_device)
 
     @staticmethod
     def plan(num_series, n, num_folds, block_bins, k_lo=1, input_kind=SSEARCH_SERIES):
@@ -2240,14 +2239,6 @@ class clSpectralSearch(_Block):
         check(lib().mi355_ssearch_plan(int(num_series), int(n), int(num_folds), int(block_bins), int(k_lo), int(input_kind), C.byref(a),
                                        C.byref(r), C.byref(sb)), "mi355_ssearch_plan")
         return a.value, r.value, sb.value
-
-    def _per_series(self, a):
-        a = np.ascontiguousarray(a)
-        if a.dtype != np.float32:
-            raise TypeError("inv_sigma is float32")
-        if a.size != self.num_series:
-            raise ValueError("inv_sigma holds %d entries, the block has %d series" % (a.size, self.num_series))
-        return a
 
     def route(self):
         return self._L.mi355_ssearch_route(self._h).decode()
@@ -2290,9 +2281,7 @@ class clSpectralSearch(_Block):
         if len(output_items) > 1 and output_items[1] is not None:
             spec = _host(output_items[1], np.float32, writable=True)
             _need("output 1", spec, self.num_series * self.num_bins)
-        cands = counts = None
-        if self.max_cands:
-            cands, counts = np.zeros(self.max_cands, SSEARCH_CAND), np.zeros(2, np.uint32)
+        cands, counts = self._new_cands()
         check(self._L.mi355_ssearch_work(self._h, _hp(x), pitch, _hp(y), None if spec is None else _hp(spec),
                                          None if cands is None else _hp(cands), self.max_cands, None if counts is None else _hp(counts)),
               "mi355_ssearch_work")
@@ -2307,21 +2296,14 @@ class clSpectralSearch(_Block):
         spec = None
         if len(output_items) > 1 and output_items[1] is not None:
             spec = _dp(output_items[1], 4 * self.num_series * self.num_bins, "output 1")
-        if self.max_cands and cands is None:
-            import torch
-            cands = torch.empty(self.max_cands * 4, dtype=torch.int32, device=input_items[0].device)
-            counts = torch.empty(2, dtype=torch.int32, device=input_items[0].device)
-        if not self.max_cands:
-            cands = counts = None
+        if not self.max_cands or cands is None:
+            cands, counts = self._new_cands(input_items[0])
         check(self._L.mi355_ssearch_work_dev(self._h, xin, pitch, _dp(output_items[0], 8 * self.num_series * self.records, "output"), spec,
                                              None if cands is None else _dp(cands, self.max_cands * 16, "candidates"), self.max_cands,
                                              None if counts is None else _dp(counts, 8, "counts"), _torch_stream(self.device)),
               "mi355_ssearch_work_dev")
         self._cands, self._counts = cands, counts
         return 1
-
-    peaks_of = staticmethod(clPulseSearch.peaks_of)
-    candidates = clPulseSearch.candidates
 
     def search(self, x, in_pitch=None, spectrum=False):
         """work() on a numpy input: the records as an SSEARCH_PEAK array [S][n / 2 / block_bins], or with spectrum=True (records, w

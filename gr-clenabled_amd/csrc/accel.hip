@@ -259,12 +259,6 @@ int ac_launch(mi355_accel *h, long long nS, const void *in, long long in_pitch, 
     return h->ttab.used(st);  // this version of the table may be released behind these launches
 }
 
-bool ac_overlap(const void *p, long long pb, const void *q, long long qb)
-{
-    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-    return a < b + (uintptr_t)qb && b < a + (uintptr_t)pb;
-}
-
 int ac_args(const mi355_accel *h, const void *in, long long in_pitch, const void *out, long long out_pitch, int a0, int na)
 {
     const long long S = h->f.S, N = h->f.N;
@@ -279,7 +273,7 @@ int ac_args(const mi355_accel *h, const void *in, long long in_pitch, const void
         return MI355_ERR_UNSUPPORTED;
     }
     const long long ib = 4 * ((S - 1) * in_pitch + N), ob = 4 * ((S * na - 1) * out_pitch + N);
-    MI355_REQUIRE(!ac_overlap(in, ib, out, ob), "clAccelResampler does not work in place: in and out overlap");
+    MI355_REQUIRE(!mi355_overlap(in, ib, out, ob), "clAccelResampler does not work in place: in and out overlap");
     return MI355_OK;
 }
 

@@ -126,6 +126,13 @@ static inline unsigned mi355_grid_256(const mi355_ctx *ctx, long long total, int
     return (unsigned)(g > cap ? cap : g < 1 ? 1 : g);
 }
 
+// do the pb bytes at p and the qb bytes at q share a byte?
+static inline bool mi355_overlap(const void *p, long long pb, const void *q, long long qb)
+{
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+    return a < b + (uintptr_t)qb && b < a + (uintptr_t)pb;
+}
+
 // Persistent-kernel grid: k workgroups per CU, k in [kmin, kmax] (all resident).  More resident
 // workgroups hide latency better, so kmax is the default; a smaller k is taken only when it divides
 // the work units more evenly by more than `tol` (a ragged last round costs up to 1/rounds of the

@@ -426,12 +426,6 @@ int fb_launch(mi355_fbclean *h, long long n, const void *in, void *out, void *cf
     return h->dmask.used(st);
 }
 
-bool fb_overlap(const void *p, long long pb, const void *q, long long qb)
-{
-    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-    return a < b + (uintptr_t)qb && b < a + (uintptr_t)pb;
-}
-
 int fb_args(const mi355_fbclean *h, long long n, const void *in, const void *out, const void *cflags, const void *tflags, const void *stats)
 {
     MI355_REQUIRE(n >= 0, "n is negative");
@@ -447,13 +441,13 @@ int fb_args(const mi355_fbclean *h, long long n, const void *in, const void *out
         return MI355_ERR_UNSUPPORTED;
     }
     const long long xb = n * per, nblk = n / h->Tb;
-    MI355_REQUIRE(in == out || !fb_overlap(in, xb, out, xb), "in and out overlap without being the same buffer");
+    MI355_REQUIRE(in == out || !mi355_overlap(in, xb, out, xb), "in and out overlap without being the same buffer");
     const void *p[4] = {out, cflags, tflags, stats};
     const long long pb[4] = {xb, nblk * h->R * h->F, n * h->R, 8 * nblk * h->R * h->F};
     for (int i = 1; i < 4; i++) {
         if (!p[i]) continue;
-        MI355_REQUIRE(!fb_overlap(in, xb, p[i], pb[i]), "in overlaps cflags, tflags or stats");
-        for (int j = 0; j < i; j++) MI355_REQUIRE(!p[j] || !fb_overlap(p[j], pb[j], p[i], pb[i]), "two outputs overlap");
+        MI355_REQUIRE(!mi355_overlap(in, xb, p[i], pb[i]), "in overlaps cflags, tflags or stats");
+        for (int j = 0; j < i; j++) MI355_REQUIRE(!p[j] || !mi355_overlap(p[j], pb[j], p[i], pb[i]), "two outputs overlap");
     }
     return MI355_OK;
 }

@@ -24,65 +24,31 @@
 #include <string>
 #include <vector>
 #include "common.h"
+#include "peakkey.hpp"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-typedef unsigned long long u64;
+using peakkey::u64;
 
 constexpr int kFfaMaxS = 1 << 20, kFfaMinP = 16, kFfaMaxP = 4096, kFfaMaxL = 12, kFfaMaxK = 11;
 constexpr long long kFfaMaxBytes = 1ll << 40;
 constexpr long long kFfaHostBytes = 4ll << 20;    // host path: input bytes per staged piece unless one series needs more
 constexpr long long kFfaBatchFloats = 1ll << 23;  // base periods share a launch while a scratch plane stays below this (32 MiB)
-constexpr u64 kFfaEmpty = 0x007FFFFF00000000ull;  // the key that decodes to {-Inf, 0xFFFFFFFF}: below the key of every value
 constexpr int kFfaPairs = 16;                     // (head, tail) pairs a thread of k_ffa_pass owns: 32 sums in registers
 constexpr int kFfaEval = 8;                       // bins a thread owns per evaluation chunk; a chunk holds whole rows, so threads x 8 >= p
 constexpr int kFfaSmallPairs = 256 * kFfaPairs, kFfaLargePairs = 1024 * kFfaPairs;  // pairs of a unit: 256 or 1024 threads
 constexpr int kFfaMaxQ = 8;
 
-// c_e: the binary32 nearest to 2^(-e/2)
-__device__ __forceinline__ float ffa_c(int e) { return __uint_as_float(((e & 1) ? 0x3F3504F3u : 0x3F800000u) - ((unsigned)(e >> 1) << 23)); }
-
-// snr of one sum at level e = L + k folded into the running best of its bin: ascending k and a strict comparison keep the smallest k
-// of equals.  The order-preserving map of the bits, 0 for a NaN: below the map of every value
+// snr of one sum at level e = L + k folded into the running best of its bin under the tag k (peakkey.hpp has the key)
 __device__ __forceinline__ void ffa_fold(float b, int e, int k, float mean, float isg, unsigned &bo, unsigned &bk)
 {
     const float m = mean * (float)(1 << e);
-    const float g = isg * ffa_c(e);
+    const float g = isg * peakkey::c(e);
     const float d = b - m;
-    const float s = d * g;
-    const unsigned u = __float_as_uint(s);
-    unsigned o = u ^ ((unsigned)((int)u >> 31) | 0x80000000u);
-    o = s == s ? o : 0u;
-    bk = o > bo ? (unsigned)k : bk;
-    bo = o > bo ? o : bo;
+    peakkey::fold(d * g, k, bo, bk);
 }
-
-__device__ __forceinline__ uint2 ffa_record(u64 key)
-{
-    if (key == 0) key = kFfaEmpty;
-    const unsigned o = (unsigned)(key >> 32);
-    return make_uint2((o & 0x80000000u) ? (o ^ 0x80000000u) : ~o, ~(unsigned)key);
-}
-
-// the largest (smallest) value of a wave (all 64 lanes active), the same in every lane
-#define FFA_DPP(op, ctrl) v = op(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, ctrl, 0xf, 0xf, false));
-#define FFA_WAVE(name, op)                                                                   \
-    __device__ __forceinline__ unsigned name(unsigned v)                                     \
-    {                                                                                        \
-        FFA_DPP(op, 0xB1)  /* quad_perm:[1,0,3,2] */                                         \
-        FFA_DPP(op, 0x4E)  /* quad_perm:[2,3,0,1] */                                         \
-        FFA_DPP(op, 0x141) /* row_half_mirror */                                             \
-        FFA_DPP(op, 0x140) /* row_mirror */                                                  \
-        const unsigned r0 = (unsigned)__builtin_amdgcn_readlane((int)v, 0), r1 = (unsigned)__builtin_amdgcn_readlane((int)v, 16); \
-        const unsigned r2 = (unsigned)__builtin_amdgcn_readlane((int)v, 32), r3 = (unsigned)__builtin_amdgcn_readlane((int)v, 48); \
-        return op(op(r0, r1), op(r2, r3));                                                   \
-    }
-__device__ __forceinline__ unsigned ffa_umax(unsigned a, unsigned b) { return a > b ? a : b; }
-__device__ __forceinline__ unsigned ffa_umin(unsigned a, unsigned b) { return a < b ? a : b; }
-FFA_WAVE(ffa_wave_max, ffa_umax)
-FFA_WAVE(ffa_wave_min, ffa_umin)
 
 // e = l p + j with j < p, for magic = floor(2^32 / p): mulhi gives l or one less
 __device__ __forceinline__ void ffa_div(unsigned e, unsigned p, unsigned magic, unsigned &l, unsigned &j)
@@ -237,16 +203,16 @@ __global__ __launch_bounds__(THREADS, 4) void k_ffa_pass(const float *__restrict
                         const int firstl = __ffsll((long long)live) - 1;
                         const unsigned rref = (unsigned)__builtin_amdgcn_readlane((int)row, firstl);
                         if (__ballot(o != 0 && row != rref) == 0) {
-                            // one row: the largest ordered snr, then the smallest loc among the lanes that hold it
-                            const unsigned mo = ffa_wave_max(o);
-                            const unsigned ml = ffa_wave_min(o == mo ? loc : 0xFFFFFFFFu);
-                            if (lane == firstl) atomicMax(&lkeys[rref], ((u64)mo << 32) | (u64)(~ml));
-                        } else if (o != 0) atomicMax(&lkeys[row], ((u64)o << 32) | (u64)(~loc));
+                            // one row: the largest ordered snr, then the smallest loc among the lanes that hold it (as k_ps_tiled, k_ss_tiled)
+                            const unsigned mo = peakkey::wave_max(o);
+                            const unsigned ml = peakkey::wave_min(o == mo ? loc : 0xFFFFFFFFu);
+                            if (lane == firstl) atomicMax(&lkeys[rref], peakkey::key(mo, ml));
+                        } else if (o != 0) atomicMax(&lkeys[row], peakkey::key(o, loc));
                     }
                 }
             }
             __syncthreads();
-            if (tid < rows) peaks[trial0 + (size_t)tid] = ffa_record(lkeys[tid]);
+            if (tid < rows) peaks[trial0 + (size_t)tid] = peakkey::record(lkeys[tid]);
         }
         __syncthreads();  // the rows, the shifts and the keys are free for the next unit
     }
@@ -309,7 +275,7 @@ __global__ __launch_bounds__(256) void k_ffa_eval(const float *__restrict__ y, l
                     }
                 }
             }
-            const u64 mine = bo ? ((u64)bo << 32) | (u64)(~((bk << 24) | (unsigned)j)) : 0;
+            const u64 mine = bo ? peakkey::key(bo, (bk << 24) | (unsigned)j) : 0;
             key = mine > key ? mine : key;
         }
         for (int d = 32; d > 0; d >>= 1) {
@@ -317,7 +283,7 @@ __global__ __launch_bounds__(256) void k_ffa_eval(const float *__restrict__ y, l
             const u64 other = ((u64)hi << 32) | lo;
             key = other > key ? other : key;
         }
-        if (lane == 0) peaks[trial] = ffa_record(key);
+        if (lane == 0) peaks[trial] = peakkey::record(key);
     }
 }
 
@@ -362,8 +328,7 @@ struct mi355_ffa {
     int threads = 0, lds_bytes = 0;
     long long batch = 1;
     bool generic = false;
-    std::vector<float> stats;  // [mean S | inv_sigma S]
-    mi355_tables stab;
+    peakkey::SeriesStats stats;
     DevWorkspace ws;           // two scratch planes, allocated by _create
     DevBuf d_in, d_out;        // host path
     std::string route;
@@ -401,7 +366,7 @@ void ffa_name_route(mi355_ffa *h)
 int ffa_launch(mi355_ffa *h, int s0, int nS, const float *in, long long in_pitch, uint2 *peaks, float *profiles, hipStream_t st)
 {
     const FfaShape &f = h->f;
-    const float *d_stats = (const float *)h->stab.current() + s0;
+    const float *d_stats = h->stats.current() + s0;
     int rc = h->ws.acquire(h->ws.bytes(), st);  // the size of _create: nothing is allocated here
     if (rc) return rc;
     const long long slot = (long long)h->m * f.p_hi;
@@ -446,13 +411,7 @@ int ffa_launch(mi355_ffa *h, int s0, int nS, const float *in, long long in_pitch
     MI355_HIP(hipGetLastError());
     rc = h->ws.release(st);
     if (rc) return rc;
-    return h->stab.used(st);  // this version of the statistics may be released behind these launches
-}
-
-bool ffa_overlap(const void *p, long long pb, const void *q, long long qb)
-{
-    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-    return a < b + (uintptr_t)qb && b < a + (uintptr_t)pb;
+    return h->stats.used(st);  // this version of the statistics may be released behind these launches
 }
 
 int ffa_args(const mi355_ffa *h, const void *in, long long in_pitch, const void *peaks, const void *profiles)
@@ -469,10 +428,10 @@ int ffa_args(const mi355_ffa *h, const void *in, long long in_pitch, const void 
         return MI355_ERR_UNSUPPORTED;
     }
     const long long ib = 4 * ((S - 1) * in_pitch + h->N), pb = 8 * S * rec, fb = 4 * S * rec * h->f.p_hi;
-    MI355_REQUIRE(!ffa_overlap(in, ib, peaks, pb), "clPeriodSearch does not work in place: in and peaks overlap");
+    MI355_REQUIRE(!mi355_overlap(in, ib, peaks, pb), "clPeriodSearch does not work in place: in and peaks overlap");
     if (profiles) {
-        MI355_REQUIRE(!ffa_overlap(in, ib, profiles, fb), "in and profiles overlap");
-        MI355_REQUIRE(!ffa_overlap(peaks, pb, profiles, fb), "peaks and profiles overlap");
+        MI355_REQUIRE(!mi355_overlap(in, ib, profiles, fb), "in and profiles overlap");
+        MI355_REQUIRE(!mi355_overlap(peaks, pb, profiles, fb), "peaks and profiles overlap");
     }
     return MI355_OK;
 }
@@ -511,18 +470,13 @@ extern "C" int mi355_ffa_create(mi355_ctx *ctx, int num_series, int p_lo, int p_
     if (!h) return MI355_ERR_NOMEM;
     h->ctx = ctx; h->f = f; h->m = 1 << f.L; h->P = f.p_hi - f.p_lo + 1; h->N = (long long)h->m * f.p_hi;
     ffa_plan(h);
-    const size_t S = (size_t)f.S;
-    h->stats.assign(2 * S, 0.0f);
-    for (size_t s = 0; s < S; s++) {
-        h->stats[s] = mean ? mean[s] : 0.0f;
-        h->stats[S + s] = inv_sigma ? inv_sigma[s] : 1.0f;
-    }
+    h->stats.init((size_t)f.S, mean, inv_sigma, "mi355_ffa: statistics");
     const hipError_t e = hipSetDevice(ctx->device);
     if (e != hipSuccess) {
         mi355_set_error("mi355_ffa_create: %s", hipGetErrorString(e));
         rc = MI355_ERR_HIP;
     } else {
-        rc = h->stab.publish(ctx, h->stats.data(), 2 * S * 4, "mi355_ffa: statistics");
+        rc = h->stats.publish(ctx);
         if (rc == MI355_OK) rc = h->ws.acquire((size_t)ffa_scratch_bytes(f), ctx->stream[0]);
     }
     if (rc) { mi355_ffa_destroy(h); return rc; }
@@ -539,7 +493,7 @@ extern "C" int mi355_ffa_destroy(mi355_ffa *h)
     (void)hipSetDevice(h->ctx->device);
     (void)h->ws.wait();
     h->ws.destroy();
-    h->stab.release();
+    h->stats.release();
     h->d_in.release();
     h->d_out.release();
     delete h;
@@ -550,16 +504,9 @@ extern "C" int mi355_ffa_set_stats(mi355_ffa *h, const float *mean, const float 
 {
     MI355_REQUIRE(h != nullptr, "handle is NULL");
     MI355_REQUIRE(mean && inv_sigma, "mean or inv_sigma is NULL");
-    const size_t S = (size_t)h->f.S;
-    std::vector<float> img(2 * S);
-    memcpy(img.data(), mean, S * 4);
-    memcpy(img.data() + S, inv_sigma, S * 4);
     std::lock_guard<std::mutex> g(h->lock);
     MI355_HIP(hipSetDevice(h->ctx->device));
-    const int rc = h->stab.publish(h->ctx, img.data(), 2 * S * 4, "mi355_ffa: statistics");  // on failure the version in use stays
-    if (rc) return rc;
-    h->stats.swap(img);
-    return MI355_OK;
+    return h->stats.set(h->ctx, mean, inv_sigma);
 }
 
 extern "C" int mi355_ffa_get_stats(const mi355_ffa *h, float *mean, float *inv_sigma, long long cap_entries)
@@ -567,8 +514,7 @@ extern "C" int mi355_ffa_get_stats(const mi355_ffa *h, float *mean, float *inv_s
     MI355_REQUIRE(h && mean && inv_sigma, "NULL argument");
     std::lock_guard<std::mutex> g(const_cast<mi355_ffa *>(h)->lock);
     MI355_REQUIRE(cap_entries >= (long long)h->f.S, "out too small");
-    memcpy(mean, h->stats.data(), (size_t)h->f.S * 4);
-    memcpy(inv_sigma, h->stats.data() + h->f.S, (size_t)h->f.S * 4);
+    h->stats.get(mean, inv_sigma);
     return MI355_OK;
 }
 

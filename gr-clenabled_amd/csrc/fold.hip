@@ -335,12 +335,6 @@ int fo_launch(mi355_fold *h, unsigned long long T, long long n, const void *in, 
     return h->dmodels.used(st);
 }
 
-bool fo_overlap(const void *p, long long pb, const void *q, long long qb)
-{
-    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-    return a < b + (uintptr_t)qb && b < a + (uintptr_t)pb;
-}
-
 int fo_args(const mi355_fold *h, long long n, const void *in, const void *tflags, const void *out, const void *hits)
 {
     MI355_REQUIRE(n >= 0, "n is negative");
@@ -360,7 +354,7 @@ int fo_args(const mi355_fold *h, long long n, const void *in, const void *tflags
     const long long pb[4] = {n * per_in, nsub * per_out, n * h->R, 4 * nsub * h->R * h->nbin};
     for (int i = 1; i < 4; i++) {
         if (!p[i]) continue;
-        for (int j = 0; j < i; j++) MI355_REQUIRE(!p[j] || !fo_overlap(p[j], pb[j], p[i], pb[i]), "two buffers overlap");
+        for (int j = 0; j < i; j++) MI355_REQUIRE(!p[j] || !mi355_overlap(p[j], pb[j], p[i], pb[i]), "two buffers overlap");
     }
     return MI355_OK;
 }

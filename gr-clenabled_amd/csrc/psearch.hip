@@ -5,10 +5,9 @@
 //     snr_k[t] = (b_k[t] - mean 2^k) (inv_sigma c_k)                      one subtraction, one multiplication
 //     peak of a (block of Tb outputs, series) = the largest 64-bit key {order-preserving map of snr's bits, ~((k << 24) | t)}
 //
-// The key maximum does not depend on the order of the reduction, so registers, a wave, LDS atomics and global integer atomics may all
-// take part.  The peaks buffer itself carries the keys of a call: k_ps_init fills it with the key of {-Inf, 0xFFFFFFFF} (below every
-// key a value can have), the search kernel folds its keys in with 64-bit integer atomicMax, k_ps_emit decodes every key in place
-// into its {snr, loc} record and compacts the records at or above the threshold into the candidate list (an integer counter).
+// The key and its kernels are peakkey.hpp's.  The peaks buffer itself carries the keys of a call: k_peak_init fills it with the empty
+// key, the search kernel folds its keys in with 64-bit integer atomicMax, k_peak_emit decodes every key in place into its {snr, loc}
+// record and compacts the records at or above the threshold into the candidate list (an integer counter).
 //
 // k_ps_tiled  the fused route.  A workgroup owns NS series x Tt = W - Hs outputs and stages the W samples of each in LDS (TRIAL_MAJOR:
 //             NS = 1, contiguous runs; TIME_MAJOR: NS = 32, the 128-byte runs of 32 series per time sample, transposed into rows of
@@ -27,58 +26,33 @@
 #include <string>
 #include <vector>
 #include "common.h"
+#include "peakkey.hpp"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-typedef unsigned long long u64;
+using peakkey::u64;
 
 constexpr int kPsMaxR = 4096, kPsMaxD = 4096, kPsMaxK = 13, kPsMinTb = 16, kPsMaxTb = (1 << 24) - 1;
 constexpr long long kPsMaxCall = 1ll << 40;
 constexpr long long kPsHostBytes = 4ll << 20;   // host path: input bytes per staged piece unless one block needs more
-constexpr u64 kPsEmpty = 0x007FFFFF00000000ull;  // the key that decodes to {-Inf, 0xFFFFFFFF}: below the key of every value
 constexpr int kPsLdsMax = 160 << 10;
 constexpr int kPsTimeNS = 32;                    // series per workgroup of the TIME_MAJOR route: one 128-byte run per time sample
 
-// c_k: the binary32 nearest to 2^(-k/2)
-__device__ __forceinline__ float ps_c(int k) { return __uint_as_float(((k & 1) ? 0x3F3504F3u : 0x3F800000u) - ((unsigned)(k >> 1) << 23)); }
-
-// snr_k of one sum folded into the running best of its output: ascending k and a strict comparison keep the smallest k of equals.
-// Straight-line code (selects, no branches): the order-preserving map of the bits, 0 for a NaN -- below the map of every value
+// snr_k of one sum folded into the running best of its output
 __device__ __forceinline__ void ps_fold(float b, int k, float mean, float isg, unsigned &bo, unsigned &bk)
 {
     const float m = mean * (float)(1 << k);
-    const float g = isg * ps_c(k);
+    const float g = isg * peakkey::c(k);
     const float d = b - m;
-    const float s = d * g;
-    const unsigned u = __float_as_uint(s);
-    unsigned o = u ^ ((unsigned)((int)u >> 31) | 0x80000000u);
-    o = s == s ? o : 0u;
-    bk = o > bo ? (unsigned)k : bk;
-    bo = o > bo ? o : bo;
+    peakkey::fold(d * g, k, bo, bk);
 }
 
-__device__ __forceinline__ u64 ps_key(unsigned bo, unsigned bk, unsigned t_in_block) { return ((u64)bo << 32) | (u64)(~((bk << 24) | t_in_block)); }
-
-// the largest (smallest) value of a wave (all 64 lanes active), the same in every lane: pairs, quads, half rows and rows of 16 by
-// DPP, the four rows through scalar registers
-#define PS_DPP(op, ctrl) v = op(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, ctrl, 0xf, 0xf, false));
-#define PS_WAVE(name, op)                                                                    \
-    __device__ __forceinline__ unsigned name(unsigned v)                                     \
-    {                                                                                        \
-        PS_DPP(op, 0xB1)  /* quad_perm:[1,0,3,2] */                                          \
-        PS_DPP(op, 0x4E)  /* quad_perm:[2,3,0,1] */                                          \
-        PS_DPP(op, 0x141) /* row_half_mirror */                                              \
-        PS_DPP(op, 0x140) /* row_mirror */                                                   \
-        const unsigned r0 = (unsigned)__builtin_amdgcn_readlane((int)v, 0), r1 = (unsigned)__builtin_amdgcn_readlane((int)v, 16); \
-        const unsigned r2 = (unsigned)__builtin_amdgcn_readlane((int)v, 32), r3 = (unsigned)__builtin_amdgcn_readlane((int)v, 48); \
-        return op(op(r0, r1), op(r2, r3));                                                   \
-    }
-__device__ __forceinline__ unsigned ps_umax(unsigned a, unsigned b) { return a > b ? a : b; }
-__device__ __forceinline__ unsigned ps_umin(unsigned a, unsigned b) { return a < b ? a : b; }
-PS_WAVE(ps_wave_max, ps_umax)
-PS_WAVE(ps_wave_min, ps_umin)
+// record i of the [block][S series] peaks buffer
+struct PsSplit {
+    __device__ __forceinline__ uint2 operator()(long long i, int S) const { return make_uint2((unsigned)(i % S), (unsigned)(i / S)); }
+};
 
 struct PsArgs {
     int S, K, Tb, Tt, nbl;  // Tt = W - Hs outputs per tile; nbl: blocks a tile's outputs can touch
@@ -89,7 +63,7 @@ struct PsArgs {
     long long units;
 };
 
-// keys: the call's peaks buffer, [block][series] 64-bit keys (k_ps_init has filled it)
+// keys: the call's peaks buffer, [block][series] 64-bit keys (k_peak_init has filled it)
 // stats: [mean S | inv_sigma S]
 template <int ORDER, int THREADS, int NS, int EP, int CH>
 __global__ __launch_bounds__(THREADS) void k_ps_tiled(const float *__restrict__ in, const float *__restrict__ stats, u64 *keys, const PsArgs a)
@@ -173,11 +147,11 @@ __global__ __launch_bounds__(THREADS) void k_ps_tiled(const float *__restrict__ 
                     const int first = __ffsll((long long)live) - 1;
                     const unsigned bref = (unsigned)__builtin_amdgcn_readlane((int)bl, first);
                     if (__ballot(o != 0 && bl != bref) == 0) {
-                        // one block: the largest ordered snr, then the smallest loc among the lanes that hold it
-                        const unsigned mo = ps_wave_max(o);
-                        const unsigned ml = ps_wave_min(o == mo ? loc : 0xFFFFFFFFu);
-                        if (lane == first) atomicMax(&lkeys[j * a.nbl + (int)bref], ((u64)mo << 32) | (u64)(~ml));
-                    } else if (o != 0) atomicMax(&lkeys[j * a.nbl + (int)bl], ps_key(o, bk[c], tin));
+                        // one block: the largest ordered snr, then the smallest loc among the lanes that hold it (as k_ffa_pass, k_ss_tiled)
+                        const unsigned mo = peakkey::wave_max(o);
+                        const unsigned ml = peakkey::wave_min(o == mo ? loc : 0xFFFFFFFFu);
+                        if (lane == first) atomicMax(&lkeys[j * a.nbl + (int)bref], peakkey::key(mo, ml));
+                    } else if (o != 0) atomicMax(&lkeys[j * a.nbl + (int)bl], peakkey::key(o, loc));
                 }
             }
         }
@@ -237,34 +211,7 @@ __global__ __launch_bounds__(256) void k_ps_gen(const float *__restrict__ in, co
         }
         if (bo != 0) {
             const long long b = t / Tb;
-            atomicMax(&keys[(size_t)b * (size_t)S + (size_t)s], ps_key(bo, bk, (unsigned)(t - b * Tb)));
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void k_ps_init(u64 *keys, long long count, unsigned *counts)
-{
-    const long long first = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (counts && first == 0) { counts[0] = 0; counts[1] = 0; }
-    for (long long i = first; i < count; i += (long long)gridDim.x * 256) keys[i] = kPsEmpty;
-}
-
-// keys -> {float snr; uint32 loc} in place; records at or above the threshold -> {snr, loc, series, block}, counted in full
-__global__ __launch_bounds__(256) void k_ps_emit(u64 *peaks, long long count, int S, float thr, uint2 *cands, long long max_cands, unsigned *counts)
-{
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < count; i += (long long)gridDim.x * 256) {
-        const u64 key = peaks[i];
-        const unsigned o = (unsigned)(key >> 32);
-        const unsigned bits = (o & 0x80000000u) ? (o ^ 0x80000000u) : ~o;
-        const unsigned loc = ~(unsigned)key;
-        peaks[i] = ((u64)loc << 32) | bits;
-        if (cands && __uint_as_float(bits) >= thr) {
-            const unsigned at = atomicAdd(&counts[0], 1u);
-            if ((long long)at < max_cands) {
-                atomicAdd(&counts[1], 1u);
-                cands[2 * (size_t)at] = make_uint2(bits, loc);
-                cands[2 * (size_t)at + 1] = make_uint2((unsigned)(i % S), (unsigned)(i / S));
-            }
+            atomicMax(&keys[(size_t)b * (size_t)S + (size_t)s], peakkey::key(bo, (bk << 24) | (unsigned)(t - b * Tb)));
         }
     }
 }
@@ -323,8 +270,7 @@ struct mi355_psearch {
     int W = 0, Tt = 0, nbl = 0, lds_bytes = 0;
     bool generic = false;
     float threshold = INFINITY;
-    std::vector<float> stats;  // [mean S | inv_sigma S]
-    mi355_tables stab;
+    peakkey::SeriesStats stats;
     DevBuf d_in, d_out;        // host path
     std::string route;
     std::mutex lock;
@@ -379,14 +325,10 @@ int psr_launch_tiled(const mi355_psearch *h, const PsArgs &a, int wg_per_cu, con
 int psr_launch(mi355_psearch *h, long long n, const void *in, long long in_pitch, void *peaks, void *cands, long long max_cands, void *counts,
                hipStream_t st)
 {
-    const int cus = mi355_cus(h->ctx);
-    const float *d_stats = (const float *)h->stab.current();
+    const float *d_stats = h->stats.current();
     const long long nrec = n / h->Tb * h->S;
-    auto small_grid = [&](long long items) {
-        const long long blocks = (items + 255) / 256, cap = (long long)cus * 32;
-        return dim3((unsigned)(blocks < cap ? blocks : cap));
-    };
-    hipLaunchKernelGGL(k_ps_init, small_grid(nrec), dim3(256), 0, st, (u64 *)peaks, nrec, cands ? (unsigned *)counts : nullptr);
+    const dim3 rec_grid(mi355_grid_256(h->ctx, nrec, 32));
+    hipLaunchKernelGGL(peakkey::k_peak_init<>, rec_grid, dim3(256), 0, st, (u64 *)peaks, nrec, cands ? (unsigned *)counts : nullptr);
     if (psr_fused(h)) {
         PsArgs a = {};
         a.S = h->S; a.K = h->K; a.Tb = h->Tb; a.Tt = h->Tt; a.nbl = h->nbl;
@@ -405,7 +347,7 @@ int psr_launch(mi355_psearch *h, long long n, const void *in, long long in_pitch
         }
         if (rc) return rc;
     } else {
-        const dim3 grid = small_grid(n * h->S);
+        const dim3 grid(mi355_grid_256(h->ctx, n * h->S, 32));
         if (h->order == MI355_PSEARCH_TRIAL_MAJOR)
             hipLaunchKernelGGL(k_ps_gen<MI355_PSEARCH_TRIAL_MAJOR>, grid, dim3(256), 0, st, (const float *)in, d_stats, (u64 *)peaks, h->S, h->K, h->Tb, n,
                                in_pitch);
@@ -413,16 +355,10 @@ int psr_launch(mi355_psearch *h, long long n, const void *in, long long in_pitch
             hipLaunchKernelGGL(k_ps_gen<MI355_PSEARCH_TIME_MAJOR>, grid, dim3(256), 0, st, (const float *)in, d_stats, (u64 *)peaks, h->S, h->K, h->Tb, n,
                                in_pitch);
     }
-    hipLaunchKernelGGL(k_ps_emit, small_grid(nrec), dim3(256), 0, st, (u64 *)peaks, nrec, h->S, h->threshold, (uint2 *)cands, max_cands,
-                       (unsigned *)counts);
+    hipLaunchKernelGGL(peakkey::k_peak_emit<PsSplit>, rec_grid, dim3(256), 0, st, (u64 *)peaks, nrec, h->S, h->threshold, (uint2 *)cands,
+                       max_cands, (unsigned *)counts);
     MI355_HIP(hipGetLastError());
-    return h->stab.used(st);  // this version of the statistics may be released behind these launches
-}
-
-bool psr_overlap(const void *p, long long pb, const void *q, long long qb)
-{
-    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-    return a < b + (uintptr_t)qb && b < a + (uintptr_t)pb;
+    return h->stats.used(st);  // this version of the statistics may be released behind these launches
 }
 
 // bytes from the first to one past the last float a call for n outputs reads
@@ -442,11 +378,7 @@ int psr_args(const mi355_psearch *h, long long n, const void *in, long long in_p
     MI355_REQUIRE(in && peaks, "NULL buffer");
     MI355_REQUIRE((reinterpret_cast<uintptr_t>(in) & 3u) == 0, "in must be 4-byte aligned");
     MI355_REQUIRE((reinterpret_cast<uintptr_t>(peaks) & 7u) == 0, "peaks must be 8-byte aligned");
-    if (cands) {
-        MI355_REQUIRE(counts != nullptr, "cands without counts");
-        MI355_REQUIRE((reinterpret_cast<uintptr_t>(cands) & 7u) == 0, "cands must be 8-byte aligned");
-        MI355_REQUIRE((reinterpret_cast<uintptr_t>(counts) & 7u) == 0, "counts must be 8-byte aligned");
-    }
+    if (const int rc = peakkey::check_cands(cands, counts)) return rc;
     if (h->order == MI355_PSEARCH_TIME_MAJOR) MI355_REQUIRE(in_pitch == 0, "in_pitch must be 0 in TIME_MAJOR order");
     else MI355_REQUIRE(in_pitch >= n + h->Hs, "in_pitch is below n + history");
     const long long nblk = n / h->Tb;
@@ -457,15 +389,8 @@ int psr_args(const mi355_psearch *h, long long n, const void *in, long long in_p
         return MI355_ERR_UNSUPPORTED;
     }
     const long long ib = psr_in_bytes(h, n, in_pitch), pb = 8 * nblk * h->S;
-    MI355_REQUIRE(!psr_overlap(in, ib, peaks, pb), "clPulseSearch does not work in place: in and peaks overlap");
-    if (cands) {
-        MI355_REQUIRE(max_cands == 0 || !psr_overlap(in, ib, cands, 16 * max_cands), "in and cands overlap");
-        MI355_REQUIRE(!psr_overlap(in, ib, counts, 8), "in and counts overlap");
-        MI355_REQUIRE(max_cands == 0 || !psr_overlap(peaks, pb, cands, 16 * max_cands), "peaks and cands overlap");
-        MI355_REQUIRE(!psr_overlap(peaks, pb, counts, 8), "peaks and counts overlap");
-        MI355_REQUIRE(max_cands == 0 || !psr_overlap(cands, 16 * max_cands, counts, 8), "cands and counts overlap");
-    }
-    return MI355_OK;
+    MI355_REQUIRE(!mi355_overlap(in, ib, peaks, pb), "clPulseSearch does not work in place: in and peaks overlap");
+    return peakkey::check_cands_apart(in, ib, peaks, pb, cands, max_cands, counts);
 }
 
 }  // namespace
@@ -498,17 +423,12 @@ extern "C" int mi355_psearch_create(mi355_ctx *ctx, int num_rows, int num_trials
     h->ctx = ctx; h->R = num_rows; h->D = num_trials; h->S = num_rows * num_trials; h->K = num_widths; h->Tb = block_len; h->order = order;
     h->Hs = (1 << (num_widths - 1)) - 1;
     psr_plan(h);
-    const size_t S = (size_t)h->S;
-    h->stats.assign(2 * S, 0.0f);
-    for (size_t s = 0; s < S; s++) {
-        h->stats[s] = mean ? mean[s] : 0.0f;
-        h->stats[S + s] = inv_sigma ? inv_sigma[s] : 1.0f;
-    }
+    h->stats.init((size_t)h->S, mean, inv_sigma, "mi355_psearch: statistics");
     const hipError_t e = hipSetDevice(ctx->device);
     if (e != hipSuccess) {
         mi355_set_error("mi355_psearch_create: %s", hipGetErrorString(e));
         rc = MI355_ERR_HIP;
-    } else rc = h->stab.publish(ctx, h->stats.data(), 2 * S * 4, "mi355_psearch: statistics");
+    } else rc = h->stats.publish(ctx);
     if (rc) { mi355_psearch_destroy(h); return rc; }
     psr_name_route(h);
     mi355_log(ctx, MI355_LOG_INFO, "clPulseSearch: %d rows, %d trials, %d widths, blocks of %d: %s", h->R, h->D, h->K, h->Tb, h->route.c_str());
@@ -520,7 +440,7 @@ extern "C" int mi355_psearch_destroy(mi355_psearch *h)
 {
     if (!h) return MI355_OK;
     (void)hipSetDevice(h->ctx->device);
-    h->stab.release();
+    h->stats.release();
     h->d_in.release();
     h->d_out.release();
     delete h;
@@ -531,16 +451,9 @@ extern "C" int mi355_psearch_set_stats(mi355_psearch *h, const float *mean, cons
 {
     MI355_REQUIRE(h != nullptr, "handle is NULL");
     MI355_REQUIRE(mean && inv_sigma, "mean or inv_sigma is NULL");
-    const size_t S = (size_t)h->S;
-    std::vector<float> img(2 * S);
-    memcpy(img.data(), mean, S * 4);
-    memcpy(img.data() + S, inv_sigma, S * 4);
     std::lock_guard<std::mutex> g(h->lock);
     MI355_HIP(hipSetDevice(h->ctx->device));
-    const int rc = h->stab.publish(h->ctx, img.data(), 2 * S * 4, "mi355_psearch: statistics");  // on failure the version in use stays
-    if (rc) return rc;
-    h->stats.swap(img);
-    return MI355_OK;
+    return h->stats.set(h->ctx, mean, inv_sigma);
 }
 
 extern "C" int mi355_psearch_get_stats(const mi355_psearch *h, float *mean, float *inv_sigma, long long cap_entries)
@@ -548,8 +461,7 @@ extern "C" int mi355_psearch_get_stats(const mi355_psearch *h, float *mean, floa
     MI355_REQUIRE(h && mean && inv_sigma, "NULL argument");
     std::lock_guard<std::mutex> g(const_cast<mi355_psearch *>(h)->lock);
     MI355_REQUIRE(cap_entries >= (long long)h->S, "out too small");
-    memcpy(mean, h->stats.data(), (size_t)h->S * 4);
-    memcpy(inv_sigma, h->stats.data() + h->S, (size_t)h->S * 4);
+    h->stats.get(mean, inv_sigma);
     return MI355_OK;
 }
 
@@ -604,9 +516,7 @@ extern "C" int mi355_psearch_work(mi355_psearch *h, long long n, const void *in,
     if ((rc = h->d_in.reserve((size_t)(4 * S * (piece * Tb + Hs))))) return rc;
     if ((rc = h->d_out.reserve(peak_bytes + 8 + cand_bytes))) return rc;
     char *d_peaks = (char *)h->d_out.get(), *d_counts = d_peaks + peak_bytes, *d_cands = d_counts + 8;
-    unsigned long long found = 0;
-    long long stored = 0;
-    std::vector<uint32_t> got;
+    peakkey::CandList list(cands, max_cands);
     rc = mi355_pageable_run(h->ctx, nblk, piece, [&](long long b0, long long nb, hipStream_t st) -> int {
         const long long m = nb * Tb, rows = m + Hs;
         if (time_major) MI355_HIP(hipMemcpyAsync(h->d_in.get(), (const float *)in + b0 * Tb * S, (size_t)(4 * rows * S), hipMemcpyHostToDevice, st));
@@ -616,28 +526,10 @@ extern "C" int mi355_psearch_work(mi355_psearch *h, long long n, const void *in,
         const int lrc = psr_launch(h, m, h->d_in.get(), time_major ? 0 : rows, d_peaks, cands ? d_cands : nullptr, max_cands, d_counts, st);
         if (lrc) return lrc;
         MI355_HIP(hipMemcpyAsync((char *)peaks + 8 * b0 * S, d_peaks, (size_t)(8 * nb * S), hipMemcpyDeviceToHost, st));
-        if (!cands) return MI355_OK;
-        uint32_t c[2] = {0, 0};
-        MI355_HIP(hipMemcpyAsync(c, d_counts, 8, hipMemcpyDeviceToHost, st));
-        MI355_HIP(hipStreamSynchronize(st));
-        found += c[0];
-        if (c[1]) {
-            got.resize(4 * (size_t)c[1]);
-            MI355_HIP(hipMemcpyAsync(got.data(), d_cands, 16 * (size_t)c[1], hipMemcpyDeviceToHost, st));
-            MI355_HIP(hipStreamSynchronize(st));
-            for (uint32_t i = 0; i < c[1] && stored < max_cands; i++, stored++) {
-                uint32_t *dst = (uint32_t *)cands + 4 * stored;
-                memcpy(dst, got.data() + 4 * (size_t)i, 16);
-                dst[3] += (uint32_t)b0;
-            }
-        }
-        return MI355_OK;
+        return cands ? list.append(d_counts, d_cands, peakkey::CandList::BLOCK, b0, st) : MI355_OK;
     });
     if (rc) return rc;
-    if (cands) {
-        ((uint32_t *)counts)[0] = found > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)found;
-        ((uint32_t *)counts)[1] = (uint32_t)stored;
-    }
+    if (cands) list.finish(counts);
     return MI355_OK;
 }
 

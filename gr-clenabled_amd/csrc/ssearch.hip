@@ -18,66 +18,39 @@
 //             Neighbouring lanes read the same or the adjacent word.  The keys of a wave are reduced with DPP, a tile's in LDS, a
 //             block's (Bb > Tk) with one 64-bit integer atomicMax per tile into the peaks buffer itself.
 // k_ss_gen    the generic route: one thread per bin gathers from global memory.
-// k_ss_init / k_ss_emit  as clPulseSearch: the peaks buffer carries the keys of a call and is decoded in place; candidates by an
-//             integer counter.
+// The key and its kernels (k_peak_init, k_peak_emit) are peakkey.hpp's, as clPulseSearch: the peaks buffer carries the keys of a
+// call and is decoded in place; candidates by an integer counter.
 #include <cmath>
 #include <cstdint>
 #include <string>
 #include <vector>
 #include "common.h"
+#include "peakkey.hpp"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-typedef unsigned long long u64;
+using peakkey::u64;
 
 constexpr int kSsMaxS = 1 << 20, kSsMinLog2N = 8, kSsMaxLog2N = 22, kSsMaxH = 5, kSsMinBb = 16;
 constexpr long long kSsMaxBytes = 1ll << 40;
 constexpr long long kSsHostBytes = 4ll << 20;     // host path: input bytes per staged piece unless one series needs more
 constexpr long long kSsChunkFloats = 1ll << 24;   // SERIES input: series share a chunk while its samples stay below this (64 MiB)
-constexpr u64 kSsEmpty = 0x007FFFFF00000000ull;   // the key that decodes to {-Inf, 0xFFFFFFFF}: below the key of every value
 constexpr int kSsThreads = 256, kSsEp = 4;        // a tile holds at most 256 x 4 bins
 constexpr int kSsMaxTk = kSsThreads * kSsEp;
 // LDS of a level: its 2^(h-1) windows hold at most Tk 2^(h-2) + 2^h floats, and each is placed 0 .. 3 floats into a slot rounded up
 // to a multiple of 4: 8 Tk + 32 + 16 x 6 at h = 5
 constexpr int kSsLdsFloats = 8 * kSsMaxTk + 32 + 96;
 
-// c_h: the binary32 nearest to 2^(-h/2)
-__device__ __forceinline__ float ss_c(int h) { return __uint_as_float(((h & 1) ? 0x3F3504F3u : 0x3F800000u) - ((unsigned)(h >> 1) << 23)); }
-
-// snr_h of one sum folded into the running best of its bin: ascending h and a strict comparison keep the smallest h of equals.  The
-// order-preserving map of the bits, 0 for a NaN: below the map of every value
+// snr_h of one sum folded into the running best of its bin
 __device__ __forceinline__ void ss_fold(float sum, int h, unsigned &bo, unsigned &bh)
 {
     const float d = sum - (float)(1 << h);
-    const float s = d * ss_c(h);
-    const unsigned u = __float_as_uint(s);
-    unsigned o = u ^ ((unsigned)((int)u >> 31) | 0x80000000u);
-    o = s == s ? o : 0u;
-    bh = o > bo ? (unsigned)h : bh;
-    bo = o > bo ? o : bo;
+    peakkey::fold(d * peakkey::c(h), h, bo, bh);
 }
 
 __device__ __forceinline__ unsigned ss_r(unsigned k, unsigned j, int h) { return (k * j + (1u << (h - 1))) >> h; }  // k j < 2^26
-
-// the largest (smallest) value of a wave (all 64 lanes active), the same in every lane
-#define SS_DPP(op, ctrl) v = op(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, ctrl, 0xf, 0xf, false));
-#define SS_WAVE(name, op)                                                                    \
-    __device__ __forceinline__ unsigned name(unsigned v)                                     \
-    {                                                                                        \
-        SS_DPP(op, 0xB1)  /* quad_perm:[1,0,3,2] */                                          \
-        SS_DPP(op, 0x4E)  /* quad_perm:[2,3,0,1] */                                          \
-        SS_DPP(op, 0x141) /* row_half_mirror */                                              \
-        SS_DPP(op, 0x140) /* row_mirror */                                                   \
-        const unsigned r0 = (unsigned)__builtin_amdgcn_readlane((int)v, 0), r1 = (unsigned)__builtin_amdgcn_readlane((int)v, 16); \
-        const unsigned r2 = (unsigned)__builtin_amdgcn_readlane((int)v, 32), r3 = (unsigned)__builtin_amdgcn_readlane((int)v, 48); \
-        return op(op(r0, r1), op(r2, r3));                                                   \
-    }
-__device__ __forceinline__ unsigned ss_umax(unsigned a, unsigned b) { return a > b ? a : b; }
-__device__ __forceinline__ unsigned ss_umin(unsigned a, unsigned b) { return a < b ? a : b; }
-SS_WAVE(ss_wave_max, ss_umax)
-SS_WAVE(ss_wave_min, ss_umin)
 
 // rows of n2 float2 at pitch in_pitch floats -> rows of n2 float2
 __global__ __launch_bounds__(256) void k_ss_pack(const float2 *__restrict__ in, long long in_pitch2, float2 *__restrict__ out, long long total, int log2_n2)
@@ -134,7 +107,7 @@ struct SsArgs {
     long long units;  // series of the launch x tiles per series
 };
 
-// keys: the call's peaks buffer at the launch's first series, [series][block] 64-bit keys (k_ss_init has filled it)
+// keys: the call's peaks buffer at the launch's first series, [series][block] 64-bit keys (k_peak_init has filled it)
 __global__ __launch_bounds__(kSsThreads) void k_ss_tiled(const float *__restrict__ in, u64 *keys, const SsArgs a)
 {
     __shared__ __attribute__((aligned(16))) float lds[kSsLdsFloats];
@@ -213,11 +186,11 @@ __global__ __launch_bounds__(kSsThreads) void k_ss_tiled(const float *__restrict
                 const int first = __ffsll((long long)live) - 1;
                 const unsigned bref = (unsigned)__builtin_amdgcn_readlane((int)bl, first);
                 if (__ballot(o != 0 && bl != bref) == 0) {
-                    // one block: the largest ordered snr, then the smallest loc among the lanes that hold it
-                    const unsigned mo = ss_wave_max(o);
-                    const unsigned ml = ss_wave_min(o == mo ? loc : 0xFFFFFFFFu);
-                    if (lane == first) atomicMax(&lkeys[bref], ((u64)mo << 32) | (u64)(~ml));
-                } else if (o != 0) atomicMax(&lkeys[bl], ((u64)o << 32) | (u64)(~loc));
+                    // one block: the largest ordered snr, then the smallest loc among the lanes that hold it (as k_ps_tiled, k_ffa_pass)
+                    const unsigned mo = peakkey::wave_max(o);
+                    const unsigned ml = peakkey::wave_min(o == mo ? loc : 0xFFFFFFFFu);
+                    if (lane == first) atomicMax(&lkeys[bref], peakkey::key(mo, ml));
+                } else if (o != 0) atomicMax(&lkeys[bl], peakkey::key(o, loc));
             }
         }
         __syncthreads();
@@ -246,38 +219,18 @@ __global__ __launch_bounds__(256) void k_ss_gen(const float *__restrict__ in, u6
         }
         if (bo != 0) {
             const unsigned loc = (bh << 24) | (k & ((1u << log2_bb) - 1));
-            atomicMax(&keys[((size_t)s << (log2_nb - log2_bb)) + (size_t)(k >> log2_bb)], ((u64)bo << 32) | (u64)(~loc));
+            atomicMax(&keys[((size_t)s << (log2_nb - log2_bb)) + (size_t)(k >> log2_bb)], peakkey::key(bo, loc));
         }
     }
 }
 
-__global__ __launch_bounds__(256) void k_ss_init(u64 *keys, long long count, unsigned *counts)
-{
-    const long long first = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (counts && first == 0) { counts[0] = 0; counts[1] = 0; }
-    for (long long i = first; i < count; i += (long long)gridDim.x * 256) keys[i] = kSsEmpty;
-}
-
-// keys -> {float snr; uint32 loc} in place; records at or above the threshold -> {snr, loc, series, block}, counted in full
-__global__ __launch_bounds__(256) void k_ss_emit(u64 *peaks, long long count, int log2_nblk, float thr, uint2 *cands, long long max_cands,
-                                                 unsigned *counts)
-{
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < count; i += (long long)gridDim.x * 256) {
-        const u64 key = peaks[i];
-        const unsigned o = (unsigned)(key >> 32);
-        const unsigned bits = (o & 0x80000000u) ? (o ^ 0x80000000u) : ~o;
-        const unsigned loc = ~(unsigned)key;
-        peaks[i] = ((u64)loc << 32) | bits;
-        if (cands && __uint_as_float(bits) >= thr) {
-            const unsigned at = atomicAdd(&counts[0], 1u);
-            if ((long long)at < max_cands) {
-                atomicAdd(&counts[1], 1u);
-                cands[2 * (size_t)at] = make_uint2(bits, loc);
-                cands[2 * (size_t)at + 1] = make_uint2((unsigned)(i >> log2_nblk), (unsigned)(i & ((1ll << log2_nblk) - 1)));
-            }
-        }
+// record i of the [series][2^log2_nblk blocks] peaks buffer
+struct SsSplit {
+    __device__ __forceinline__ uint2 operator()(long long i, int log2_nblk) const
+    {
+        return make_uint2((unsigned)(i >> log2_nblk), (unsigned)(i & ((1ll << log2_nblk) - 1)));
     }
-}
+};
 
 struct SsShape {
     int S, N, H, Bb, k_lo, kind;
@@ -373,7 +326,7 @@ int ss_launch(mi355_ssearch *h, long long s0, long long nS, const void *in, long
     const SsShape &f = h->f;
     const long long nrec = nS * h->nblk;
     u64 *keys = (u64 *)peaks;
-    hipLaunchKernelGGL(k_ss_init, dim3(mi355_grid_256(h->ctx, nrec, 32)), dim3(256), 0, st, keys, nrec, cands ? (unsigned *)counts : nullptr);
+    hipLaunchKernelGGL(peakkey::k_peak_init<>, dim3(mi355_grid_256(h->ctx, nrec, 32)), dim3(256), 0, st, keys, nrec, cands ? (unsigned *)counts : nullptr);
     if (f.kind == MI355_SSEARCH_SPECTRUM) ss_sum(h, (const float *)in, in_pitch, nS, keys, st);
     else {
         int rc = h->ws.acquire(h->ws.bytes(), st);  // the size of _create: nothing is allocated here
@@ -401,17 +354,11 @@ int ss_launch(mi355_ssearch *h, long long s0, long long nS, const void *in, long
         }
         if ((rc = h->ws.release(st))) return rc;
     }
-    hipLaunchKernelGGL(k_ss_emit, dim3(mi355_grid_256(h->ctx, nrec, 32)), dim3(256), 0, st, keys, nrec, ss_log2(h->nblk), h->threshold, (uint2 *)cands,
+    hipLaunchKernelGGL(peakkey::k_peak_emit<SsSplit>, dim3(mi355_grid_256(h->ctx, nrec, 32)), dim3(256), 0, st, keys, nrec, ss_log2(h->nblk), h->threshold, (uint2 *)cands,
                        max_cands, (unsigned *)counts);
     MI355_HIP(hipGetLastError());
     if (f.kind == MI355_SSEARCH_SERIES) return h->stab.used(st);  // this version of the statistics may be released behind these launches
     return MI355_OK;
-}
-
-bool ss_overlap(const void *p, long long pb, const void *q, long long qb)
-{
-    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-    return a < b + (uintptr_t)qb && b < a + (uintptr_t)pb;
 }
 
 int ss_args(const mi355_ssearch *h, const void *in, long long in_pitch, const void *peaks, const void *spectrum, const void *cands,
@@ -425,11 +372,7 @@ int ss_args(const mi355_ssearch *h, const void *in, long long in_pitch, const vo
     MI355_REQUIRE((reinterpret_cast<uintptr_t>(peaks) & 7u) == 0, "peaks must be 8-byte aligned");
     MI355_REQUIRE((reinterpret_cast<uintptr_t>(spectrum) & 3u) == 0, "spectrum must be 4-byte aligned");
     MI355_REQUIRE(series || !spectrum, "a spectrum output with SPECTRUM input");
-    if (cands) {
-        MI355_REQUIRE(counts != nullptr, "cands without counts");
-        MI355_REQUIRE((reinterpret_cast<uintptr_t>(cands) & 7u) == 0, "cands must be 8-byte aligned");
-        MI355_REQUIRE((reinterpret_cast<uintptr_t>(counts) & 7u) == 0, "counts must be 8-byte aligned");
-    }
+    if (const int rc = peakkey::check_cands(cands, counts)) return rc;
     MI355_REQUIRE(in_pitch >= row, "in_pitch is below the floats of a series");
     MI355_REQUIRE(!series || (in_pitch & 1) == 0, "in_pitch must be even with SERIES input");
     if (in_pitch > kSsMaxBytes / (4 * S) || max_cands > kSsMaxBytes / 16) {
@@ -437,21 +380,15 @@ int ss_args(const mi355_ssearch *h, const void *in, long long in_pitch, const vo
         return MI355_ERR_UNSUPPORTED;
     }
     const long long ib = 4 * ((S - 1) * in_pitch + row), pb = 8 * S * h->nblk, sb = 4 * S * h->Nb, cb = 16 * max_cands;
-    MI355_REQUIRE(!ss_overlap(in, ib, peaks, pb), "clSpectralSearch does not work in place: in and peaks overlap");
+    MI355_REQUIRE(!mi355_overlap(in, ib, peaks, pb), "clSpectralSearch does not work in place: in and peaks overlap");
     if (spectrum) {
-        MI355_REQUIRE(!ss_overlap(in, ib, spectrum, sb), "in and spectrum overlap");
-        MI355_REQUIRE(!ss_overlap(peaks, pb, spectrum, sb), "peaks and spectrum overlap");
+        MI355_REQUIRE(!mi355_overlap(in, ib, spectrum, sb), "in and spectrum overlap");
+        MI355_REQUIRE(!mi355_overlap(peaks, pb, spectrum, sb), "peaks and spectrum overlap");
     }
-    if (cands) {
-        MI355_REQUIRE(max_cands == 0 || !ss_overlap(in, ib, cands, cb), "in and cands overlap");
-        MI355_REQUIRE(!ss_overlap(in, ib, counts, 8), "in and counts overlap");
-        MI355_REQUIRE(max_cands == 0 || !ss_overlap(peaks, pb, cands, cb), "peaks and cands overlap");
-        MI355_REQUIRE(!ss_overlap(peaks, pb, counts, 8), "peaks and counts overlap");
-        MI355_REQUIRE(max_cands == 0 || !ss_overlap(cands, cb, counts, 8), "cands and counts overlap");
-        if (spectrum) {
-            MI355_REQUIRE(max_cands == 0 || !ss_overlap(spectrum, sb, cands, cb), "spectrum and cands overlap");
-            MI355_REQUIRE(!ss_overlap(spectrum, sb, counts, 8), "spectrum and counts overlap");
-        }
+    if (const int rc = peakkey::check_cands_apart(in, ib, peaks, pb, cands, max_cands, counts)) return rc;
+    if (cands && spectrum) {
+        MI355_REQUIRE(max_cands == 0 || !mi355_overlap(spectrum, sb, cands, cb), "spectrum and cands overlap");
+        MI355_REQUIRE(!mi355_overlap(spectrum, sb, counts, 8), "spectrum and counts overlap");
     }
     return MI355_OK;
 }
@@ -635,9 +572,7 @@ extern "C" int mi355_ssearch_work(mi355_ssearch *h, const void *in, long long in
     if ((rc = h->d_in.reserve((size_t)(4 * row * piece)))) return rc;
     if ((rc = h->d_out.reserve((size_t)(piece * peak_bytes + 8 + cand_bytes + piece * spec_bytes)))) return rc;
     char *d_peaks = (char *)h->d_out.get(), *d_counts = d_peaks + piece * peak_bytes, *d_cands = d_counts + 8, *d_spec = d_cands + cand_bytes;
-    unsigned long long found = 0;
-    long long stored = 0;
-    std::vector<uint32_t> got;
+    peakkey::CandList list(cands, max_cands);
     rc = mi355_pageable_run(h->ctx, S, piece, [&](long long s0, long long ns, hipStream_t st) -> int {
         MI355_HIP(hipMemcpy2DAsync(h->d_in.get(), (size_t)(4 * row), (const float *)in + s0 * in_pitch, (size_t)(4 * in_pitch), (size_t)(4 * row), (size_t)ns,
                                    hipMemcpyHostToDevice, st));
@@ -646,28 +581,10 @@ extern "C" int mi355_ssearch_work(mi355_ssearch *h, const void *in, long long in
         if (lrc) return lrc;
         MI355_HIP(hipMemcpyAsync((char *)peaks + s0 * peak_bytes, d_peaks, (size_t)(ns * peak_bytes), hipMemcpyDeviceToHost, st));
         if (spectrum) MI355_HIP(hipMemcpyAsync((char *)spectrum + s0 * spec_bytes, d_spec, (size_t)(ns * spec_bytes), hipMemcpyDeviceToHost, st));
-        if (!cands) return MI355_OK;
-        uint32_t c[2] = {0, 0};
-        MI355_HIP(hipMemcpyAsync(c, d_counts, 8, hipMemcpyDeviceToHost, st));
-        MI355_HIP(hipStreamSynchronize(st));
-        found += c[0];
-        if (c[1]) {
-            got.resize(4 * (size_t)c[1]);
-            MI355_HIP(hipMemcpyAsync(got.data(), d_cands, 16 * (size_t)c[1], hipMemcpyDeviceToHost, st));
-            MI355_HIP(hipStreamSynchronize(st));
-            for (uint32_t i = 0; i < c[1] && stored < max_cands; i++, stored++) {
-                uint32_t *dst = (uint32_t *)cands + 4 * stored;
-                memcpy(dst, got.data() + 4 * (size_t)i, 16);
-                dst[2] += (uint32_t)s0;
-            }
-        }
-        return MI355_OK;
+        return cands ? list.append(d_counts, d_cands, peakkey::CandList::SERIES, s0, st) : MI355_OK;
     });
     if (rc) return rc;
-    if (cands) {
-        ((uint32_t *)counts)[0] = found > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)found;
-        ((uint32_t *)counts)[1] = (uint32_t)stored;
-    }
+    if (cands) list.finish(counts);
     return MI355_OK;
 }
 
